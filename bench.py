@@ -1,6 +1,6 @@
 """Benchmark of the AnyLoc-VLAD-DINOv2 hot path on MI355X (driver contract).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One *step* = one pass of the hot path over one batch of synthetic input, per rank:
     B query images (322x322, resident in HBM) -> DINOv2 ViT-G/14 layer-31 'value' tokens
@@ -335,6 +335,33 @@ def rccl_record(dist, world, legs, ms_per_step, legs_per_rank=None, overlapped=N
     return rec
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """``--dump-outputs DIR``: the arrays the timed path handed its caller in the LAST timed step, one ``DIR/<name>.npy``
+    each -- float32, or float64 for integer and float64 arrays (indices stay exact).  The arrays share their leading axis
+    (one row per query); past DUMP_BYTES in all, every array keeps the same fixed, seeded sample of those rows, whose row
+    numbers go to ``DIR/sample_rows.npy``."""
+    host = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        host[name] = a.astype(np.float64 if a.dtype.kind in "biu" or a.dtype == np.float64 else np.float32)
+    n = {a.shape[0] for a in host.values()}
+    assert len(n) == 1, {k: a.shape for k, a in host.items()}
+    n = n.pop()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BYTES:
+        keep = max(1, DUMP_BYTES // (total // n + 8))                # (+ 8 bytes a row: its number in sample_rows)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        host = {k: a[rows] for k, a in host.items()}
+        host["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return sorted(host)
+
+
 def main_config3(args):
     """BASELINE.json configs[2]: 10 000 query VLADs against a 1 M-row database sharded 125 000 rows (24.6 GB) per GPU.
     One step = the whole retrieval: query descriptors all-gathered over RCCL, per-shard normalise + top-20 on the HIP
@@ -395,6 +422,8 @@ def main_config3(args):
     if rank != 0:
         dist.destroy_process_group()
         return
+    if args.dump_outputs:                                                  # the merged top-k lists of the last timed step
+        dump_outputs(args.dump_outputs, {"topk_distances": results[-1][0], "topk_indices": results[-1][1]})
     idx = results[-1][1]
     idx = idx.cpu().numpy() if torch.is_tensor(idx) else np.asarray(idx)
     want = (np.arange(n_plant) * 17 + 5)                                  # rank 0's planted queries come first in the merged order
@@ -465,7 +494,13 @@ def main():
                          "10 000 queries against a database sharded 125 000 rows per GPU")
     ap.add_argument("--queries", type=int, default=10000, help="--workload config3: query VLADs of the whole job")
     ap.add_argument("--shard-rows", type=int, default=125000, help="--workload config3: database rows per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (top-k distances / indices, and the "
+                         "query VLADs at N = 1) as DIR/<name>.npy, float32 / float64, at most 64 MB in all; the inputs are "
+                         "seeded, so runs with the same arguments are comparable output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     os.environ["ANYLOC_GEMM"] = args.gemm
     if args.workload == "config3":
         return main_config3(args)
@@ -554,6 +589,9 @@ def main():
         rccl_legs_all = [None] * world
         dist.all_gather_object(rccl_legs_all, rccl_legs)
     timed_results = list(results)            # (the untimed steps below and the `modes` block re-use and clear `results`)
+    if args.dump_outputs and rank == 0:      # the last timed step: its query VLADs (N = 1) and the (merged) top-k lists
+        last = timed_results[-1]
+        dump_outputs(args.dump_outputs, dict(zip(("topk_distances", "topk_indices", "query_vlads"), last)))
     # Socket power / shader clock: sampled over EXTRA, untimed steps identical to the timed ones, right after them -- the
     # sampler reads the GPU's own hwmon nodes (an SMU query each), so it never runs while `value` is being measured
     sampler, power_timed = None, None

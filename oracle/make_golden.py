@@ -157,14 +157,40 @@ def golden_kmeans(ref):
     print("kmeans iters", vlad.kmeans.n_iter_)
 
 
-def main():
+def golden_reduce_pca(ref):
+    """Reference ``reduce_pca`` (numpy in / numpy out) on the seeded decaying-spectrum rows of
+    tests/test_host_logic.py: the plain, whitened and ``low_factor`` branches and the too-few-samples
+    fallback.  The inputs are stored next to the outputs (they come from a float64 QR, which is
+    not bit-stable across LAPACK builds)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_anyloc_test_host_logic", os.path.join(ROOT, "tests", "test_host_logic.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    tr, ts = mod._decaying(80, 48, seed=3, decay=0.92).numpy(), mod._decaying(9, 48, seed=4, decay=0.92).numpy()
+    fb_tr, fb_ts = mod._decaying(30, 64, seed=5, rank=20).numpy(), mod._decaying(8, 64, seed=6, rank=8).numpy()
+    out = dict(tr=tr, ts=ts, fb_tr=fb_tr, fb_ts=fb_ts)
+    for tag, kwargs in REDUCE_PCA_CASES.items():
+        out[f"{tag}_tr"], out[f"{tag}_ts"] = ref.reduce_pca(tr.copy(), ts.copy(), **kwargs)
+    out["fallback_tr"], out["fallback_ts"] = ref.reduce_pca(fb_tr.copy(), fb_ts.copy(), lower_dim=6, low_factor=0.5, fallback=16)
+    np.savez_compressed(os.path.join(GOLDEN, "reduce_pca_n80_d48.npz"), **out)
+    print("reduce_pca:", {k: v.shape for k, v in out.items()})
+
+
+# the keyword sets of tests/test_host_logic.py::test_reduce_pca_surface_matches_reference_function
+REDUCE_PCA_CASES = {"plain": dict(lower_dim=10), "whiten": dict(lower_dim=10, whitening=True),
+                    "low": dict(lower_dim=10, low_factor=0.3)}
+RECORDERS = {"config1": golden_config1, "vlad_shapes": golden_vlad_shapes, "kmeans": golden_kmeans,
+             "reduce_pca": golden_reduce_pca}
+
+
+def main(names=None):
+    """Record every fixture, or only the ones named on the command line (``python -m oracle.make_golden reduce_pca``)."""
     os.makedirs(GOLDEN, exist_ok=True)
     torch.set_num_threads(max(1, os.cpu_count() or 1))
     ref = ref_loader.load_reference_utilities("root")
-    golden_config1(ref)
-    golden_vlad_shapes(ref)
-    golden_kmeans(ref)
+    for name in names or RECORDERS:
+        RECORDERS[name](ref)
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])

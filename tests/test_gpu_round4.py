@@ -1,6 +1,6 @@
 """Round-4 GPU tests: retrieval index identity at the full BASELINE.json configs[1] size and on one configs[2] panel
 against an exact float64 search, the host <-> device transfers, the reference scripts' CPU-tensor call pattern through
-``VLAD.generate_multi`` / ``get_top_k_recall``, and an 8-rank run of ``bench.py --workload config3`` on one GPU."""
+``VLAD.generate_multi`` / ``get_top_k_recall``, and a 4-rank run of ``bench.py --workload config3`` on one GPU."""
 import json
 import os
 import subprocess
@@ -135,23 +135,25 @@ def test_cpu_tensor_call_pattern_equals_the_device_path():
     assert r1 == r2 and r1[1] == 1.0
 
 
-def test_bench_config3_eight_ranks_on_one_gpu():
-    """``bench.py --workload config3 --gpus 8`` at a reduced shard (8 x 2 048 rows, 512 queries) with the ranks sharing the one
-    GPU over gloo: the query all-gather with static counts, eight per-shard searches with global indices, the single packed
-    gather and the host merge -- the planted neighbour of every rank-0 query is found in ITS shard."""
+def test_bench_config3_four_ranks_on_one_gpu():
+    """``bench.py --workload config3 --gpus 4`` at a reduced shard (4 x 2 048 rows, 512 queries) with the ranks sharing the one
+    GPU over gloo: the query all-gather with static counts, four per-shard searches with global indices, the single packed
+    gather and the host merge -- the planted neighbour of every rank-0 query is found in ITS shard.  Four ranks, not the
+    eight of configs[2]: with this test process they are five processes holding the one GPU, and the suite keeps that
+    number at six or fewer."""
     env = dict(os.environ, ANYLOC_DIST_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "config3", "--gpus", "8", "--steps", "1",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "config3", "--gpus", "4", "--steps", "1",
                           "--warmup", "0", "--queries", "512", "--shard-rows", "2048"], env=env, capture_output=True, text=True,
                          timeout=1500)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]
     out = json.loads(lines[0])
-    assert out["n_gpus"] == 8 and out["unit"] == "queries/s" and out["value"] > 0
+    assert out["n_gpus"] == 4 and out["unit"] == "queries/s" and out["value"] > 0
     assert out["planted_neighbours_found"] is True
-    assert out["config"]["db_rows_total"] == 8 * 2048 and out["config"]["queries"] == 512
+    assert out["config"]["db_rows_total"] == 4 * 2048 and out["config"]["queries"] == 512
 
 
 # ---------------------------------------------------------------------------------- few-query scores, running row scale
@@ -258,7 +260,8 @@ def test_reference_call_pattern_driver_through_anyloc_amd_run(tmp_path):
     torchvision transforms through the shims, one image per extractor call with ``.to(device)`` / ``.cpu()``, ``VLAD.fit`` +
     ``generate_multi`` with cache ids (``c_centers.pt``, ``_r/_l`` files), ``get_top_k_recall`` on CPU tensors -- twice: the
     second run restores the vocabulary and the VLADs from the cache and must print the same recalls and top-1 indices.
-    (The reference's own script runs the same way wherever its tree exists: tests/test_gpu_round3.py.)"""
+    (The reference's own script runs unmodified on the CPU oracle backend in tests/test_reference_scripts_cpu.py, and on the
+    HIP path through tools/reference_scripts_on_hip.py wherever its tree exists.)"""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import make_synth_dataset
     make_synth_dataset.write(str(tmp_path / "data"), "st_lucia", n_db=6, n_qu=4, h=112, w=140)

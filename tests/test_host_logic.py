@@ -223,29 +223,28 @@ def test_pca_host_logic_matches_sklearn(monkeypatch, shape, k, whiten):
     assert np.abs(got_ts.numpy() - want_ts).max() < 1e-4 * max(scale, np.abs(want_ts).max())
 
 
-def test_reduce_pca_surface_matches_reference_function(monkeypatch, capsys):
+def test_reduce_pca_surface_matches_reference_function(monkeypatch, capsys, golden_dir):
     """utilities.reduce_pca (numpy in / numpy out, low_factor and fallback branches) against the reference's own
-    function imported verbatim (utilities.py:522-586)."""
+    function (utilities.py:522-586), whose outputs on the same inputs tests/golden/reduce_pca_n80_d48.npz holds
+    (recorded by ``python -m oracle.make_golden reduce_pca``)."""
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import _oracle_backend
-    from oracle import ref_loader
-    if not ref_loader.reference_available():
-        pytest.skip("reference tree not present")
     import utilities
-    ref = ref_loader.load_reference_utilities()
+    from oracle.make_golden import REDUCE_PCA_CASES
+    g = np.load(os.path.join(golden_dir, "reduce_pca_n80_d48.npz"))
     _oracle_backend.install(monkeypatch)
-    tr, ts = _decaying(80, 48, seed=3, decay=0.92).numpy(), _decaying(9, 48, seed=4, decay=0.92).numpy()
-    for kwargs in (dict(lower_dim=10), dict(lower_dim=10, whitening=True), dict(lower_dim=10, low_factor=0.3)):
+    tr, ts = g["tr"], g["ts"]
+    for tag, kwargs in REDUCE_PCA_CASES.items():
         a_tr, a_ts = utilities.reduce_pca(tr, ts, **kwargs)
-        b_tr, b_ts = ref.reduce_pca(tr.copy(), ts.copy(), **kwargs)
+        b_tr, b_ts = g[f"{tag}_tr"], g[f"{tag}_ts"]
         assert isinstance(a_tr, np.ndarray) and a_tr.shape == b_tr.shape and a_ts.shape == b_ts.shape
         m = np.abs(b_tr).max()
         assert np.abs(a_tr - b_tr).max() < 2e-4 * m and np.abs(a_ts - b_ts).max() < 2e-4 * m, kwargs
     # too few samples: joint projection to `fallback` dims first (reference :566-574)
-    tr, ts = _decaying(30, 64, seed=5, rank=20).numpy(), _decaying(8, 64, seed=6, rank=8).numpy()
+    tr, ts = g["fb_tr"], g["fb_ts"]
     a_tr, a_ts = utilities.reduce_pca(tr, ts, lower_dim=6, low_factor=0.5, fallback=16)
-    b_tr, b_ts = ref.reduce_pca(tr.copy(), ts.copy(), lower_dim=6, low_factor=0.5, fallback=16)
+    b_tr, b_ts = g["fallback_tr"], g["fallback_ts"]
     assert "Too few samples, fallback to 16d first" in capsys.readouterr().out
     assert a_tr.shape == b_tr.shape == (30, 6) and a_ts.shape == (8, 6)
     # the lowest-variance axes of a rank-deficient matrix are not unique: compare the well-defined top half

@@ -1,6 +1,8 @@
 """The reference's scripts run UNMODIFIED on top of our ``utilities`` surface
-(``python -m anyloc_amd.run <script>``).  Needs /root/reference (build container only, skipped
-elsewhere) and no GPU: the device entry points are swapped for the CPU oracle
+(``python -m anyloc_amd.run <script>``).  The tests that run the reference's own scripts need the
+reference tree (``oracle.ref_loader.REFERENCE_ROOT``, set by ``ANYLOC_REFERENCE_ROOT``; skipped where it
+is absent -- its sources are never copied here); the stand-in driver test at the end runs everywhere.
+No GPU: the device entry points are swapped for the CPU oracle
 (tests/_oracle_backend.py), so this pins the host-side contract -- CLI parsing through the
 stand-in tyro, dataset loader -> extractor -> VLAD.fit / generate_multi -> get_top_k_recall,
 cache files, ``.npy`` outputs -- against what the reference's own drivers expect."""
@@ -13,10 +15,11 @@ import torch
 
 from anyloc_amd import run as launcher, synth, weights
 
-REF = os.environ.get("ANYLOC_REFERENCE_ROOT", "/root/reference")
-pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "scripts", "dino_v2_vlad.py")),
-                                reason="reference tree not present")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from oracle.ref_loader import REFERENCE_ROOT as REF  # noqa: E402
+
+needs_reference = pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "scripts", "dino_v2_vlad.py")),
+                                     reason="reference tree not present")
 
 
 @pytest.fixture()
@@ -38,6 +41,7 @@ def cpu_backend(monkeypatch):
             sys.modules.pop(m, None)
 
 
+@needs_reference
 def test_dino_v2_vlad_script_unmodified(cpu_backend, tmp_path, capsys):
     sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tools"))
     import make_synth_dataset
@@ -67,6 +71,7 @@ def test_dino_v2_vlad_script_unmodified(cpu_backend, tmp_path, capsys):
     assert "c_centers.pt" in pts and any(f.endswith("_r.pt") for f in pts) and any(f.endswith("_l.pt") for f in pts)
 
 
+@needs_reference
 def test_global_vocab_script_unmodified(cpu_backend, tmp_path, capsys):
     """scripts/dino_v2_global_vocab_vlad.py (the caller of VLAD.fit that builds the shared
     vocabularies): vocabulary from a pool of datasets' database images ->
@@ -109,6 +114,7 @@ def _run_recall_script(script, extra, tmp_path, capsys, n_db=5, n_qu=3):
     return out
 
 
+@needs_reference
 @pytest.mark.parametrize("method", ["average", "max"])
 def test_global_pooling_script_unmodified(cpu_backend, tmp_path, capsys, method):
     """scripts/dino_v2_gp.py: extractor -> torch mean/max over tokens -> get_top_k_recall."""
@@ -117,12 +123,14 @@ def test_global_pooling_script_unmodified(cpu_backend, tmp_path, capsys, method)
     assert "Generated pooled descriptors" in out and "R@1" in out
 
 
+@needs_reference
 def test_gem_script_unmodified(cpu_backend, tmp_path, capsys):
     out = _run_recall_script("dino_v2_gem.py", ["--desc-layer", "9", "--desc-facet", "value", "--gem-p", "3"],
                              tmp_path, capsys)
     assert "Database GeMs shape: torch.Size([5, 384])" in out and "R@1" in out
 
 
+@needs_reference
 def test_cls_global_descriptor_script_unmodified(cpu_backend, tmp_path, capsys):
     """scripts/dino_v2_global_vpr.py calls torch.hub.load itself and uses the model's CLS output: the launcher's
     hub stand-in hands it our model object (all 12 blocks + final norm)."""
@@ -130,6 +138,7 @@ def test_cls_global_descriptor_script_unmodified(cpu_backend, tmp_path, capsys):
     assert "R@1" in out or "Recall" in out
 
 
+@needs_reference
 def test_demo_vlad_generate_unmodified(cpu_backend, tmp_path, capsys, monkeypatch):
     from PIL import Image
     in_dir, out_dir = tmp_path / "imgs", tmp_path / "out"
