@@ -118,13 +118,21 @@ SIGNATURES = {
     "anyloc_vit_forward": (C.c_int, [C.c_void_p, c_f32p, c_i64, c_i64, c_i64, c_f32p, C.c_int32,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint, c_f32p,
                                      C.c_void_p, c_sz, C.c_void_p]),
+    "anyloc_vit_workspace_bytes_ragged": (c_sz, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "anyloc_vit_forward_ragged": (C.c_int, [C.c_void_p, c_f32p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, c_f32p,
+                                            C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint, c_f32p,
+                                            C.c_void_p, c_sz, C.c_void_p]),
+    "anyloc_attention_ragged": (C.c_int, [c_f32p, c_f32p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, c_i64, c_i64,
+                                          C.c_void_p]),
+    "anyloc_attention_h3_ragged": (C.c_int, [c_f32p, C.c_void_p, c_f32p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p,
+                                             c_i64, c_i64, C.c_void_p, c_sz, C.c_void_p]),
     "anyloc_profile_enable": (C.c_int, [C.c_int]),
     "anyloc_profile_filter": (C.c_int, [C.c_char_p]),
     "anyloc_profile_reset": (C.c_int, []),
     "anyloc_profile_dump": (C.c_int, [C.c_char_p, c_sz]),
 }
 
-ABI_VERSION = 9          # include/anyloc_hip.h ANYLOC_ABI_VERSION the structs and signatures above were written for
+ABI_VERSION = 10         # include/anyloc_hip.h ANYLOC_ABI_VERSION the structs and signatures above were written for
 
 _lib = None
 

@@ -31,10 +31,12 @@ constexpr int KLD = HD + 4;   // padded K row (ds_read_b128 conflict-free)
 //          the MFMA chains that consume them (2 waves/SIMD instead of 3, but no LDS wait inside a chain)
 // OUT3: the output is written as the three-plane bf16 image (x3 layout of gemm_x6.hip, R = batch*T rows) that the
 // projection GEMM reads, instead of fp32
-template <int WB, bool FASTEXP, bool PRELOAD, bool OUT3 = false>
+// RAGGED: images of different lengths packed back to back -- image b owns rows tok_off[b] .. tok_off[b + 1], T is the longest
+// image (grid), query tiles past an image's end exit (the uniform instantiations ignore tok_off)
+template <int WB, bool FASTEXP, bool PRELOAD, bool OUT3 = false, bool RAGGED = false>
 __global__ __launch_bounds__(64 * WB, PRELOAD ? 2 : 1) void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                             int T, int D, float scale, unsigned char* __restrict__ out3,
-                                                            int64_t R3) {
+                                                            int64_t R3, const int64_t* __restrict__ tok_off) {
   constexpr int NT = 64 * WB;
   constexpr int RPP = NT / 16;          // K/V rows staged per pass (16 lanes per 256-byte row)
   constexpr int NLD = KT / RPP;         // staging passes per tile
@@ -45,7 +47,13 @@ __global__ __launch_bounds__(64 * WB, PRELOAD ? 2 : 1) void attention_kernel(con
   const int h = blockIdx.y;
   const int64_t b = blockIdx.z;
   const int64_t ld = 3 * (int64_t)D;
-  const float* base = qkv + b * T * ld;
+  int64_t rb = b * T;                   // first row of the image
+  if constexpr (RAGGED) {
+    rb = tok_off[b];
+    T = (int)(tok_off[b + 1] - rb);
+    if ((int)blockIdx.x * (32 * WB) >= T) return;    // (workgroup-uniform)
+  }
+  const float* base = qkv + rb * ld;
   const int q0 = blockIdx.x * (32 * WB) + wave * 32;
   const int ql = lane & 31, h2 = lane >> 5;
   const bool wave_active = q0 < T;
@@ -173,7 +181,7 @@ __global__ __launch_bounds__(64 * WB, PRELOAD ? 2 : 1) void attention_kernel(con
   // oacc[db][r] = O[q0+ql][db*32 + (r&3) + 8*(r>>2) + 4*h2]  ->  float4 per (db, r>>2)
   if (wave_active && q0 + ql < T) {
     const float inv = 1.0f / l_run;
-    const int64_t row = b * T + q0 + ql;
+    const int64_t row = rb + q0 + ql;
     float* op = out + row * (int64_t)D + h * HD + 4 * h2;
 #pragma unroll
     for (int db = 0; db < 2; ++db)
@@ -232,10 +240,10 @@ __device__ __forceinline__ void split4(const f32x4 v, unsigned pk[3][2]) {
 #define ANYLOC_MFMA_BF16(a, b, c) \
   __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(attn_bf16x8, a), __builtin_bit_cast(attn_bf16x8, b), c, 0, 0, 0)
 
-template <bool OUT3>
+template <bool OUT3, bool RAGGED = false>
 __global__ __launch_bounds__(256, 2) void attention_x6_kernel(const float* __restrict__ qkv, float* __restrict__ out, int T,
                                                               int D, float scale, unsigned char* __restrict__ out3,
-                                                              int64_t R3) {
+                                                              int64_t R3, const int64_t* __restrict__ tok_off) {
   __shared__ __attribute__((aligned(16))) unsigned char Ks[2][3][KT * KROW];
   __shared__ __attribute__((aligned(16))) unsigned char Vs[2][3][HD * VROW];
 
@@ -243,7 +251,13 @@ __global__ __launch_bounds__(256, 2) void attention_x6_kernel(const float* __res
   const int h = blockIdx.y;
   const int64_t b = blockIdx.z;
   const int64_t ld = 3 * (int64_t)D;
-  const float* base = qkv + b * T * ld;
+  int64_t rb = b * T;                   // first row of the image (RAGGED: as attention_kernel)
+  if constexpr (RAGGED) {
+    rb = tok_off[b];
+    T = (int)(tok_off[b + 1] - rb);
+    if ((int)blockIdx.x * 128 >= T) return;
+  }
+  const float* base = qkv + rb * ld;
   const int q0 = blockIdx.x * 128 + wave * 32;
   const int ql = lane & 31, h2 = lane >> 5;
   const bool wave_active = q0 < T;
@@ -400,7 +414,7 @@ __global__ __launch_bounds__(256, 2) void attention_x6_kernel(const float* __res
   // oacc[db][r] = O[q0+ql][db*32 + (r&3) + 8*(r>>2) + 4*h2]
   if (wave_active && q0 + ql < T) {
     const float inv = 1.0f / l_run;
-    const int64_t row = b * T + q0 + ql;
+    const int64_t row = rb + q0 + ql;
     float* op = out + row * (int64_t)D + h * HD + 4 * h2;
 #pragma unroll
     for (int db = 0; db < 2; ++db)
@@ -469,11 +483,16 @@ constexpr int AH_STAGE = 16384;       // K hi | K lo | V hi | V lo, 4 KiB each
 // KS = 2 (few images per call): every step stages KS consecutive key tiles, key wave kw takes tile KS * step + kw, and the
 // key waves' partial (O, m, l) meet in LDS at the end in split order -- twice the workgroups and half the serial chain of
 // key tiles per wave: one ViT-g image is 24 heads x 5 workgroups x 17 tiles with KS = 1, 24 x 9 x 9 with KS = 2.
-template <int QG, int NW, int KS = 1>
+// RAGGED (1, 2): image b owns the rows tok_off[b] .. tok_off[b + 1]; QB comes from the longest image and workgroups past an
+// image's last query group exit (the uniform instantiations, RAGGED = 0, ignore tok_off).  RAGGED = 1 keeps the uniform
+// kernel's order (a contiguous range of (image, head) units per XCD); RAGGED = 2 deals the units round-robin over the 8 XCDs
+// (unit u on XCD u % 8, its QB workgroups consecutive there) so that every XCD gets its share of every image: the images'
+// costs differ (T_i^2), and contiguous ranges of them load the XCDs unevenly.  RAGGED = 2 passes the number of images as T.
+template <int QG, int NW, int KS = 1, int RAGGED = 0>
 __global__ __launch_bounds__(64 * NW, 2) void attention_h3_kernel(const unsigned char* __restrict__ planes,
                                                                   const float* __restrict__ inv, int T, int heads, int64_t G,
                                                                   unsigned char* __restrict__ out2, float* __restrict__ out_inv,
-                                                                  int64_t R, int QB) {
+                                                                  int64_t R, int QB, const int64_t* __restrict__ tok_off) {
   static_assert((QG == 1 || QG == 2) && (KS == 1 || KS == 2) && NW % KS == 0 && 16 * KS % NW == 0, "unsupported shape");
   constexpr int NT = 64 * NW;
   constexpr int QW = NW / KS;           // query waves
@@ -482,12 +501,25 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_h3_kernel(const unsigned
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // 1-D grid, XCD-aware: the QB workgroups of one (image, head) -- which stream the same K / V tiles, 271 KB at T = 530 -- get
   // consecutive ids on ONE XCD, so the tiles come from HBM / the fabric into that XCD's L2 once instead of once per XCD
-  const int logical = xcd_contiguous_id((int)blockIdx.x, (int)gridDim.x);
-  const int qb = logical % QB, h = (logical / QB) % heads;
-  const int64_t b = logical / (QB * heads);
-  const int64_t r0 = b * T, r1 = r0 + T;
+  int qb, h;
+  int64_t b;
+  if constexpr (RAGGED == 2) {
+    const int xcd = (int)blockIdx.x & 7, loc = (int)blockIdx.x >> 3;
+    const int64_t u = xcd + 8 * (int64_t)(loc / QB);
+    qb = loc % QB;
+    h = (int)(u % heads);
+    b = u / heads;
+    if (b >= T) return;                 // (the grid is padded to whole rounds of 8 units; workgroup-uniform)
+  } else {
+    const int logical = xcd_contiguous_id((int)blockIdx.x, (int)gridDim.x);
+    qb = logical % QB;
+    h = (logical / QB) % heads;
+    b = logical / (QB * heads);
+  }
+  const int64_t r0 = RAGGED ? tok_off[b] : b * T, r1 = RAGGED ? tok_off[b + 1] : r0 + T;
   const int64_t g_first = r0 >> 5, g_last = (r1 - 1) >> 5;
   const int ng = (int)(g_last - g_first + 1);
+  if (RAGGED && g_first + (int64_t)qb * QW * QG > g_last) return;          // (workgroup-uniform: no query group of its own)
   const int qw = KS == 1 ? wave : wave % QW, kw = KS == 1 ? 0 : wave / QW;   // (KS = 1 compiles to the unsplit kernel)
   const int64_t gq0 = g_first + (qb * QW + qw) * QG;
   const bool wave_active = gq0 <= g_last;
@@ -839,7 +871,7 @@ int attention_h3(const unsigned char* planes, const float* inv, int64_t batch, i
     const size_t lds2 = 4 * AH_STAGE + 64;
     static DynLds dyn_lds_once;                          // (per device: a process may drive several GPUs)
     ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(attention_h3_kernel<1, 4, 2>), (int)lds2));
-    hipLaunchKernelGGL((attention_h3_kernel<1, 4, 2>), grid2, dim3(256), lds2, stream, planes, inv, T, heads, G, out2, out_inv, R, QB2);
+    hipLaunchKernelGGL((attention_h3_kernel<1, 4, 2>), grid2, dim3(256), lds2, stream, planes, inv, T, heads, G, out2, out_inv, R, QB2, nullptr);
     return launch_status("attention_h3_kernel<1,4,2>");
   }
   const int QB = (qgroups + 3) / 4;                         // workgroups (of four 32-query groups) per image and head
@@ -848,10 +880,10 @@ int attention_h3(const unsigned char* planes, const float* inv, int64_t batch, i
   // option attn_h3_qg = 2 (A/B): two waves of 64 queries per workgroup -- a wave's K / V fragments serve 64 queries (half the
   // LDS reads, DMA issues and barriers per unit of work) at one wave per SIMD and workgroup
   if (option(OPT_ATTN_H3_QG) == 2) {
-    hipLaunchKernelGGL((attention_h3_kernel<2, 2>), grid, dim3(128), lds, stream, planes, inv, T, heads, G, out2, out_inv, R, QB);
+    hipLaunchKernelGGL((attention_h3_kernel<2, 2>), grid, dim3(128), lds, stream, planes, inv, T, heads, G, out2, out_inv, R, QB, nullptr);
     return launch_status("attention_h3_kernel<2,2>");
   }
-  hipLaunchKernelGGL((attention_h3_kernel<1, 4>), grid, dim3(256), lds, stream, planes, inv, T, heads, G, out2, out_inv, R, QB);
+  hipLaunchKernelGGL((attention_h3_kernel<1, 4>), grid, dim3(256), lds, stream, planes, inv, T, heads, G, out2, out_inv, R, QB, nullptr);
   return launch_status("attention_h3_kernel");
 }
 
@@ -870,21 +902,86 @@ int attention(const float* qkv, float* out, int64_t batch, int T, int D, int hea
   // option attn_x6: 1 = split-bf16 kernel for every call (kernel tests), 0 = never, -1 (default) = when the caller asks
   if (option(OPT_ATTN_X6) >= 0) x6 = option(OPT_ATTN_X6) != 0;
   if (x6) {
-    if (out3) hipLaunchKernelGGL((attention_x6_kernel<true>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3);
-    else hipLaunchKernelGGL((attention_x6_kernel<false>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3);
+    if (out3) hipLaunchKernelGGL((attention_x6_kernel<true>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3, nullptr);
+    else hipLaunchKernelGGL((attention_x6_kernel<false>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3, nullptr);
     return launch_status("attention_x6_kernel");
   }
   if (out3) {
-    hipLaunchKernelGGL((attention_kernel<4, true, true, true>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3);
+    hipLaunchKernelGGL((attention_kernel<4, true, true, true>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3, nullptr);
     return launch_status("attention_kernel");
   }
   switch (cfg) {
-    case 1: hipLaunchKernelGGL((attention_kernel<4, false, false>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3); break;
-    case 2: hipLaunchKernelGGL((attention_kernel<4, true, false>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3); break;
-    case 3: hipLaunchKernelGGL((attention_kernel<4, false, true>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3); break;
-    default: hipLaunchKernelGGL((attention_kernel<4, true, true>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3); break;
+    case 1: hipLaunchKernelGGL((attention_kernel<4, false, false>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3, nullptr); break;
+    case 2: hipLaunchKernelGGL((attention_kernel<4, true, false>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3, nullptr); break;
+    case 3: hipLaunchKernelGGL((attention_kernel<4, false, true>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3, nullptr); break;
+    default: hipLaunchKernelGGL((attention_kernel<4, true, true>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3, nullptr); break;
   }
   return launch_status("attention_kernel");
+}
+
+int attention_h3_ragged(const unsigned char* planes, const float* inv, int n_img, int max_T, const int64_t* tok_off, int64_t rows,
+                        int D, int heads, unsigned char* out2, float* out_inv, hipStream_t stream) {
+  ANYLOC_CHECK_ARG(planes && inv && out2 && out_inv && tok_off, "attention_h3: null pointer");
+  ANYLOC_CHECK_ARG(D == heads * HD, "attention_h3: head_dim must be 64 (D=%d heads=%d)", D, heads);
+  ANYLOC_CHECK_ARG(max_T > 0 && n_img > 0 && n_img < 65536 && rows >= max_T, "attention_h3: bad T/batch");
+  const int64_t G = (rows + 31) / 32;
+  ANYLOC_CHECK_ARG((int64_t)heads * G * 8192 < (1ll << 31), "attention_h3: operand tiles exceed the 2 GiB buffer-addressing range");
+  ProfScope prof("attention", stream, 4.0 * heads * (double)rows * max_T * HD, 8.0 * rows * D * 2);
+  // the grid of the uniform launcher for n_img images of the longest length (same workgroup shapes, same KS rule); the
+  // workgroups of a shorter image past its last query group exit at once.  Option attn_h3_ragged_xcd (1, default): the
+  // (image, head) units dealt round-robin over the XCDs, grid padded to whole rounds of 8 units; 0: the uniform order
+  const int qgroups = (max_T + 31) / 32 + 1;
+  const int QB2 = (qgroups + 1) / 2;
+  const int64_t units = (int64_t)heads * n_img;
+  const bool deal = option(OPT_ATTN_H3_RAGGED_XCD) != 0;
+  const int64_t slots = deal ? (units + 7) / 8 * 8 : units;
+  const int targ = deal ? n_img : max_T;
+  const int64_t ks_opt = option(OPT_ATTN_H3_KS);
+  if (ks_opt == 2 || (ks_opt == 0 && (int64_t)QB2 * units <= 512)) {
+    const size_t lds2 = 4 * AH_STAGE + 64;
+    const dim3 grid2((unsigned)((int64_t)QB2 * slots));
+    if (deal) {
+      static DynLds dyn_lds_deal;
+      ANYLOC_TRY(ensure_dyn_lds(dyn_lds_deal, reinterpret_cast<const void*>(attention_h3_kernel<1, 4, 2, 2>), (int)lds2));
+      hipLaunchKernelGGL((attention_h3_kernel<1, 4, 2, 2>), grid2, dim3(256), lds2, stream, planes, inv, targ, heads, G, out2,
+                         out_inv, rows, QB2, tok_off);
+    } else {
+      static DynLds dyn_lds_once;
+      ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(attention_h3_kernel<1, 4, 2, 1>), (int)lds2));
+      hipLaunchKernelGGL((attention_h3_kernel<1, 4, 2, 1>), grid2, dim3(256), lds2, stream, planes, inv, targ, heads, G, out2,
+                         out_inv, rows, QB2, tok_off);
+    }
+    return launch_status("attention_h3_kernel<1,4,2,ragged>");
+  }
+  const int QB = (qgroups + 3) / 4;
+  ANYLOC_CHECK_ARG((int64_t)QB * slots < (1ll << 31), "attention_h3: grid too large");
+  const dim3 grid((unsigned)((int64_t)QB * slots));
+  if (deal)
+    hipLaunchKernelGGL((attention_h3_kernel<1, 4, 1, 2>), grid, dim3(256), 2 * AH_STAGE + 64, stream, planes, inv, targ, heads, G,
+                       out2, out_inv, rows, QB, tok_off);
+  else
+    hipLaunchKernelGGL((attention_h3_kernel<1, 4, 1, 1>), grid, dim3(256), 2 * AH_STAGE + 64, stream, planes, inv, targ, heads, G,
+                       out2, out_inv, rows, QB, tok_off);
+  return launch_status("attention_h3_kernel<ragged>");
+}
+
+int attention_ragged(const float* qkv, float* out, int n_img, int max_T, const int64_t* tok_off, int64_t rows, int D, int heads,
+                     hipStream_t stream, unsigned char* out3, bool x6) {
+  ANYLOC_CHECK_ARG(D == heads * HD, "attention: head_dim must be 64 (D=%d heads=%d)", D, heads);
+  ANYLOC_CHECK_ARG(qkv && tok_off && (out || out3) && max_T > 0 && n_img > 0 && n_img < 65536, "attention: bad T/batch");
+  ProfScope prof("attention", stream, 4.0 * heads * (double)rows * max_T * HD, 16.0 * rows * D);
+  const dim3 g4((max_T + 127) / 128, heads, (unsigned)n_img);
+  if (option(OPT_ATTN_X6) >= 0) x6 = option(OPT_ATTN_X6) != 0;
+  if (x6) {
+    if (out3) hipLaunchKernelGGL((attention_x6_kernel<true, true>), g4, dim3(256), 0, stream, qkv, out, max_T, D, 0.125f, out3, rows, tok_off);
+    else hipLaunchKernelGGL((attention_x6_kernel<false, true>), g4, dim3(256), 0, stream, qkv, out, max_T, D, 0.125f, out3, rows, tok_off);
+    return launch_status("attention_x6_kernel<ragged>");
+  }
+  if (out3)
+    hipLaunchKernelGGL((attention_kernel<4, true, true, true, true>), g4, dim3(256), 0, stream, qkv, out, max_T, D, 0.125f, out3, rows, tok_off);
+  else
+    hipLaunchKernelGGL((attention_kernel<4, true, true, false, true>), g4, dim3(256), 0, stream, qkv, out, max_T, D, 0.125f, out3, rows, tok_off);
+  return launch_status("attention_kernel<ragged>");
 }
 
 }  // namespace anyloc

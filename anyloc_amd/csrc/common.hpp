@@ -99,6 +99,7 @@ enum Option {
   OPT_H3_LN_LEAD,        // batched calls: LayerNorm as lead workgroups interleaved with its consumer GEMM's tiles (LN1 + qkv, LN2 + fc1 / w12); 0 = two launches
   OPT_VLAD_GATHER_V,     // one-pass VLAD kernel at D = 1536: variants of the register-indexed gather kept for the hazard study (0 = shipped)
   OPT_TOPK_SCREEN,       // many-query retrieval: score panels on the leading fp16 planes + exact re-scoring of the rows inside the bound (scores_screen.hip): -1 = where it pays, 0 = never, 1 = wherever possible
+  OPT_ATTN_H3_RAGGED_XCD, // ragged attention_h3: 1 = (image, head) units dealt round-robin over the XCDs, 0 = the uniform kernel's contiguous ranges
   OPT_COUNT
 };
 int64_t option(Option o);
@@ -356,6 +357,26 @@ int facet_rows(const float* src, int64_t lds_, int coff, float* out, int64_t ldo
 int attention(const float* qkv, float* out, int64_t batch, int T, int D, int heads,
               hipStream_t stream, unsigned char* out3 = nullptr,    // out3: write the result as a plane image instead
               bool x6 = false);                                      // x6: split-bf16 matrix products
+
+// ragged batches (anyloc_vit_forward_ragged): the device table `meta` is int64 [RAGGED_ROWS][n_img + 1], row-major --
+//   RAGGED_TOK: token-row offsets (T_i = N_i + 1 rows per image, CLS first), entry n_img = total rows
+//   RAGGED_PIX: float offset of image i in the packed CHW input, RAGGED_POS: first row of image i's positional table in the
+//   packed tables, RAGGED_H / RAGGED_W: the image size (last entry of these three unused)
+enum { RAGGED_TOK = 0, RAGGED_PIX = 1, RAGGED_POS = 2, RAGGED_H = 3, RAGGED_W = 4, RAGGED_ROWS = 5 };
+int im2col_ragged(const float* img, float* col, const int64_t* meta, int n_img, int64_t patch_rows, int P, int kpad,
+                  hipStream_t stream);
+int embed_ragged(float* x, const float* patch, const float* cls, const float* pos, const int64_t* meta, int n_img, int64_t rows,
+                 int dim, hipStream_t stream);
+int facet_rows_ragged(const float* src, int64_t lds_, int coff, float* out, int64_t ldo, int ooff, const int64_t* meta,
+                      int n_img, int64_t out_rows, int skip, int dim, int normalize, float eps, hipStream_t stream);
+// attention over images of different lengths: tok_off = device [n_img + 1] row offsets, max_T the longest image
+int attention_ragged(const float* qkv, float* out, int n_img, int max_T, const int64_t* tok_off, int64_t rows, int D, int heads,
+                     hipStream_t stream, unsigned char* out3, bool x6);
+int attention_h3_ragged(const unsigned char* planes, const float* inv, int n_img, int max_T, const int64_t* tok_off, int64_t rows,
+                        int D, int heads, unsigned char* out2, float* out_inv, hipStream_t stream);
+// FFN-bound telemetry, one figure per (block, image) of a ragged batch
+int ffn_looseness_ragged(const unsigned* rowmax, int nblocks, int64_t M, const int64_t* tok_off, int n_img, float* out,
+                         hipStream_t stream);
 
 // single-pass fused VLAD / k-means (vlad_fused.hip)
 struct FusedArgs {

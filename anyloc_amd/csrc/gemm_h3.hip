@@ -320,7 +320,44 @@ __global__ __launch_bounds__(256) void ffn_looseness_kernel(const unsigned* __re
     out[blockIdx.x] = (any[0] | any[1] | any[2] | any[3]) ? fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) : 0.0f;
 }
 
+// the same figure per (block, image) of a ragged batch: group g = the token rows tok_off[g] .. tok_off[g + 1]
+__global__ __launch_bounds__(256) void ffn_looseness_ragged_kernel(const unsigned* __restrict__ rowmax, int64_t M,
+                                                                   const int64_t* __restrict__ tok_off, int groups,
+                                                                   float* __restrict__ out) {
+  __shared__ float red[4];
+  __shared__ unsigned any[4];
+  const int l = blockIdx.x / groups, g = blockIdx.x % groups;
+  const unsigned* rm = rowmax + (int64_t)l * M;
+  const int64_t r0 = tok_off[g], r1 = min(M, tok_off[g + 1]);
+  float loose = 0.f;
+  unsigned seen = 0u;
+  for (int64_t r = r0 + threadIdx.x; r < r1; r += 256) {
+    const unsigned b = rm[r];
+    seen |= b;
+    loose = fmaxf(loose, b ? 32768.0f / __uint_as_float(b) : 1.099511627776e12f);
+  }
+  loose = wave_max(loose);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) seen |= (unsigned)__shfl_xor((int)seen, o, 64);
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = loose;
+    any[threadIdx.x >> 6] = seen;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    out[blockIdx.x] = (any[0] | any[1] | any[2] | any[3]) ? fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) : 0.0f;
+}
+
 }  // namespace
+
+int ffn_looseness_ragged(const unsigned* rowmax, int nblocks, int64_t M, const int64_t* tok_off, int n_img, float* out,
+                         hipStream_t stream) {
+  ANYLOC_CHECK_ARG(rowmax && out && tok_off && nblocks > 0 && M > 0 && n_img > 0, "ffn_looseness: bad arguments");
+  ProfScope prof("ffn_telemetry", stream, 0.0, 4.0 * nblocks * M);
+  hipLaunchKernelGGL(ffn_looseness_ragged_kernel, dim3((unsigned)(nblocks * n_img)), dim3(256), 0, stream, rowmax, M, tok_off,
+                     n_img, out);
+  return launch_status("ffn_looseness_ragged_kernel");
+}
 
 int ffn_looseness(const unsigned* rowmax, int nblocks, int64_t M, int64_t rows_per_group, float* out, hipStream_t stream) {
   ANYLOC_CHECK_ARG(rowmax && out && nblocks > 0 && M > 0 && rows_per_group > 0, "ffn_looseness: bad arguments");

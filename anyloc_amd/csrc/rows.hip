@@ -132,6 +132,84 @@ __global__ __launch_bounds__(256) void facet_rows_kernel(const float* __restrict
   }
 }
 
+// ---- ragged batches (anyloc_vit_forward_ragged): images of different sizes packed back to back ----
+// meta = the device table of common.hpp (RAGGED_* rows of n_img + 1 int64 each).  Image i owns token rows
+// tok[i] .. tok[i+1], patch rows tok[i] - i .. tok[i+1] - i - 1 and, without the CLS row, output rows tok[i] - i ..
+
+// the image whose rows [off(i), off(i+1)) hold row r, off(i) = tok[i] - sub * i (strictly ascending for sub <= 1)
+__device__ __forceinline__ int ragged_image(const int64_t* __restrict__ tok, int n_img, int64_t r, int sub) {
+  int lo = 0, hi = n_img - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tok[mid] - (int64_t)sub * mid <= r) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// col[patch row, c*P*P + i*P + j] = img_i[c, py*P + i, px*P + j] for the image i that owns the patch row
+__global__ __launch_bounds__(256) void im2col_ragged_kernel(const float* __restrict__ img, float* __restrict__ col,
+                                                            const int64_t* __restrict__ meta, int n_img, int P, int kpad) {
+  const int64_t prow = blockIdx.x;
+  const int64_t stride = n_img + 1;
+  const int i = ragged_image(meta, n_img, prow, 1);
+  const int H = (int)meta[RAGGED_H * stride + i], W = (int)meta[RAGGED_W * stride + i], gw = W / P;
+  const int pi = (int)(prow - (meta[i] - i)), py = pi / gw, px = pi - py * gw;
+  const float* src = img + meta[RAGGED_PIX * stride + i];
+  const int kk = 3 * P * P;
+  float* dst = col + prow * kpad;
+  for (int k = threadIdx.x; k < kpad; k += 256) {
+    float v = 0.f;
+    if (k < kk) {
+      const int c = k / (P * P), rem = k - c * P * P, a = rem / P, j = rem - a * P;
+      v = src[((int64_t)c * H + (py * P + a)) * W + (px * P + j)];
+    }
+    dst[k] = v;
+  }
+}
+
+// token row t of image i: x = cls + pos_i[0] (t = 0) or patch[patch row] + pos_i[t] -- the sums EPI_PATCH and
+// cls_row_kernel form in the uniform forward
+__global__ __launch_bounds__(256) void embed_ragged_kernel(float* __restrict__ x, const float* __restrict__ patch,
+                                                           const float* __restrict__ cls, const float* __restrict__ pos,
+                                                           const int64_t* __restrict__ meta, int n_img, int dim) {
+  const int64_t row = blockIdx.x;
+  const int i = ragged_image(meta, n_img, row, 0);
+  const int64_t t = row - meta[i];
+  const float* pr = pos + (meta[RAGGED_POS * (int64_t)(n_img + 1) + i] + t) * dim;
+  const float* sr = t == 0 ? cls : patch + (row - i - 1) * dim;
+  float* dst = x + row * dim;
+  for (int k = threadIdx.x; k < dim; k += 256) dst[k] = sr[k] + pr[k];
+}
+
+// out[orow, ooff + d] = src[tok[i] + skip + n, coff + d], orow = tok[i] - skip * i + n   (optionally / max(||.||, eps))
+__global__ __launch_bounds__(256) void facet_rows_ragged_kernel(const float* __restrict__ src, int64_t lds_, int coff,
+                                                                float* __restrict__ out, int64_t ldo, int ooff,
+                                                                const int64_t* __restrict__ meta, int n_img, int skip,
+                                                                int dim, int normalize, float eps) {
+  __shared__ float red[4];
+  const int64_t orow = blockIdx.x;
+  const int i = ragged_image(meta, n_img, orow, skip);
+  const int64_t srow = orow + (int64_t)skip * (i + 1);
+  const f32x4* s = reinterpret_cast<const f32x4*>(src + srow * lds_ + coff);
+  f32x4* o = reinterpret_cast<f32x4*>(out + orow * ldo + ooff);
+  const int n4 = dim >> 2;
+  float nrm = 1.0f;
+  if (normalize) {
+    float ss = 0.f;
+    for (int k = threadIdx.x; k < n4; k += 256) {
+      const f32x4 v = s[k];
+      ss += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+    }
+    nrm = fmaxf(sqrtf(block_sum(ss, red)), eps);
+  }
+  for (int k = threadIdx.x; k < n4; k += 256) {
+    f32x4 v = s[k];
+    if (normalize) { v[0] /= nrm; v[1] /= nrm; v[2] /= nrm; v[3] /= nrm; }
+    o[k] = v;
+  }
+}
+
 // uint8 HWC -> float CHW, centre crop, (x/255 - mean)/std : ToTensor + Normalize + CenterCrop
 // (reference dvgl_benchmark/datasets_ws.py:20-23, scripts/dino_v2_vlad.py:173-176)
 __global__ __launch_bounds__(256) void preprocess_u8_kernel(const unsigned char* __restrict__ img,
@@ -201,6 +279,30 @@ int facet_rows(const float* src, int64_t lds_, int coff, float* out, int64_t ldo
   hipLaunchKernelGGL(facet_rows_kernel, dim3((unsigned)(batch * rows_per_img)), dim3(256), 0, stream, src, lds_, coff,
                      out, ldo, ooff, T, skip, rows_per_img, dim, normalize, eps);
   return launch_status("facet_rows_kernel");
+}
+
+int im2col_ragged(const float* img, float* col, const int64_t* meta, int n_img, int64_t patch_rows, int P, int kpad,
+                  hipStream_t stream) {
+  ProfScope prof("im2col", stream, 0.0, 8.0 * patch_rows * kpad);
+  hipLaunchKernelGGL(im2col_ragged_kernel, dim3((unsigned)patch_rows), dim3(256), 0, stream, img, col, meta, n_img, P, kpad);
+  return launch_status("im2col_ragged_kernel");
+}
+
+int embed_ragged(float* x, const float* patch, const float* cls, const float* pos, const int64_t* meta, int n_img, int64_t rows,
+                 int dim, hipStream_t stream) {
+  ProfScope prof("cls_rows", stream, (double)rows * dim, 12.0 * rows * dim);
+  hipLaunchKernelGGL(embed_ragged_kernel, dim3((unsigned)rows), dim3(256), 0, stream, x, patch, cls, pos, meta, n_img, dim);
+  return launch_status("embed_ragged_kernel");
+}
+
+int facet_rows_ragged(const float* src, int64_t lds_, int coff, float* out, int64_t ldo, int ooff, const int64_t* meta,
+                      int n_img, int64_t out_rows, int skip, int dim, int normalize, float eps, hipStream_t stream) {
+  ANYLOC_CHECK_ARG(dim % 4 == 0 && coff % 4 == 0 && ooff % 4 == 0 && lds_ % 4 == 0 && ldo % 4 == 0,
+                   "facet_rows: alignment");
+  ProfScope prof("facet_rows", stream, 3.0 * out_rows * dim, 8.0 * out_rows * dim);
+  hipLaunchKernelGGL(facet_rows_ragged_kernel, dim3((unsigned)out_rows), dim3(256), 0, stream, src, lds_, coff, out, ldo, ooff,
+                     meta, n_img, skip, dim, normalize, eps);
+  return launch_status("facet_rows_ragged_kernel");
 }
 
 }  // namespace anyloc

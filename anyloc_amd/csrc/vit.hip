@@ -18,6 +18,7 @@
 //   y   = LN2(x)
 //   h   = gelu(y W1^T + b)  |  silu(y Wg^T+b)*(y Wv^T+b)    EPI_GELU | EPI_SWIGLU
 //   x  += ls2 * (h W2^T + b)                        EPI_LS_RESID (in place)
+#include <algorithm>
 #include <cstdlib>
 #include <vector>
 
@@ -62,18 +63,18 @@ struct VitWs {
   size_t bytes;
 };
 
-VitWs carve(void* ws, size_t cap, const anyloc_vit_config& c, int64_t batch, int64_t H, int64_t W) {
+// M token rows, P patch rows (uniform: batch * T and batch * np; ragged: the sums over the images)
+VitWs carve(void* ws, size_t cap, const anyloc_vit_config& c, int64_t M, int64_t P) {
   Arena a(ws, cap);
-  const int64_t np = (H / c.patch) * (W / c.patch), T = np + 1, M = batch * T;
   VitWs w;
   w.x = a.take<float>(M * c.dim);
   w.y = a.take<float>(M * c.dim);
   // fp32 [M, 3D], or the im2col patches, or (fp16 mode) the q | k | v tiles of attention_h3: rows padded to 32
-  const int64_t qkv_elems = std::max<int64_t>((M + 31) / 32 * 32 * 3 * c.dim, batch * np * ((c.patch_k_pad + 15) / 16 * 16));
+  const int64_t qkv_elems = std::max<int64_t>((M + 31) / 32 * 32 * 3 * c.dim, P * ((c.patch_k_pad + 15) / 16 * 16));
   w.qkv = a.take<float>(qkv_elems);
   w.h = a.take<float>(M * c.ffn_hidden);
   // (fp16 mode also quantises the gathered patches into a3: [batch * np, patch_k_pad rounded up to 16] as two fp16 planes)
-  w.a3 = a.take<unsigned char>(std::max(x3_bytes(M, c.dim), h2_bytes(batch * np, (c.patch_k_pad + 15) / 16 * 16)));
+  w.a3 = a.take<unsigned char>(std::max(x3_bytes(M, c.dim), h2_bytes(P, (c.patch_k_pad + 15) / 16 * 16)));
   w.h3 = a.take<unsigned char>(x3_bytes(M, c.ffn_hidden));
   w.ainv = a.take<float>(M);
   w.hinv = a.take<float>(M);
@@ -344,17 +345,30 @@ void anyloc_vit_destroy(anyloc_vit_t* h) {
 
 size_t anyloc_vit_workspace_bytes(const anyloc_vit_t* h, int64_t batch, int64_t img_h, int64_t img_w) {
   if (!h || batch <= 0 || img_h < h->cfg.patch || img_w < h->cfg.patch) return 0;
-  return carve(nullptr, 0, h->cfg, batch, img_h, img_w).bytes + 256;
+  const int64_t np = (img_h / h->cfg.patch) * (img_w / h->cfg.patch);
+  return carve(nullptr, 0, h->cfg, batch * (np + 1), batch * np).bytes + 256;
 }
 
-// the launch sequence of one forward on `stream` (shape and taps already validated by anyloc_vit_forward)
+// a ragged batch (anyloc_vit_forward_ragged): images of different sizes packed back to back
+struct RaggedBatch {
+  const int64_t* meta;      // device table (common.hpp, RAGGED_*)
+  int64_t rows;             // token rows, sum of T_i
+  int max_T;                // the longest image
+};
+
+// the launch sequence of one forward on `stream` (shape and taps already validated by anyloc_vit_forward /
+// anyloc_vit_forward_ragged).  rg == nullptr: `batch` images of img_h x img_w; otherwise `batch` images of the sizes in rg
+// (img_h / img_w unused) -- the block GEMMs, LayerNorms and quantisers work on rows and do not see the difference
 static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch, int64_t img_h, int64_t img_w,
                                 const float* pos, int32_t n_taps, const int32_t* tap_layers, const int32_t* tap_facets,
-                                unsigned flags, float* out, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+                                unsigned flags, float* out, void* workspace, size_t workspace_bytes, hipStream_t stream,
+                                const RaggedBatch* rg = nullptr) {
   const anyloc_vit_config& c = h->cfg;
-  const int D = c.dim, gh = (int)(img_h / c.patch), gw = (int)(img_w / c.patch), np = gh * gw, T = np + 1;
-  const int64_t M = batch * T;
-  VitWs w = carve(workspace, workspace_bytes, c, batch, img_h, img_w);
+  const int D = c.dim, gh = rg ? 0 : (int)(img_h / c.patch), gw = rg ? 0 : (int)(img_w / c.patch), np = gh * gw;
+  const int T = rg ? rg->max_T : np + 1;
+  const int64_t M = rg ? rg->rows : batch * T, P = rg ? rg->rows - batch : batch * np;
+  const int64_t* meta = rg ? rg->meta : nullptr;
+  VitWs w = carve(workspace, workspace_bytes, c, M, P);
   if (!workspace || w.bytes > workspace_bytes) {
     set_error("vit_forward: workspace %zu < %zu", workspace_bytes, w.bytes);
     return ANYLOC_ERR_WORKSPACE;
@@ -372,8 +386,14 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
   const bool h3f = h3m && option(OPT_H3_FUSE) != 0;
   const bool use_cls = flags & ANYLOC_VIT_USE_CLS;
   const int rows_per_img = use_cls ? T : np, skip = use_cls ? 0 : 1;
+  const int64_t out_rows = rg ? (use_cls ? M : P) : batch * rows_per_img;
   const int64_t ldo = (int64_t)n_taps * D;
   const int norm_taps = (flags & ANYLOC_VIT_NORM_TAPS) ? 1 : 0;
+  // the tapped rows of src (width lds_, columns coff ..) -> out columns ooff ..
+  auto facet = [&](const float* src, int64_t lds_, int coff, int ooff) {
+    if (rg) return facet_rows_ragged(src, lds_, coff, out, ldo, ooff, meta, (int)batch, out_rows, skip, D, norm_taps, 1e-12f, stream);
+    return facet_rows(src, lds_, coff, out, ldo, ooff, batch, T, skip, rows_per_img, D, norm_taps, 1e-12f, stream);
+  };
   const int last_layer = tap_layers[n_taps - 1];
   // split-K arrival counters; with telemetry on also the rows' maxima of every block that will run (adjacent: one memset)
   const bool telem = h3m && h->ffn_looseness != nullptr;
@@ -391,33 +411,39 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
   float* col = w.qkv;
   const bool patch_h3 = h3m && h->patch_w2 && option(OPT_H3_PATCH) != 0;
   const int kp = patch_h3 ? (c.patch_k_pad + 15) / 16 * 16 : c.patch_k_pad;    // fp16 mode: whole 16-element k-blocks
-  ANYLOC_TRY(im2col(img, col, batch, (int)img_h, (int)img_w, c.patch, kp, stream));
+  if (rg) ANYLOC_TRY(im2col_ragged(img, col, meta, (int)batch, P, c.patch, kp, stream));
+  else ANYLOC_TRY(im2col(img, col, batch, (int)img_h, (int)img_w, c.patch, kp, stream));
+  // ragged: the patch GEMM with its bias epilogue into w.y [P, D]; embed_ragged then adds each image's positional rows and
+  // writes the CLS rows (the same two sums as EPI_PATCH + cls_rows)
+  float* patch_out = rg ? w.y : w.x;
+  const int patch_epi = rg ? EPI_STORE : EPI_PATCH;
   if (patch_h3) {
     // fp16 mode: the gathered patches are quantised like every other operand (row maximum -> power-of-two scale)
-    ANYLOC_TRY(split_h2(col, kp, batch * np, kp, w.a3, w.ainv, stream));
+    ANYLOC_TRY(split_h2(col, kp, P, kp, w.a3, w.ainv, stream));
     H3Problem g{};
-    g.A2 = w.a3; g.RA = batch * np; g.a_inv = w.ainv;
+    g.A2 = w.a3; g.RA = P; g.a_inv = w.ainv;
     g.W2 = h->patch_w2; g.RW = D; g.w_inv = h->patch_inv;
-    g.C = w.x; g.ldc = D;
-    g.M = batch * np; g.N = D; g.K16 = kp / 16;
+    g.C = patch_out; g.ldc = D;
+    g.M = P; g.N = D; g.K16 = kp / 16;
     g.bias = h->patch_b;
-    g.pos = pos;
+    g.pos = rg ? nullptr : pos;
     g.patches = np;
     g.tag = "vit_patch_embed_gemm";
-    ANYLOC_TRY(gemm_h3(g, EPI_PATCH, stream));
+    ANYLOC_TRY(gemm_h3(g, patch_epi, stream));
   } else {
     GemmProblem g{};
     g.A = col; g.lda = c.patch_k_pad;
     g.W = h->patch_w; g.ldw = c.patch_k_pad;
-    g.C = w.x; g.ldc = D;
-    g.M = batch * np; g.N = D; g.K = c.patch_k_pad;
+    g.C = patch_out; g.ldc = D;
+    g.M = P; g.N = D; g.K = c.patch_k_pad;
     g.bias = h->patch_b;
-    g.pos = pos;
+    g.pos = rg ? nullptr : pos;
     g.patches = np;
     g.tag = "vit_patch_embed_gemm";
-    ANYLOC_TRY(gemm_nt(g, EPI_PATCH, stream));
+    ANYLOC_TRY(gemm_nt(g, patch_epi, stream));
   }
-  ANYLOC_TRY(cls_rows(w.x, h->cls, pos, batch, T, D, stream));
+  if (rg) ANYLOC_TRY(embed_ragged(w.x, w.y, h->cls, pos, meta, (int)batch, M, D, stream));
+  else ANYLOC_TRY(cls_rows(w.x, h->cls, pos, batch, T, D, stream));
 
   for (int l = 0; l <= last_layer; ++l) {
     const anyloc_vit_block_weights& b = h->blocks[l];
@@ -451,8 +477,7 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
         else
           ANYLOC_TRY(linear(w.y, D, b.qkv_w + (int64_t)f * D * D, D, b.qkv_b + (int64_t)f * D, w.qkv, D, M, D,
                             EPI_STORE, nullptr, "vit_facet_gemm", stream));
-        ANYLOC_TRY(facet_rows(w.qkv, D, 0, out, ldo, t * D, batch, T, skip, rows_per_img, D, norm_taps, 1e-12f,
-                              stream));
+        ANYLOC_TRY(facet(w.qkv, D, 0, t * D));
       }
       break;
     }
@@ -466,7 +491,11 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
       ANYLOC_TRY(linear_h3(nullptr, D, w.a3, w.ainv, h->h2[l].qkv_w2, h->h2[l].qkv_inv, 3 * D, 0, b.qkv_b, nullptr, 3 * D, M,
                            3 * D, EPI_QKV_PLANES, nullptr, "vit_qkv_gemm", stream, nullptr, nullptr,
                            reinterpret_cast<unsigned char*>(w.qkv), w.qinv, c.heads, &w, H3_KIND_QKV, nullptr, &ln1));
-      ANYLOC_TRY(attention_h3(reinterpret_cast<const unsigned char*>(w.qkv), w.qinv, batch, T, D, c.heads, w.a3, w.ainv, stream));
+      if (rg)
+        ANYLOC_TRY(attention_h3_ragged(reinterpret_cast<const unsigned char*>(w.qkv), w.qinv, (int)batch, T, meta, M, D, c.heads,
+                                       w.a3, w.ainv, stream));
+      else
+        ANYLOC_TRY(attention_h3(reinterpret_cast<const unsigned char*>(w.qkv), w.qinv, batch, T, D, c.heads, w.a3, w.ainv, stream));
       ANYLOC_TRY(linear_h3(nullptr, D, w.a3, w.ainv, h->h2[l].proj_w2, h->h2[l].proj_inv, D, 0, b.proj_b, w.x, D, M, D,
                            EPI_LS_RESID, b.ls1, "vit_proj_gemm", stream, nullptr, nullptr, nullptr, nullptr, 0, &w, H3_KIND_PROJ));
     } else {
@@ -480,9 +509,9 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
         ANYLOC_TRY(linear(w.y, D, b.qkv_w, D, b.qkv_b, w.qkv, 3 * D, M, 3 * D, EPI_STORE, nullptr, "vit_qkv_gemm", stream));
       for (int t = 0; t < n_taps; ++t)
         if (tap_layers[t] == l && tap_facets[t] != ANYLOC_FACET_TOKEN)
-          ANYLOC_TRY(facet_rows(w.qkv, 3 * D, tap_facets[t] * D, out, ldo, t * D, batch, T, skip, rows_per_img, D,
-                                norm_taps, 1e-12f, stream));
-      ANYLOC_TRY(attention(w.qkv, w.y, batch, T, D, c.heads, stream, fuse ? w.a3 : nullptr, x6 || h3m));
+          ANYLOC_TRY(facet(w.qkv, 3 * D, tap_facets[t] * D, t * D));
+      if (rg) ANYLOC_TRY(attention_ragged(w.qkv, w.y, (int)batch, T, meta, M, D, c.heads, stream, fuse ? w.a3 : nullptr, x6 || h3m));
+      else ANYLOC_TRY(attention(w.qkv, w.y, batch, T, D, c.heads, stream, fuse ? w.a3 : nullptr, x6 || h3m));
       if (h3m)     // the attention output is fp32: its rows span all heads, the row maximum is only known now
         ANYLOC_TRY(linear_h3(w.y, D, w.a3, w.ainv, h->h2[l].proj_w2, h->h2[l].proj_inv, D, 0, b.proj_b, w.x, D, M, D,
                              EPI_LS_RESID, b.ls1, "vit_proj_gemm", stream));
@@ -545,12 +574,14 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
     }
     for (int t = 0; t < n_taps; ++t)
       if (tap_layers[t] == l && tap_facets[t] == ANYLOC_FACET_TOKEN)
-        ANYLOC_TRY(facet_rows(w.x, D, 0, out, ldo, t * D, batch, T, skip, rows_per_img, D, norm_taps, 1e-12f, stream));
+        ANYLOC_TRY(facet(w.x, D, 0, t * D));
   }
   if (flags & ANYLOC_VIT_NORM_CONCAT)
-    ANYLOC_TRY(l2norm_rows(out, ldo, out, ldo, batch * rows_per_img, ldo, 1e-12f, stream));
+    ANYLOC_TRY(l2norm_rows(out, ldo, out, ldo, out_rows, ldo, 1e-12f, stream));
   // FFN-bound telemetry: one figure per executed block (and image) from the row maxima the fc1 / w12 epilogues left
-  if (telem) ANYLOC_TRY(ffn_looseness(w.hmax, last_layer + 1, M, h->telemetry_per_image ? T : M, h->ffn_looseness, stream));
+  if (telem && rg && h->telemetry_per_image)
+    ANYLOC_TRY(ffn_looseness_ragged(w.hmax, last_layer + 1, M, meta, (int)batch, h->ffn_looseness, stream));
+  else if (telem) ANYLOC_TRY(ffn_looseness(w.hmax, last_layer + 1, M, h->telemetry_per_image ? T : M, h->ffn_looseness, stream));
   return ANYLOC_OK;
 }
 
@@ -573,6 +604,107 @@ int anyloc_vit_forward(anyloc_vit_t* h, const float* img, int64_t batch, int64_t
   }
   return vit_forward_launches(h, img, batch, img_h, img_w, pos, n_taps, tap_layers, tap_facets, flags, out, workspace,
                               workspace_bytes, stream);
+}
+
+// ---- ragged batches (ABI 10) ----
+
+// host-side check of the image sizes of a ragged call -> total token rows and the longest image
+static int ragged_shape(const anyloc_vit_t* h, int32_t n_img, const int32_t* img_hw, int64_t* rows, int* max_T, const char* who) {
+  ANYLOC_CHECK_ARG(h, "%s: null handle", who);
+  ANYLOC_CHECK_ARG(img_hw, "%s: null size array", who);
+  ANYLOC_CHECK_ARG(n_img > 0 && n_img < 65536, "%s: n_img %d outside [1, 65535]", who, n_img);
+  const int P = h->cfg.patch;
+  int64_t r = 0;
+  int mt = 0;
+  for (int i = 0; i < n_img; ++i) {
+    const int64_t ih = img_hw[2 * i], iw = img_hw[2 * i + 1];
+    ANYLOC_CHECK_ARG(ih >= P && iw >= P && ih % P == 0 && iw % P == 0 && ih <= 65535 && iw <= 65535,
+                     "%s: image %d is %lldx%lld, not a positive multiple of the patch size %d", who, i, (long long)ih,
+                     (long long)iw, P);
+    const int64_t T = (ih / P) * (iw / P) + 1;
+    ANYLOC_CHECK_ARG(T < (1 << 30), "%s: image %d has too many tokens", who, i);
+    r += T;
+    mt = std::max<int>(mt, (int)T);
+  }
+  ANYLOC_CHECK_ARG(r < (1ll << 31), "%s: %lld token rows in one call", who, (long long)r);
+  *rows = r;
+  *max_T = mt;
+  return ANYLOC_OK;
+}
+
+size_t anyloc_vit_workspace_bytes_ragged(const anyloc_vit_t* h, int32_t n_img, const int32_t* img_hw) {
+  int64_t rows = 0;
+  int max_T = 0;
+  if (ragged_shape(h, n_img, img_hw, &rows, &max_T, "vit_workspace_bytes_ragged") != ANYLOC_OK) return 0;
+  return carve(nullptr, 0, h->cfg, rows, rows - n_img).bytes + 256;
+}
+
+int anyloc_vit_forward_ragged(anyloc_vit_t* h, const float* img, int32_t n_img, const int32_t* img_hw, const int64_t* dev_meta,
+                              const float* pos, int32_t n_taps, const int32_t* tap_layers, const int32_t* tap_facets,
+                              unsigned flags, float* out, void* workspace, size_t workspace_bytes, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  int64_t rows = 0;
+  int max_T = 0;
+  ANYLOC_TRY(ragged_shape(h, n_img, img_hw, &rows, &max_T, "vit_forward_ragged"));
+  ANYLOC_CHECK_ARG(img && dev_meta && pos && out && tap_layers && tap_facets, "vit_forward_ragged: null pointer");
+  const anyloc_vit_config& c = h->cfg;
+  ANYLOC_CHECK_ARG(n_taps >= 1 && n_taps <= 64, "vit_forward_ragged: n_taps %d", n_taps);
+  for (int t = 0; t < n_taps; ++t) {
+    ANYLOC_CHECK_ARG(tap_layers[t] >= 0 && tap_layers[t] < c.depth, "vit_forward_ragged: tap layer %d outside [0,%d)",
+                     tap_layers[t], c.depth);
+    ANYLOC_CHECK_ARG(tap_facets[t] >= 0 && tap_facets[t] <= 3, "vit_forward_ragged: facet %d", tap_facets[t]);
+    ANYLOC_CHECK_ARG(t == 0 || tap_layers[t] >= tap_layers[t - 1], "vit_forward_ragged: tap layers must ascend");
+  }
+  const RaggedBatch rg{dev_meta, rows, max_T};
+  return vit_forward_launches(h, img, n_img, 0, 0, pos, n_taps, tap_layers, tap_facets, flags, out, workspace, workspace_bytes,
+                              stream, &rg);
+}
+
+// the attention kernels on their own, over a ragged batch (kernel tests): tokens = host [n_img] lengths, tok_off = device
+// [n_img + 1] offsets of the same lengths
+static int attention_ragged_shape(int32_t n_img, const int32_t* tokens, int64_t* rows, int* max_T) {
+  ANYLOC_CHECK_ARG(tokens && n_img > 0 && n_img < 65536, "attention_ragged: n_img %d / null token counts", n_img);
+  int64_t r = 0;
+  int mt = 0;
+  for (int i = 0; i < n_img; ++i) {
+    ANYLOC_CHECK_ARG(tokens[i] > 0, "attention_ragged: image %d has %d tokens", i, tokens[i]);
+    r += tokens[i];
+    mt = std::max(mt, (int)tokens[i]);
+  }
+  *rows = r;
+  *max_T = mt;
+  return ANYLOC_OK;
+}
+
+int anyloc_attention_ragged(const float* qkv, float* out, int32_t n_img, const int32_t* tokens, const int64_t* tok_off,
+                            int64_t dim, int64_t heads, void* stream) {
+  ANYLOC_CHECK_ARG(qkv && out && tok_off, "attention_ragged: null pointer");
+  int64_t rows = 0;
+  int max_T = 0;
+  ANYLOC_TRY(attention_ragged_shape(n_img, tokens, &rows, &max_T));
+  return attention_ragged(qkv, out, n_img, max_T, tok_off, rows, (int)dim, (int)heads, static_cast<hipStream_t>(stream), nullptr,
+                          false);
+}
+
+int anyloc_attention_h3_ragged(const float* qkv, void* out_img, float* out_inv, int32_t n_img, const int32_t* tokens,
+                               const int64_t* tok_off, int64_t dim, int64_t heads, void* workspace, size_t workspace_bytes,
+                               void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  ANYLOC_CHECK_ARG(qkv && out_img && out_inv && tok_off && workspace, "attention_h3_ragged: null pointer");
+  ANYLOC_CHECK_ARG(heads > 0 && dim == heads * 64, "attention_h3_ragged: bad shape");
+  int64_t rows = 0;
+  int max_T = 0;
+  ANYLOC_TRY(attention_ragged_shape(n_img, tokens, &rows, &max_T));
+  if (workspace_bytes < anyloc_attention_h3_workspace_bytes(1, rows, heads)) {
+    set_error("attention_h3_ragged: workspace %zu < %zu", workspace_bytes, anyloc_attention_h3_workspace_bytes(1, rows, heads));
+    return ANYLOC_ERR_WORKSPACE;
+  }
+  Arena a(workspace, workspace_bytes);
+  unsigned char* planes = a.take<unsigned char>(qkv_planes_bytes(rows, (int)heads));
+  float* inv = a.take<float>(qkv_inv_count(rows, (int)heads));
+  ANYLOC_TRY(qkv_planes_from_f32(qkv, rows, (int)dim, (int)heads, planes, inv, stream));
+  return attention_h3_ragged(planes, inv, n_img, max_T, tok_off, rows, (int)dim, (int)heads, static_cast<unsigned char*>(out_img),
+                             out_inv, stream);
 }
 
 }  // extern "C"

@@ -73,6 +73,35 @@ def interpolate_pos_embed(pos_embed, h_img, w_img):
     return torch.cat([pos_embed[0, :1], grid], dim=0).contiguous()
 
 
+def ragged_chunks(sizes, max_rows, patch=PATCH):
+    """Greedy packing of images of sizes [(H, W), ...] in input order under a budget of ``max_rows`` token rows per call:
+    -> [(start, stop), ...] index ranges.  An image whose own rows exceed the budget runs alone."""
+    chunks, start, rows = [], 0, 0
+    for i, (h, w) in enumerate(sizes):
+        t = (int(h) // patch) * (int(w) // patch) + 1
+        if i > start and rows + t > max_rows:
+            chunks.append((start, i))
+            start, rows = i, 0
+        rows += t
+    if start < len(sizes):
+        chunks.append((start, len(sizes)))
+    return chunks
+
+
+def ragged_offsets(sizes, use_cls, patch=PATCH):
+    """Row layout of one ragged call (include/anyloc_hip.h, anyloc_vit_forward_ragged): -> (tok_off, out_off, pix_off),
+    int64 NumPy arrays of len(sizes) + 1 -- token rows (T_i = N_i + 1), output rows (N_i, or T_i with the CLS row) and
+    float offsets of the packed CHW images."""
+    hw = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    n = (hw[:, 0] // patch) * (hw[:, 1] // patch)
+    tok = np.zeros(len(hw) + 1, dtype=np.int64)
+    tok[1:] = np.cumsum(n + 1)
+    out = tok.copy() if use_cls else tok - np.arange(len(hw) + 1, dtype=np.int64)
+    pix = np.zeros(len(hw) + 1, dtype=np.int64)
+    pix[1:] = np.cumsum(3 * hw[:, 0] * hw[:, 1])
+    return tok, out, pix
+
+
 class HipDinoV2:
     """Device-resident DINOv2 weights + the C handle of the HIP forward."""
 
@@ -235,6 +264,149 @@ class HipDinoV2:
             self._begin_call()
             return self._forward_taps(img, taps, use_cls, norm_taps, norm_concat)
 
+    @torch.no_grad()
+    def forward_taps_ragged(self, imgs, taps, use_cls=False, norm_taps=True, norm_concat=False):
+        """Images of DIFFERENT sizes in few launches: ``imgs`` = a list of [3, H_i, W_i] tensors, or a pair (packed
+        float buffer holding the CHW images back to back, [(H_i, W_i), ...]).  -> (packed [sum rows_i, len(taps)*D],
+        offsets int64 [n+1] on the model's device), rows_i = N_i (+1 with ``use_cls``): image i's rows are
+        packed[offsets[i]:offsets[i+1]] -- the pair ``ops.vlad`` takes as it is.  The images are packed greedily in input
+        order under ``max_rows`` token rows per call (an image above the budget runs alone); every image gets the rows a
+        ``forward_taps`` call on that image alone computes, within the arithmetic's rounding."""
+        with _on_device(self.device):
+            self._begin_call()
+            if isinstance(imgs, tuple) and len(imgs) == 2 and isinstance(imgs[0], torch.Tensor) and imgs[0].ndim == 1:
+                flat, sizes = imgs
+                sizes = [(int(h), int(w)) for h, w in sizes]
+                flat = ops._f32c(flat, self.device).reshape(-1)
+            else:
+                sizes, parts = [], []
+                for im in imgs:
+                    if im.ndim != 3 or im.shape[0] != 3:
+                        raise ValueError(f"expected [3, H, W] images, got {tuple(im.shape)}")
+                    sizes.append((int(im.shape[1]), int(im.shape[2])))
+                    parts.append(ops._f32c(im, self.device).reshape(-1))
+                flat = torch.cat(parts) if parts else torch.empty(0, device=self.device)
+            for h, w in sizes:
+                if h % PATCH or w % PATCH or h < PATCH or w < PATCH:
+                    raise ValueError(f"image {h}x{w} is not a positive multiple of the patch size {PATCH}")
+            tok, out_off, pix = ragged_offsets(sizes, use_cls)
+            if flat.numel() != pix[-1]:
+                raise ValueError(f"packed buffer holds {flat.numel()} floats, the sizes need {int(pix[-1])}")
+            taps = list(taps)
+            for layer, facet in taps:
+                if not 0 <= layer < self.depth:
+                    raise IndexError(f"layer {layer} outside the {self.depth} loaded blocks")
+            order = sorted(range(len(taps)), key=lambda i: taps[i][0])
+            offsets = torch.from_numpy(out_off).to(self.device)
+            chunks = ragged_chunks(sizes, self.max_rows)
+            inv = [order.index(i) for i in range(len(taps))] if order != list(range(len(taps))) else None
+            # one chunk (the common case): the forward writes the caller's result directly; several: into slices of it
+            out = None if len(chunks) == 1 and inv is None else \
+                torch.empty(int(out_off[-1]), len(taps) * self.dim, dtype=torch.float32, device=self.device)
+            for a, b in chunks:
+                r0, r1 = int(out_off[a]), int(out_off[b])
+                res = self._forward_ragged(flat[int(pix[a]):int(pix[b])], sizes[a:b], [taps[i] for i in order], use_cls,
+                                           norm_taps, norm_concat)
+                if out is None:
+                    return res, offsets
+                if inv is not None:
+                    # the caller's tap order ("l n d -> n (l d)"); every normalisation is invariant to the block order
+                    res = res.reshape(res.shape[0], len(taps), self.dim)[:, inv].reshape(res.shape[0], -1)
+                out[r0:r1] = res
+            if out is None:                                  # (no images)
+                out = torch.empty(0, len(taps) * self.dim, dtype=torch.float32, device=self.device)
+            return out, offsets
+
+    def _forward_ragged(self, flat, sizes, taps, use_cls, norm_taps, norm_concat):
+        """One ragged call (taps ascending) over images that fit one launch sequence -> [sum rows_i, len(taps)*D]."""
+        n_img, n_taps = len(sizes), len(taps)
+        tok, out_off, pix = ragged_offsets(sizes, use_cls)
+        out = torch.empty(int(out_off[-1]), n_taps * self.dim, dtype=torch.float32, device=self.device)
+        # positional tables: one per distinct size (the pos_table cache), packed, addressed per image by its first row
+        first, tables, pos_row, at = {}, [], [], 0
+        for hw in sizes:
+            if hw not in first:
+                t = self.pos_table(*hw)
+                first[hw] = at
+                tables.append(t)
+                at += t.shape[0]
+            pos_row.append(first[hw])
+        pos = tables[0] if len(tables) == 1 else torch.cat(tables)
+        meta = np.zeros((5, n_img + 1), dtype=np.int64)
+        meta[0], meta[1] = tok, pix
+        meta[2, :n_img] = pos_row
+        meta[3, :n_img] = [h for h, _ in sizes]
+        meta[4, :n_img] = [w for _, w in sizes]
+        dev_meta = torch.from_numpy(meta).pin_memory().to(self.device, non_blocking=True)
+        hw_host = (C.c_int32 * (2 * n_img))(*[v for hw in sizes for v in hw])
+        lib = _lib.load()
+        ws_bytes = lib.anyloc_vit_workspace_bytes_ragged(self._handle, n_img, hw_host)
+        if ws_bytes == 0:
+            raise _lib.AnylocHipError(f"anyloc_vit_workspace_bytes_ragged: {lib.anyloc_last_error().decode()}")
+        ws = _lib.workspace(ws_bytes, self.device, "vit")
+        layers = (C.c_int32 * n_taps)(*[t[0] for t in taps])
+        facets = (C.c_int32 * n_taps)(*[ops.FACETS[t[1]] for t in taps])
+        flags = (ops.VIT_USE_CLS if use_cls else 0) | (ops.VIT_NORM_TAPS if norm_taps else 0) | \
+            (ops.VIT_NORM_CONCAT if norm_concat else 0) | (ops.VIT_SPLIT_BF16 if self.gemm == "x6" else 0) | \
+            (ops.VIT_SPLIT_FP16 if self.gemm == "h3" else 0)
+
+        def forward(y):
+            _lib.check(lib.anyloc_vit_forward_ragged(self._handle, _lib.ptr(flat), n_img, hw_host, _lib.ptr(dev_meta),
+                                                     _lib.ptr(pos), n_taps, layers, facets, flags, _lib.ptr(y), _lib.ptr(ws),
+                                                     ws.numel(), _lib.stream_ptr()), "anyloc_vit_forward_ragged")
+        if self.gemm != "h3" or not self.ffn_check:
+            forward(out)
+            return out
+        # the FFN-bound check of _forward_taps, per image of the ragged batch: images that trip blocks are grouped by the
+        # set they trip, the WHOLE call runs again with exactly that set exact, and only the group's rows are taken from it
+        loose = self._telemetry_call(lambda: forward(out), n_img, taps[-1][0] + 1)
+        bad = loose > FFN_LOOSENESS_MAX
+        if bad.any():
+            groups = {}
+            for b in range(n_img):
+                key = tuple(int(l) for l in np.nonzero(bad[:, b])[0])
+                if key:
+                    groups.setdefault(key, []).append(b)
+            res = torch.empty_like(out)
+            for key, members in groups.items():
+                self._with_exact(key, lambda: forward(res))
+                rows = torch.from_numpy(np.concatenate([np.arange(out_off[b], out_off[b + 1]) for b in members])).to(self.device)
+                out.index_copy_(0, rows, res.index_select(0, rows))
+                self.ffn_exact_blocks.update(key)
+                self.ffn_reruns += len(members)
+        return out
+
+    def _telemetry_call(self, run, n_img, n_blocks):
+        """Run ``run()`` with the per-image FFN-bound telemetry on -> looseness [n_blocks, n_img] (NumPy), merged into
+        ``ffn_looseness``."""
+        lib = _lib.load()
+        if self._telemetry is None or self._telemetry.numel() < self.depth * n_img:
+            self._telemetry = torch.empty(self.depth * n_img, dtype=torch.float32, device=self.device)
+            self._telemetry_host = torch.empty(self.depth * n_img, dtype=torch.float32, pin_memory=True)
+        _lib.check(lib.anyloc_vit_set_telemetry(self._handle, _lib.ptr(self._telemetry), 1), "anyloc_vit_set_telemetry")
+        try:
+            run()
+        finally:
+            _lib.check(lib.anyloc_vit_set_telemetry(self._handle, None, 0), "anyloc_vit_set_telemetry")
+        self._telemetry_host[:n_blocks * n_img].copy_(self._telemetry[:n_blocks * n_img], non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()                            # (the call's one host sync)
+        loose = self._telemetry_host.numpy()[:n_blocks * n_img].reshape(n_blocks, n_img).copy()
+        worst = loose.max(axis=1)
+        self.ffn_looseness = worst if self.ffn_looseness is None or len(self.ffn_looseness) != len(worst) \
+            else np.maximum(self.ffn_looseness, worst)
+        return loose
+
+    def _with_exact(self, blocks, run):
+        """``run()`` with the FFN blocks ``blocks`` on the exact row-maximum quantiser (cleared again afterwards)."""
+        lib = _lib.load()
+        try:
+            for l in blocks:
+                _lib.check(lib.anyloc_vit_block_ffn_exact(self._handle, l, 1), "anyloc_vit_block_ffn_exact")
+            run()
+        finally:
+            for l in blocks:
+                _lib.check(lib.anyloc_vit_block_ffn_exact(self._handle, l, 0), "anyloc_vit_block_ffn_exact")
+
     def _begin_call(self):
         """The per-call record of the FFN-bound check starts empty (a batch forwarded in chunks is ONE call: the chunks'
         figures are merged)."""
@@ -287,50 +459,26 @@ class HipDinoV2:
             forward(img, out)
             return out
         # the call with the FFN-bound telemetry on: one figure per (executed block, image)
-        if self._telemetry is None or self._telemetry.numel() < self.depth * B:
-            self._telemetry = torch.empty(self.depth * B, dtype=torch.float32, device=self.device)
-            # the figures come back through PINNED memory and are read with NumPy: `.cpu()` + torch CPU reductions of these
-            # hundred bytes cost 15 + 9 ms per call on the 256-thread host (a one-image forward is 5.5 ms;
-            # profiles/r06_ffn_telemetry_b1.log), an asynchronous copy + a stream wait + a NumPy max cost ~0.03 ms
-            self._telemetry_host = torch.empty(self.depth * B, dtype=torch.float32, pin_memory=True)
-        _lib.check(lib.anyloc_vit_set_telemetry(self._handle, _lib.ptr(self._telemetry), 1), "anyloc_vit_set_telemetry")
-        try:
-            forward(img, out)
-            n_blocks = taps[-1][0] + 1
-            self._telemetry_host[:n_blocks * B].copy_(self._telemetry[:n_blocks * B], non_blocking=True)
-            torch.cuda.current_stream(self.device).synchronize()                        # (the call's one host sync)
-            loose = self._telemetry_host.numpy()[:n_blocks * B].reshape(n_blocks, B)
-            worst = loose.max(axis=1)
-            self.ffn_looseness = worst if self.ffn_looseness is None or len(self.ffn_looseness) != len(worst) \
-                else np.maximum(self.ffn_looseness, worst)
-            bad = loose > FFN_LOOSENESS_MAX
-            if bad.any():
-                # images grouped by the set of blocks THEY trip: for each such set the call runs again with exactly those
-                # blocks exact -- the WHOLE batch, same row count and batch positions, because the kernels' summation orders
-                # depend on both (small-M plans, the global 32-row key groups of attention) -- and only the group's images
-                # take their rows from it.  So an image's bits depend on the image, its position and the call's shape, never
-                # on what its batch mates contain; the switches are cleared before the call returns.
-                groups = {}
-                for b in range(B):
-                    key = tuple(int(l) for l in np.nonzero(bad[:, b])[0])
-                    if key:
-                        groups.setdefault(key, []).append(b)
-                _lib.check(lib.anyloc_vit_set_telemetry(self._handle, None, 0), "anyloc_vit_set_telemetry")
-                res = torch.empty_like(out)
-                for key, members in groups.items():
-                    try:
-                        for l in key:
-                            _lib.check(lib.anyloc_vit_block_ffn_exact(self._handle, l, 1), "anyloc_vit_block_ffn_exact")
-                        forward(img, res)
-                    finally:
-                        for l in key:
-                            _lib.check(lib.anyloc_vit_block_ffn_exact(self._handle, l, 0), "anyloc_vit_block_ffn_exact")
-                    idx = torch.tensor(members, device=self.device)
-                    out.index_copy_(0, idx, res.index_select(0, idx))
-                    self.ffn_exact_blocks.update(key)
-                    self.ffn_reruns += len(members)
-        finally:
-            _lib.check(lib.anyloc_vit_set_telemetry(self._handle, None, 0), "anyloc_vit_set_telemetry")
+        loose = self._telemetry_call(lambda: forward(img, out), B, taps[-1][0] + 1)
+        bad = loose > FFN_LOOSENESS_MAX
+        if bad.any():
+            # images grouped by the set of blocks THEY trip: for each such set the call runs again with exactly those
+            # blocks exact -- the WHOLE batch, same row count and batch positions, because the kernels' summation orders
+            # depend on both (small-M plans, the global 32-row key groups of attention) -- and only the group's images
+            # take their rows from it.  So an image's bits depend on the image, its position and the call's shape, never
+            # on what its batch mates contain; the switches are cleared before the call returns.
+            groups = {}
+            for b in range(B):
+                key = tuple(int(l) for l in np.nonzero(bad[:, b])[0])
+                if key:
+                    groups.setdefault(key, []).append(b)
+            res = torch.empty_like(out)
+            for key, members in groups.items():
+                self._with_exact(key, lambda: forward(img, res))
+                idx = torch.tensor(members, device=self.device)
+                out.index_copy_(0, idx, res.index_select(0, idx))
+                self.ffn_exact_blocks.update(key)
+                self.ffn_reruns += len(members)
         return out
 
 
@@ -401,6 +549,18 @@ class DinoV2ExtractFeatures:
         res = self.dino_model.forward_taps(img, [(l, facet) for l in layers], use_cls=self.use_cls,
                                            norm_taps=self.norm_descs, norm_concat=norm_concat)
         return res if img.is_cuda else ops.to_home(res, img.device)
+
+    def extract_ragged(self, imgs, packed=False):
+        """Additive API: images of different sizes (a list of [3, H_i, W_i] tensors, ImageNet-normalised, sides multiples of
+        14) in few batched launches -> a list of [1, N_i(+1), D] tensors on the model's device, each what ``self(img[None])``
+        returns for that image; ``packed=True``: the (packed [sum rows_i, D], offsets [n+1]) pair instead, which
+        ``ops.vlad`` / ``VLAD.generate_multi`` take without a copy."""
+        out, offsets = self.dino_model.forward_taps_ragged(imgs, [(self.layer, self.facet)], use_cls=self.use_cls,
+                                                           norm_taps=self.norm_descs)
+        if packed:
+            return out, offsets
+        off = offsets.cpu().tolist()
+        return [out[off[i]:off[i + 1]][None] for i in range(len(off) - 1)]
 
     def __del__(self):
         fh = getattr(self, "fh_handle", None)

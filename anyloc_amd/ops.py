@@ -190,9 +190,23 @@ def attention_h3(qkv, heads):
     return img, inv
 
 
+def is_packed_pair(t):
+    """Is ``t`` the (packed [total, D] tokens, offsets int64 [n_img + 1]) pair of a ragged forward
+    (``HipDinoV2.forward_taps_ragged``)?"""
+    return isinstance(t, tuple) and len(t) == 2 and isinstance(t[0], torch.Tensor) and isinstance(t[1], torch.Tensor) \
+        and t[0].ndim == 2 and t[1].ndim == 1 and not t[1].is_floating_point()
+
+
 def _offsets_for(tokens_list_or_tensor, device):
     """-> (packed [total,D] device tensor, offsets int64 device tensor, n_img, D)."""
     t = tokens_list_or_tensor
+    if is_packed_pair(t):
+        # already packed (ragged forward): taken as it is, no copy
+        packed, offsets = t
+        n_img = offsets.numel() - 1
+        if n_img < 0:
+            raise ValueError("offsets of a packed pair need n_img + 1 >= 1 entries")
+        return _f32c(packed, device), offsets.to(device, torch.int64), n_img, packed.shape[1]
     if isinstance(t, torch.Tensor):
         if t.ndim == 2:
             t = t[None]
@@ -221,7 +235,8 @@ def vlad(tokens, centers, mode="hard", norm_descs=True, intra_norm=True, soft_te
          return_labels=False, dist_mode="cosine", parts=0, out=None):
     """VLAD descriptors of a batch of images.
 
-    tokens: device tensor [n_img, N, D] / [N, D], or a list of [N_i, D] tensors.
+    tokens: device tensor [n_img, N, D] / [N, D], a list of [N_i, D] tensors, or the (packed [total, D], offsets [n_img + 1])
+    pair of a ragged forward (taken without a copy).
     centers: [K, D].  ``dist_mode``: the metric of the hard assignment (the VLAD object's ``dist_mode``; the soft
     weights are always cosine, as in the reference).  ``parts`` (hard mode): workgroups per image as the caller's choice
     (ANYLOC_VLAD_PARTS; 0 = the library's) -- a batch handed over in pieces keeps the bits of the one-call result when every

@@ -256,6 +256,10 @@ class VLAD:
 
     def _generate_batch(self, multi_query):
         """[n_img,N,D] tensor or list of [N_i,D] -> [n_img, K*D] on the inputs' device."""
+        if ops.is_packed_pair(multi_query):           # (packed tokens, offsets) of a ragged forward: no per-image list
+            kw = dict(mode=self.vlad_mode, norm_descs=self.norm_descs, intra_norm=self.intra_norm,
+                      soft_temp=self.soft_temp, dist_mode=self.mode)
+            return ops.to_home(ops.vlad(multi_query, self._centers_dev(), **kw), multi_query[0].device)
         first = multi_query[0] if not isinstance(multi_query, torch.Tensor) else multi_query
         first = _as_tensor(first)
         home = first.device
@@ -299,8 +303,10 @@ class VLAD:
 
     def generate_multi(self, multi_query: Union[np.ndarray, torch.Tensor, list],
                        cache_ids: Union[List[str], None] = None) -> Union[torch.Tensor, list]:
-        """VLADs of several images ([n_imgs, n_kpts, d] tensor or a list of
-        [n_kpts_i, d]); one batched launch when no cache ids are involved."""
+        """VLADs of several images ([n_imgs, n_kpts, d] tensor, a list of [n_kpts_i, d], or the (packed, offsets) pair of
+        a ragged forward); one batched launch when no cache ids are involved."""
+        if ops.is_packed_pair(multi_query) and cache_ids is not None and any(c is not None for c in cache_ids):
+            raise ValueError("generate_multi: cache ids need one descriptor tensor per image, not a (packed, offsets) pair")
         self._check_fitted()
         if cache_ids is None or all(c is None for c in cache_ids) or not self.can_use_cache_vlad():
             if len(multi_query) == 0:

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ANYLOC_ABI_VERSION 9
+#define ANYLOC_ABI_VERSION 10
 
 typedef enum anyloc_status {
   ANYLOC_OK = 0,
@@ -68,6 +68,8 @@ const char* anyloc_last_error(void);
  *                                     64 queries (A/B: measured slower, profiles/r05_attention_qg2.log)
  *   attn_h3_ks (0)                    the same kernel's key splits: 2 = two query waves x two key waves per workgroup (half the serial
  *                                     chain of key tiles; partial sums meet in LDS), 1 = none, 0 = 2 when all workgroups are resident
+ *   attn_h3_ragged_xcd (1)            the same kernel over a ragged batch (anyloc_vit_forward_ragged): 1 = the (image, head) units
+ *                                     dealt round-robin over the 8 XCDs, 0 = contiguous ranges of units per XCD as in a uniform batch
  *   vlad_parts (0 = auto) vlad_two_pass (0) vlad_fused_v (0) kmeans_fused_v (0)
  *                                     which VLAD / k-means kernel serves a call
  *   topk_screen (-1)                  many queries against long rows: the screened search described at anyloc_topk_search_index_rows,
@@ -495,6 +497,41 @@ int anyloc_vit_forward(anyloc_vit_t* h, const float* img, int64_t batch,
                        int32_t n_taps, const int32_t* tap_layers,
                        const int32_t* tap_facets, unsigned flags, float* out,
                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* Ragged batches (ABI 10): images of DIFFERENT sizes in one forward, packed back to back.  Image i is
+ * img_hw[2i] x img_hw[2i+1] pixels (each a positive multiple of 14, else ANYLOC_ERR_INVALID_ARG before any
+ * device work), N_i = (H_i/14)(W_i/14) patches, T_i = N_i + 1 token rows (CLS first).  No image attends to
+ * another; flags, taps, anyloc_vit_block_ffn_exact and the telemetry mean what they mean for
+ * anyloc_vit_forward (per_image = 1: ffn_looseness[depth][n_img]).  The call is stream-ordered and never
+ * synchronises with the host: the sizes are read from the HOST array (grids, workspace, validation), the
+ * kernels read the same layout from dev_meta, which the caller builds from the same sizes:
+ *   dev_meta  device int64 [5][n_img + 1], row-major --
+ *     [0][i] token-row offset  sum_{j<i} T_j        ([0][n_img] = total rows)
+ *     [1][i] float offset of image i in img         sum_{j<i} 3 H_j W_j
+ *     [2][i] first row of image i's table in pos    (tables may be shared by images of one size)
+ *     [3][i] H_i,  [4][i] W_i                       ([1..4][n_img] unused)
+ *   img   the CHW images, image i at img + dev_meta[1][i]
+ *   pos   packed positional tables, [1 + N_i, D] for image i at row dev_meta[2][i]
+ *   out   [sum rows_i, n_taps*D], rows_i = N_i (+1 with USE_CLS); image i's rows start at dev_meta[0][i] - i
+ *         (dev_meta[0][i] with USE_CLS) -- offsets anyloc_vlad_hard / anyloc_vlad_soft take as they are */
+size_t anyloc_vit_workspace_bytes_ragged(const anyloc_vit_t* h, int32_t n_img,
+                                         const int32_t* img_hw /*host [n_img][2]*/);
+int anyloc_vit_forward_ragged(anyloc_vit_t* h, const float* img, int32_t n_img,
+                              const int32_t* img_hw /*host [n_img][2]*/,
+                              const int64_t* dev_meta, const float* pos,
+                              int32_t n_taps, const int32_t* tap_layers,
+                              const int32_t* tap_facets, unsigned flags, float* out,
+                              void* workspace, size_t workspace_bytes, void* stream);
+/* The attention kernels alone over a ragged batch (tests): tokens = host [n_img] lengths,
+ * tok_off = device [n_img + 1] int64 offsets of the same lengths; qkv [sum T_i, 3*dim].
+ * anyloc_attention_ragged: the fp32-MFMA / split-bf16 kernels (option attn_x6 as for
+ * anyloc_attention), out [sum T_i, dim].  anyloc_attention_h3_ragged: the two-term fp16 kernel,
+ * output as for anyloc_attention_h3; workspace: anyloc_attention_h3_workspace_bytes(1, sum T_i, heads). */
+int anyloc_attention_ragged(const float* qkv, float* out, int32_t n_img, const int32_t* tokens,
+                            const int64_t* tok_off, int64_t dim, int64_t heads, void* stream);
+int anyloc_attention_h3_ragged(const float* qkv, void* out_img, float* out_inv, int32_t n_img,
+                               const int32_t* tokens, const int64_t* tok_off, int64_t dim,
+                               int64_t heads, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Name and average device time (ms, HIP events on the launch stream) of the
  * kernels issued by the most recent call with profiling enabled; used by
