@@ -351,24 +351,27 @@ int im2col(const float* img, float* col, int64_t batch, int H, int W, int P, int
            hipStream_t stream);
 int cls_rows(float* x, const float* cls, const float* pos, int64_t batch, int T, int dim,
              hipStream_t stream);
+// the kept rows of every T-row image: skip leading rows, and gap more after row 0 (the register rows behind a kept CLS row)
 int facet_rows(const float* src, int64_t lds_, int coff, float* out, int64_t ldo, int ooff,
-               int64_t batch, int T, int skip, int rows_per_img, int dim, int normalize, float eps,
+               int64_t batch, int T, int skip, int gap, int rows_per_img, int dim, int normalize, float eps,
                hipStream_t stream);
 int attention(const float* qkv, float* out, int64_t batch, int T, int D, int heads,
               hipStream_t stream, unsigned char* out3 = nullptr,    // out3: write the result as a plane image instead
               bool x6 = false);                                      // x6: split-bf16 matrix products
 
 // ragged batches (anyloc_vit_forward_ragged): the device table `meta` is int64 [RAGGED_ROWS][n_img + 1], row-major --
-//   RAGGED_TOK: token-row offsets (T_i = N_i + 1 rows per image, CLS first), entry n_img = total rows
+//   RAGGED_TOK: token-row offsets (T_i = 1 + R + N_i rows per image: CLS, R registers, patches), entry n_img = total rows
 //   RAGGED_PIX: float offset of image i in the packed CHW input, RAGGED_POS: first row of image i's positional table in the
 //   packed tables, RAGGED_H / RAGGED_W: the image size (last entry of these three unused)
 enum { RAGGED_TOK = 0, RAGGED_PIX = 1, RAGGED_POS = 2, RAGGED_H = 3, RAGGED_W = 4, RAGGED_ROWS = 5 };
-int im2col_ragged(const float* img, float* col, const int64_t* meta, int n_img, int64_t patch_rows, int P, int kpad,
+int im2col_ragged(const float* img, float* col, const int64_t* meta, int n_img, int R, int64_t patch_rows, int P, int kpad,
                   hipStream_t stream);
-int embed_ragged(float* x, const float* patch, const float* cls, const float* pos, const int64_t* meta, int n_img, int64_t rows,
-                 int dim, hipStream_t stream);
+// the token rows from the patch GEMM's output [P, D]: CLS + pos[0], R register rows, patch + pos rows.  meta == nullptr: a
+// uniform batch of T-row images sharing the table pos; otherwise the ragged table (T unused)
+int embed_rows(float* x, const float* patch, const float* cls, const float* reg, int R, const float* pos, const int64_t* meta,
+               int n_img, int T, int64_t rows, int dim, hipStream_t stream);
 int facet_rows_ragged(const float* src, int64_t lds_, int coff, float* out, int64_t ldo, int ooff, const int64_t* meta,
-                      int n_img, int64_t out_rows, int skip, int dim, int normalize, float eps, hipStream_t stream);
+                      int n_img, int64_t out_rows, int skip, int gap, int dim, int normalize, float eps, hipStream_t stream);
 // attention over images of different lengths: tok_off = device [n_img + 1] row offsets, max_T the longest image
 int attention_ragged(const float* qkv, float* out, int n_img, int max_T, const int64_t* tok_off, int64_t rows, int D, int heads,
                      hipStream_t stream, unsigned char* out3, bool x6);

@@ -104,16 +104,17 @@ __global__ __launch_bounds__(256) void cls_row_kernel(float* __restrict__ x, con
   for (int i = threadIdx.x; i < dim; i += 256) dst[i] = cls[i] + pos[i];
 }
 
-// out[b, n, ooff + d] = src[(b*T + skip + n), coff + d]   (optionally / max(||.||, eps))
+// out[b, n, ooff + d] = src[(b*T + skip + n + (n > 0 ? gap : 0)), coff + d]   (optionally / max(||.||, eps))
+// (gap: the register rows that follow a kept CLS row; without the CLS row skip = 1 + R covers them)
 __global__ __launch_bounds__(256) void facet_rows_kernel(const float* __restrict__ src, int64_t lds_, int coff,
                                                          float* __restrict__ out, int64_t ldo, int ooff, int T,
-                                                         int skip, int rows_per_img, int dim, int normalize,
+                                                         int skip, int gap, int rows_per_img, int dim, int normalize,
                                                          float eps) {
   __shared__ float red[4];
   const int64_t orow = blockIdx.x;
   const int64_t b = orow / rows_per_img;
   const int n = (int)(orow - b * rows_per_img);
-  const f32x4* s = reinterpret_cast<const f32x4*>(src + (b * T + skip + n) * lds_ + coff);
+  const f32x4* s = reinterpret_cast<const f32x4*>(src + (b * T + skip + n + (n > 0 ? gap : 0)) * lds_ + coff);
   f32x4* o = reinterpret_cast<f32x4*>(out + orow * ldo + ooff);
   const int n4 = dim >> 2;
   float nrm = 1.0f;
@@ -133,10 +134,11 @@ __global__ __launch_bounds__(256) void facet_rows_kernel(const float* __restrict
 }
 
 // ---- ragged batches (anyloc_vit_forward_ragged): images of different sizes packed back to back ----
-// meta = the device table of common.hpp (RAGGED_* rows of n_img + 1 int64 each).  Image i owns token rows
-// tok[i] .. tok[i+1], patch rows tok[i] - i .. tok[i+1] - i - 1 and, without the CLS row, output rows tok[i] - i ..
+// meta = the device table of common.hpp (RAGGED_* rows of n_img + 1 int64 each).  With R register rows per image, image i
+// owns token rows tok[i] .. tok[i+1], patch rows tok[i] - i(1+R) .. tok[i+1] - (i+1)(1+R) - 1 and output rows from
+// tok[i] - i(1+R) (tok[i] - iR with the CLS row)
 
-// the image whose rows [off(i), off(i+1)) hold row r, off(i) = tok[i] - sub * i (strictly ascending for sub <= 1)
+// the image whose rows [off(i), off(i+1)) hold row r, off(i) = tok[i] - sub * i (strictly ascending for sub <= 1 + R)
 __device__ __forceinline__ int ragged_image(const int64_t* __restrict__ tok, int n_img, int64_t r, int sub) {
   int lo = 0, hi = n_img - 1;
   while (lo < hi) {
@@ -147,14 +149,15 @@ __device__ __forceinline__ int ragged_image(const int64_t* __restrict__ tok, int
   return lo;
 }
 
-// col[patch row, c*P*P + i*P + j] = img_i[c, py*P + i, px*P + j] for the image i that owns the patch row
+// col[patch row, c*P*P + i*P + j] = img_i[c, py*P + i, px*P + j] for the image i that owns the patch row (R register rows
+// per image: patch rows of image i from tok[i] - i(1+R))
 __global__ __launch_bounds__(256) void im2col_ragged_kernel(const float* __restrict__ img, float* __restrict__ col,
-                                                            const int64_t* __restrict__ meta, int n_img, int P, int kpad) {
+                                                            const int64_t* __restrict__ meta, int n_img, int R, int P, int kpad) {
   const int64_t prow = blockIdx.x;
   const int64_t stride = n_img + 1;
-  const int i = ragged_image(meta, n_img, prow, 1);
+  const int i = ragged_image(meta, n_img, prow, 1 + R);
   const int H = (int)meta[RAGGED_H * stride + i], W = (int)meta[RAGGED_W * stride + i], gw = W / P;
-  const int pi = (int)(prow - (meta[i] - i)), py = pi / gw, px = pi - py * gw;
+  const int pi = (int)(prow - (meta[i] - (int64_t)(1 + R) * i)), py = pi / gw, px = pi - py * gw;
   const float* src = img + meta[RAGGED_PIX * stride + i];
   const int kk = 3 * P * P;
   float* dst = col + prow * kpad;
@@ -168,29 +171,47 @@ __global__ __launch_bounds__(256) void im2col_ragged_kernel(const float* __restr
   }
 }
 
-// token row t of image i: x = cls + pos_i[0] (t = 0) or patch[patch row] + pos_i[t] -- the sums EPI_PATCH and
-// cls_row_kernel form in the uniform forward
-__global__ __launch_bounds__(256) void embed_ragged_kernel(float* __restrict__ x, const float* __restrict__ patch,
-                                                           const float* __restrict__ cls, const float* __restrict__ pos,
-                                                           const int64_t* __restrict__ meta, int n_img, int dim) {
+// token row t of image i: x = cls + pos_i[0] (t = 0), reg[t - 1] (1 <= t <= R, no positional term) or
+// patch[patch row] + pos_i[t - R] -- the sums EPI_PATCH and cls_row_kernel form in the plain uniform forward.
+// meta == nullptr: a uniform batch of T-row images sharing one table; otherwise the ragged table
+__global__ __launch_bounds__(256) void embed_rows_kernel(float* __restrict__ x, const float* __restrict__ patch,
+                                                         const float* __restrict__ cls, const float* __restrict__ reg, int R,
+                                                         const float* __restrict__ pos, const int64_t* __restrict__ meta,
+                                                         int n_img, int T, int dim) {
   const int64_t row = blockIdx.x;
-  const int i = ragged_image(meta, n_img, row, 0);
-  const int64_t t = row - meta[i];
-  const float* pr = pos + (meta[RAGGED_POS * (int64_t)(n_img + 1) + i] + t) * dim;
-  const float* sr = t == 0 ? cls : patch + (row - i - 1) * dim;
+  int64_t i, t;
+  const float* pb = pos;
+  if (meta) {
+    i = ragged_image(meta, n_img, row, 0);
+    t = row - meta[i];
+    pb += meta[RAGGED_POS * (int64_t)(n_img + 1) + i] * dim;
+  } else {
+    i = row / T;
+    t = row - i * T;
+  }
   float* dst = x + row * dim;
+  if (t >= 1 && t <= R) {
+    const float* rr = reg + (t - 1) * dim;
+    for (int k = threadIdx.x; k < dim; k += 256) dst[k] = rr[k];
+    return;
+  }
+  const float* pr = pb + (t == 0 ? 0 : t - R) * dim;
+  const float* sr = t == 0 ? cls : patch + (row - (i + 1) * (1 + R)) * dim;
   for (int k = threadIdx.x; k < dim; k += 256) dst[k] = sr[k] + pr[k];
 }
 
-// out[orow, ooff + d] = src[tok[i] + skip + n, coff + d], orow = tok[i] - skip * i + n   (optionally / max(||.||, eps))
+// out[orow, ooff + d] = src[tok[i] + skip + n + (n > 0 ? gap : 0), coff + d], orow = tok[i] - (skip + gap) * i + n
+// (optionally / max(||.||, eps))
 __global__ __launch_bounds__(256) void facet_rows_ragged_kernel(const float* __restrict__ src, int64_t lds_, int coff,
                                                                 float* __restrict__ out, int64_t ldo, int ooff,
                                                                 const int64_t* __restrict__ meta, int n_img, int skip,
-                                                                int dim, int normalize, float eps) {
+                                                                int gap, int dim, int normalize, float eps) {
   __shared__ float red[4];
   const int64_t orow = blockIdx.x;
-  const int i = ragged_image(meta, n_img, orow, skip);
-  const int64_t srow = orow + (int64_t)skip * (i + 1);
+  const int sub = skip + gap;
+  const int i = ragged_image(meta, n_img, orow, sub);
+  const int64_t n = orow - (meta[i] - (int64_t)sub * i);
+  const int64_t srow = orow + (int64_t)sub * i + skip + (n > 0 ? gap : 0);
   const f32x4* s = reinterpret_cast<const f32x4*>(src + srow * lds_ + coff);
   f32x4* o = reinterpret_cast<f32x4*>(out + orow * ldo + ooff);
   const int n4 = dim >> 2;
@@ -272,36 +293,37 @@ int cls_rows(float* x, const float* cls, const float* pos, int64_t batch, int T,
 }
 
 int facet_rows(const float* src, int64_t lds_, int coff, float* out, int64_t ldo, int ooff, int64_t batch, int T,
-               int skip, int rows_per_img, int dim, int normalize, float eps, hipStream_t stream) {
+               int skip, int gap, int rows_per_img, int dim, int normalize, float eps, hipStream_t stream) {
   ANYLOC_CHECK_ARG(dim % 4 == 0 && coff % 4 == 0 && ooff % 4 == 0 && lds_ % 4 == 0 && ldo % 4 == 0,
                    "facet_rows: alignment");
   ProfScope prof("facet_rows", stream, 3.0 * batch * rows_per_img * dim, 8.0 * batch * rows_per_img * dim);
   hipLaunchKernelGGL(facet_rows_kernel, dim3((unsigned)(batch * rows_per_img)), dim3(256), 0, stream, src, lds_, coff,
-                     out, ldo, ooff, T, skip, rows_per_img, dim, normalize, eps);
+                     out, ldo, ooff, T, skip, gap, rows_per_img, dim, normalize, eps);
   return launch_status("facet_rows_kernel");
 }
 
-int im2col_ragged(const float* img, float* col, const int64_t* meta, int n_img, int64_t patch_rows, int P, int kpad,
+int im2col_ragged(const float* img, float* col, const int64_t* meta, int n_img, int R, int64_t patch_rows, int P, int kpad,
                   hipStream_t stream) {
   ProfScope prof("im2col", stream, 0.0, 8.0 * patch_rows * kpad);
-  hipLaunchKernelGGL(im2col_ragged_kernel, dim3((unsigned)patch_rows), dim3(256), 0, stream, img, col, meta, n_img, P, kpad);
+  hipLaunchKernelGGL(im2col_ragged_kernel, dim3((unsigned)patch_rows), dim3(256), 0, stream, img, col, meta, n_img, R, P, kpad);
   return launch_status("im2col_ragged_kernel");
 }
 
-int embed_ragged(float* x, const float* patch, const float* cls, const float* pos, const int64_t* meta, int n_img, int64_t rows,
-                 int dim, hipStream_t stream) {
+int embed_rows(float* x, const float* patch, const float* cls, const float* reg, int R, const float* pos, const int64_t* meta,
+               int n_img, int T, int64_t rows, int dim, hipStream_t stream) {
   ProfScope prof("cls_rows", stream, (double)rows * dim, 12.0 * rows * dim);
-  hipLaunchKernelGGL(embed_ragged_kernel, dim3((unsigned)rows), dim3(256), 0, stream, x, patch, cls, pos, meta, n_img, dim);
-  return launch_status("embed_ragged_kernel");
+  hipLaunchKernelGGL(embed_rows_kernel, dim3((unsigned)rows), dim3(256), 0, stream, x, patch, cls, reg, R, pos, meta, n_img, T,
+                     dim);
+  return launch_status("embed_rows_kernel");
 }
 
 int facet_rows_ragged(const float* src, int64_t lds_, int coff, float* out, int64_t ldo, int ooff, const int64_t* meta,
-                      int n_img, int64_t out_rows, int skip, int dim, int normalize, float eps, hipStream_t stream) {
+                      int n_img, int64_t out_rows, int skip, int gap, int dim, int normalize, float eps, hipStream_t stream) {
   ANYLOC_CHECK_ARG(dim % 4 == 0 && coff % 4 == 0 && ooff % 4 == 0 && lds_ % 4 == 0 && ldo % 4 == 0,
                    "facet_rows: alignment");
   ProfScope prof("facet_rows", stream, 3.0 * out_rows * dim, 8.0 * out_rows * dim);
   hipLaunchKernelGGL(facet_rows_ragged_kernel, dim3((unsigned)out_rows), dim3(256), 0, stream, src, lds_, coff, out, ldo, ooff,
-                     meta, n_img, skip, dim, normalize, eps);
+                     meta, n_img, skip, gap, dim, normalize, eps);
   return launch_status("facet_rows_ragged_kernel");
 }
 

@@ -29,6 +29,8 @@ struct anyloc_vit {
   const float* patch_w;
   const float* patch_b;
   const float* cls;
+  const float* regs = nullptr;              // register tokens (device [n_reg, dim], caller-owned) or null
+  int n_reg = 0;                            // R: token rows per image are CLS, R registers, patches
   std::vector<anyloc_vit_block_weights> blocks;
   std::vector<anyloc_vit_block_x3> x3;      // optional: three-plane bf16 images of the four weight matrices
   std::vector<anyloc_vit_block_h2> h2;      // optional: two-plane fp16 images + row scales of the same matrices
@@ -324,6 +326,15 @@ int anyloc_vit_attach_h2(anyloc_vit_t* h, const anyloc_vit_block_h2* blocks) {
   return ANYLOC_OK;
 }
 
+int anyloc_vit_set_registers(anyloc_vit_t* h, const float* register_tokens, int32_t n_registers) {
+  ANYLOC_CHECK_ARG(h, "vit_set_registers: null handle");
+  ANYLOC_CHECK_ARG(n_registers >= 0 && n_registers <= 16, "vit_set_registers: %d registers outside [0, 16]", n_registers);
+  ANYLOC_CHECK_ARG(register_tokens || n_registers == 0, "vit_set_registers: null register tokens with %d registers", n_registers);
+  h->regs = n_registers ? register_tokens : nullptr;
+  h->n_reg = n_registers;
+  return ANYLOC_OK;
+}
+
 int anyloc_vit_set_telemetry(anyloc_vit_t* h, float* ffn_looseness, int32_t per_image) {
   ANYLOC_CHECK_ARG(h, "vit_set_telemetry: null handle");
   h->ffn_looseness = ffn_looseness;
@@ -346,7 +357,7 @@ void anyloc_vit_destroy(anyloc_vit_t* h) {
 size_t anyloc_vit_workspace_bytes(const anyloc_vit_t* h, int64_t batch, int64_t img_h, int64_t img_w) {
   if (!h || batch <= 0 || img_h < h->cfg.patch || img_w < h->cfg.patch) return 0;
   const int64_t np = (img_h / h->cfg.patch) * (img_w / h->cfg.patch);
-  return carve(nullptr, 0, h->cfg, batch * (np + 1), batch * np).bytes + 256;
+  return carve(nullptr, 0, h->cfg, batch * (np + 1 + h->n_reg), batch * np).bytes + 256;
 }
 
 // a ragged batch (anyloc_vit_forward_ragged): images of different sizes packed back to back
@@ -365,8 +376,9 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
                                 const RaggedBatch* rg = nullptr) {
   const anyloc_vit_config& c = h->cfg;
   const int D = c.dim, gh = rg ? 0 : (int)(img_h / c.patch), gw = rg ? 0 : (int)(img_w / c.patch), np = gh * gw;
-  const int T = rg ? rg->max_T : np + 1;
-  const int64_t M = rg ? rg->rows : batch * T, P = rg ? rg->rows - batch : batch * np;
+  const int R = h->n_reg;                       // register rows per image (after CLS, before the patches)
+  const int T = rg ? rg->max_T : np + 1 + R;
+  const int64_t M = rg ? rg->rows : batch * T, P = rg ? rg->rows - batch * (1 + R) : batch * np;
   const int64_t* meta = rg ? rg->meta : nullptr;
   VitWs w = carve(workspace, workspace_bytes, c, M, P);
   if (!workspace || w.bytes > workspace_bytes) {
@@ -385,14 +397,15 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
   const bool fuse_x6 = x6 && option(OPT_X6_FUSE) != 0;
   const bool h3f = h3m && option(OPT_H3_FUSE) != 0;
   const bool use_cls = flags & ANYLOC_VIT_USE_CLS;
-  const int rows_per_img = use_cls ? T : np, skip = use_cls ? 0 : 1;
-  const int64_t out_rows = rg ? (use_cls ? M : P) : batch * rows_per_img;
+  // the tap drops the register rows: without the CLS row a skip of 1 + R, with it a gap of R behind row 0
+  const int rows_per_img = use_cls ? np + 1 : np, skip = use_cls ? 0 : 1 + R, gap = use_cls ? R : 0;
+  const int64_t out_rows = rg ? (use_cls ? M - batch * R : P) : batch * rows_per_img;
   const int64_t ldo = (int64_t)n_taps * D;
   const int norm_taps = (flags & ANYLOC_VIT_NORM_TAPS) ? 1 : 0;
   // the tapped rows of src (width lds_, columns coff ..) -> out columns ooff ..
   auto facet = [&](const float* src, int64_t lds_, int coff, int ooff) {
-    if (rg) return facet_rows_ragged(src, lds_, coff, out, ldo, ooff, meta, (int)batch, out_rows, skip, D, norm_taps, 1e-12f, stream);
-    return facet_rows(src, lds_, coff, out, ldo, ooff, batch, T, skip, rows_per_img, D, norm_taps, 1e-12f, stream);
+    if (rg) return facet_rows_ragged(src, lds_, coff, out, ldo, ooff, meta, (int)batch, out_rows, skip, gap, D, norm_taps, 1e-12f, stream);
+    return facet_rows(src, lds_, coff, out, ldo, ooff, batch, T, skip, gap, rows_per_img, D, norm_taps, 1e-12f, stream);
   };
   const int last_layer = tap_layers[n_taps - 1];
   // split-K arrival counters; with telemetry on also the rows' maxima of every block that will run (adjacent: one memset)
@@ -411,12 +424,13 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
   float* col = w.qkv;
   const bool patch_h3 = h3m && h->patch_w2 && option(OPT_H3_PATCH) != 0;
   const int kp = patch_h3 ? (c.patch_k_pad + 15) / 16 * 16 : c.patch_k_pad;    // fp16 mode: whole 16-element k-blocks
-  if (rg) ANYLOC_TRY(im2col_ragged(img, col, meta, (int)batch, P, c.patch, kp, stream));
+  if (rg) ANYLOC_TRY(im2col_ragged(img, col, meta, (int)batch, R, P, c.patch, kp, stream));
   else ANYLOC_TRY(im2col(img, col, batch, (int)img_h, (int)img_w, c.patch, kp, stream));
-  // ragged: the patch GEMM with its bias epilogue into w.y [P, D]; embed_ragged then adds each image's positional rows and
-  // writes the CLS rows (the same two sums as EPI_PATCH + cls_rows)
-  float* patch_out = rg ? w.y : w.x;
-  const int patch_epi = rg ? EPI_STORE : EPI_PATCH;
+  // ragged or with registers: the patch GEMM with its bias epilogue into w.y [P, D]; embed_rows then adds each image's
+  // positional rows and writes the CLS and register rows (the same two sums as EPI_PATCH + cls_rows)
+  const bool embed_pass = rg || R > 0;
+  float* patch_out = embed_pass ? w.y : w.x;
+  const int patch_epi = embed_pass ? EPI_STORE : EPI_PATCH;
   if (patch_h3) {
     // fp16 mode: the gathered patches are quantised like every other operand (row maximum -> power-of-two scale)
     ANYLOC_TRY(split_h2(col, kp, P, kp, w.a3, w.ainv, stream));
@@ -426,7 +440,7 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
     g.C = patch_out; g.ldc = D;
     g.M = P; g.N = D; g.K16 = kp / 16;
     g.bias = h->patch_b;
-    g.pos = rg ? nullptr : pos;
+    g.pos = embed_pass ? nullptr : pos;
     g.patches = np;
     g.tag = "vit_patch_embed_gemm";
     ANYLOC_TRY(gemm_h3(g, patch_epi, stream));
@@ -437,12 +451,12 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
     g.C = patch_out; g.ldc = D;
     g.M = P; g.N = D; g.K = c.patch_k_pad;
     g.bias = h->patch_b;
-    g.pos = rg ? nullptr : pos;
+    g.pos = embed_pass ? nullptr : pos;
     g.patches = np;
     g.tag = "vit_patch_embed_gemm";
     ANYLOC_TRY(gemm_nt(g, patch_epi, stream));
   }
-  if (rg) ANYLOC_TRY(embed_ragged(w.x, w.y, h->cls, pos, meta, (int)batch, M, D, stream));
+  if (embed_pass) ANYLOC_TRY(embed_rows(w.x, w.y, h->cls, h->regs, R, pos, meta, (int)batch, T, M, D, stream));
   else ANYLOC_TRY(cls_rows(w.x, h->cls, pos, batch, T, D, stream));
 
   for (int l = 0; l <= last_layer; ++l) {
@@ -621,7 +635,7 @@ static int ragged_shape(const anyloc_vit_t* h, int32_t n_img, const int32_t* img
     ANYLOC_CHECK_ARG(ih >= P && iw >= P && ih % P == 0 && iw % P == 0 && ih <= 65535 && iw <= 65535,
                      "%s: image %d is %lldx%lld, not a positive multiple of the patch size %d", who, i, (long long)ih,
                      (long long)iw, P);
-    const int64_t T = (ih / P) * (iw / P) + 1;
+    const int64_t T = (ih / P) * (iw / P) + 1 + h->n_reg;
     ANYLOC_CHECK_ARG(T < (1 << 30), "%s: image %d has too many tokens", who, i);
     r += T;
     mt = std::max<int>(mt, (int)T);
@@ -636,7 +650,7 @@ size_t anyloc_vit_workspace_bytes_ragged(const anyloc_vit_t* h, int32_t n_img, c
   int64_t rows = 0;
   int max_T = 0;
   if (ragged_shape(h, n_img, img_hw, &rows, &max_T, "vit_workspace_bytes_ragged") != ANYLOC_OK) return 0;
-  return carve(nullptr, 0, h->cfg, rows, rows - n_img).bytes + 256;
+  return carve(nullptr, 0, h->cfg, rows, rows - (int64_t)n_img * (1 + h->n_reg)).bytes + 256;
 }
 
 int anyloc_vit_forward_ragged(anyloc_vit_t* h, const float* img, int32_t n_img, const int32_t* img_hw, const int64_t* dev_meta,

@@ -20,7 +20,7 @@ import torch
 from torch.nn import functional as F
 
 from . import _lib, ops, weights
-from .synth import ARCH, PATCH, POS_GRID
+from .synth import ARCH, PATCH, POS_GRID, n_registers
 
 DEFAULT_GEMM = "h3"      # block-GEMM arithmetic when neither the constructor nor ANYLOC_GEMM says otherwise
 # FFN-bound telemetry of the h3 forward (include/anyloc_hip.h, anyloc_vit_set_telemetry): EVERY call measures, per executed
@@ -31,7 +31,9 @@ DEFAULT_GEMM = "h3"      # block-GEMM arithmetic when neither the constructor no
 # calls (round 5 sampled call 0 and every 64th, and a tripped block stayed switched for the handle's life).  Within 2^18 of
 # the bound every element keeps its 22 bits relative to the row maximum; 2^14 leaves a margin of 4.
 FFN_LOOSENESS_MAX = 2.0 ** 14
-_DINO_V2_MODELS = ("dinov2_vits14", "dinov2_vitb14", "dinov2_vitl14", "dinov2_vitg14")
+_DINO_V2_MODELS = ("dinov2_vits14", "dinov2_vitb14", "dinov2_vitl14", "dinov2_vitg14",
+                   # with four register tokens: the patch grid comes back, never the register rows
+                   "dinov2_vits14_reg", "dinov2_vitb14_reg", "dinov2_vitl14_reg", "dinov2_vitg14_reg")
 _DINO_FACETS = ("query", "key", "value", "token")
 INTERP_OFFSET = 0.1
 
@@ -73,12 +75,32 @@ def interpolate_pos_embed(pos_embed, h_img, w_img):
     return torch.cat([pos_embed[0, :1], grid], dim=0).contiguous()
 
 
-def ragged_chunks(sizes, max_rows, patch=PATCH):
-    """Greedy packing of images of sizes [(H, W), ...] in input order under a budget of ``max_rows`` token rows per call:
-    -> [(start, stop), ...] index ranges.  An image whose own rows exceed the budget runs alone."""
+def interpolate_pos_embed_reg(pos_embed, h_img, w_img):
+    """Positional table of the models with registers (hub ``dinov2_vit*14_reg``: ``interpolate_antialias=True``,
+    ``interpolate_offset=0.0``): bicubic with antialias, align_corners=False, driven by the output size
+    ``(h/14, w/14)``; skipped for the native square grid.  [1, 1+37*37, D] -> [1 + (h/14)*(w/14), D]; the register rows
+    have no positional term."""
+    pos_embed = pos_embed.detach().to("cpu", torch.float32)
+    n_tab = pos_embed.shape[1] - 1
+    gh, gw = h_img // PATCH, w_img // PATCH
+    if gh * gw == n_tab and h_img == w_img:
+        return pos_embed[0].contiguous()
+    m = int(math.sqrt(n_tab))
+    assert m * m == n_tab
+    dim = pos_embed.shape[-1]
+    grid = pos_embed[:, 1:].reshape(1, m, m, dim).permute(0, 3, 1, 2)
+    grid = F.interpolate(grid, size=(gh, gw), mode="bicubic", align_corners=False, antialias=True)
+    grid = grid.permute(0, 2, 3, 1).reshape(gh * gw, dim)
+    return torch.cat([pos_embed[0, :1], grid], dim=0).contiguous()
+
+
+def ragged_chunks(sizes, max_rows, patch=PATCH, registers=0):
+    """Greedy packing of images of sizes [(H, W), ...] in input order under a budget of ``max_rows`` token rows per call
+    (1 + ``registers`` + N_i per image): -> [(start, stop), ...] index ranges.  An image whose own rows exceed the budget
+    runs alone."""
     chunks, start, rows = [], 0, 0
     for i, (h, w) in enumerate(sizes):
-        t = (int(h) // patch) * (int(w) // patch) + 1
+        t = (int(h) // patch) * (int(w) // patch) + 1 + registers
         if i > start and rows + t > max_rows:
             chunks.append((start, i))
             start, rows = i, 0
@@ -88,15 +110,16 @@ def ragged_chunks(sizes, max_rows, patch=PATCH):
     return chunks
 
 
-def ragged_offsets(sizes, use_cls, patch=PATCH):
+def ragged_offsets(sizes, use_cls, patch=PATCH, registers=0):
     """Row layout of one ragged call (include/anyloc_hip.h, anyloc_vit_forward_ragged): -> (tok_off, out_off, pix_off),
-    int64 NumPy arrays of len(sizes) + 1 -- token rows (T_i = N_i + 1), output rows (N_i, or T_i with the CLS row) and
-    float offsets of the packed CHW images."""
+    int64 NumPy arrays of len(sizes) + 1 -- token rows (T_i = 1 + registers + N_i), output rows (N_i, or N_i + 1 with the
+    CLS row; never the register rows) and float offsets of the packed CHW images."""
     hw = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
     n = (hw[:, 0] // patch) * (hw[:, 1] // patch)
     tok = np.zeros(len(hw) + 1, dtype=np.int64)
-    tok[1:] = np.cumsum(n + 1)
-    out = tok.copy() if use_cls else tok - np.arange(len(hw) + 1, dtype=np.int64)
+    tok[1:] = np.cumsum(n + 1 + registers)
+    idx = np.arange(len(hw) + 1, dtype=np.int64)
+    out = tok - registers * idx if use_cls else tok - (1 + registers) * idx
     pix = np.zeros(len(hw) + 1, dtype=np.int64)
     pix[1:] = np.cumsum(3 * hw[:, 0] * hw[:, 1])
     return tok, out, pix
@@ -124,6 +147,7 @@ class HipDinoV2:
         if max_layer is not None:
             depth = min(depth, max_layer + 1)
         self.name, self.dim, self.depth, self.heads, self.hidden = name, dim, depth, heads, hidden
+        self.n_reg = n_registers(name)     # register rows between CLS and the patches
         self.ffn_kind = 0 if ffn == "mlp" else 1
         self.device = device
         dev = lambda t: t.detach().to(device, torch.float32).contiguous()
@@ -137,6 +161,9 @@ class HipDinoV2:
         patch_w = keep(state_dict["patch_embed.proj.weight"].reshape(dim, 3 * PATCH * PATCH))
         patch_b = keep(state_dict["patch_embed.proj.bias"])
         cls = keep(state_dict["cls_token"].reshape(dim))
+        if self.n_reg and "register_tokens" not in state_dict:
+            raise ValueError(f"{name}: the state dict has no register_tokens (a checkpoint of the plain model?)")
+        regs = keep(state_dict["register_tokens"].reshape(self.n_reg, dim)) if self.n_reg else None
         self.full_depth = ARCH[name][1]
         self._final_norm = (keep(state_dict["norm.weight"]), keep(state_dict["norm.bias"])) \
             if "norm.weight" in state_dict else None
@@ -206,6 +233,8 @@ class HipDinoV2:
         lib = _lib.load()
         _lib.check(lib.anyloc_vit_create(C.byref(self._handle), C.byref(cfg), _lib.ptr(patch_w),
                                          _lib.ptr(patch_b), _lib.ptr(cls), blocks), "anyloc_vit_create")
+        if regs is not None:
+            _lib.check(lib.anyloc_vit_set_registers(self._handle, _lib.ptr(regs), self.n_reg), "anyloc_vit_set_registers")
         if self.gemm == "x6":
             _lib.check(lib.anyloc_vit_attach_x3(self._handle, x3), "anyloc_vit_attach_x3")
         if self.gemm == "h3":
@@ -252,7 +281,8 @@ class HipDinoV2:
     def pos_table(self, H, W):
         key = (H, W)
         if key not in self._pos_cache:
-            self._pos_cache[key] = interpolate_pos_embed(self.pos_embed_host, H, W).to(self.device)
+            interp = interpolate_pos_embed_reg if self.n_reg else interpolate_pos_embed
+            self._pos_cache[key] = interp(self.pos_embed_host, H, W).to(self.device)
         return self._pos_cache[key]
 
     @torch.no_grad()
@@ -289,7 +319,7 @@ class HipDinoV2:
             for h, w in sizes:
                 if h % PATCH or w % PATCH or h < PATCH or w < PATCH:
                     raise ValueError(f"image {h}x{w} is not a positive multiple of the patch size {PATCH}")
-            tok, out_off, pix = ragged_offsets(sizes, use_cls)
+            tok, out_off, pix = ragged_offsets(sizes, use_cls, registers=self.n_reg)
             if flat.numel() != pix[-1]:
                 raise ValueError(f"packed buffer holds {flat.numel()} floats, the sizes need {int(pix[-1])}")
             taps = list(taps)
@@ -298,7 +328,7 @@ class HipDinoV2:
                     raise IndexError(f"layer {layer} outside the {self.depth} loaded blocks")
             order = sorted(range(len(taps)), key=lambda i: taps[i][0])
             offsets = torch.from_numpy(out_off).to(self.device)
-            chunks = ragged_chunks(sizes, self.max_rows)
+            chunks = ragged_chunks(sizes, self.max_rows, registers=self.n_reg)
             inv = [order.index(i) for i in range(len(taps))] if order != list(range(len(taps))) else None
             # one chunk (the common case): the forward writes the caller's result directly; several: into slices of it
             out = None if len(chunks) == 1 and inv is None else \
@@ -320,7 +350,7 @@ class HipDinoV2:
     def _forward_ragged(self, flat, sizes, taps, use_cls, norm_taps, norm_concat):
         """One ragged call (taps ascending) over images that fit one launch sequence -> [sum rows_i, len(taps)*D]."""
         n_img, n_taps = len(sizes), len(taps)
-        tok, out_off, pix = ragged_offsets(sizes, use_cls)
+        tok, out_off, pix = ragged_offsets(sizes, use_cls, registers=self.n_reg)
         out = torch.empty(int(out_off[-1]), n_taps * self.dim, dtype=torch.float32, device=self.device)
         # positional tables: one per distinct size (the pos_table cache), packed, addressed per image by its first row
         first, tables, pos_row, at = {}, [], [], 0
@@ -438,7 +468,7 @@ class HipDinoV2:
         out = torch.empty(B, rows, n_taps * self.dim, dtype=torch.float32, device=self.device)
         if B == 0:
             return out
-        chunk = max(1, self.max_rows // (np_ + 1))
+        chunk = max(1, self.max_rows // (np_ + 1 + self.n_reg))
         if self.gemm in ("x6", "h3") and B > chunk:
             for s0 in range(0, B, chunk):
                 out[s0:s0 + chunk] = self._forward_taps(img[s0:s0 + chunk], taps, use_cls, norm_taps, norm_concat)

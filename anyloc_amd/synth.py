@@ -18,6 +18,10 @@ ARCH = {
     "dinov2_vitl14": (1024, 24, 16, "mlp", 4096),
     "dinov2_vitg14": (1536, 40, 24, "swiglu", 4096),
 }
+# DINOv2 with registers (hub dinov2_vit*14_reg, checkpoints <base>_reg4_pretrain.pth): the base shapes plus learned register
+# tokens that sit between CLS and the patches
+REGISTERS = {f"{base}_reg": 4 for base in tuple(ARCH)}
+ARCH.update({name: ARCH[name[:-len("_reg")]] for name in REGISTERS})
 PATCH = 14
 POS_GRID = 37
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
@@ -36,7 +40,15 @@ def synthetic_state_dict(name, seed=0, device="cpu", depth=None):
     Not an identity-ish init: biases, LayerNorm affine parameters and LayerScale
     gammas are all non-trivial so that every fused epilogue is exercised.
     ``depth`` truncates the block list (tests only need blocks <= hook layer).
+    A ``_reg`` name gets the base model's dict for the same seed plus ``register_tokens [1, R, D]`` drawn from a generator
+    of its own, so the base dicts stay what they were.
     """
+    if name in REGISTERS:
+        sd = synthetic_state_dict(base_model(name), seed, device, depth)
+        gen = torch.Generator(device=device)
+        gen.manual_seed(seed + 0x5EED)
+        sd["register_tokens"] = _randn(gen, (1, REGISTERS[name], ARCH[name][0]), 0.05, device)
+        return sd
     dim, full_depth, heads, ffn, hidden = ARCH[name]
     depth = full_depth if depth is None else depth
     gen = torch.Generator(device=device)
@@ -81,6 +93,15 @@ def synthetic_state_dict(name, seed=0, device="cpu", depth=None):
     sd["norm.weight"] = 1.0 + r((dim,), 0.1)
     sd["norm.bias"] = r((dim,), 0.05)
     return sd
+
+
+def base_model(name):
+    """The plain DINOv2 a name shares its blocks with (``dinov2_vitg14_reg`` -> ``dinov2_vitg14``)."""
+    return name[:-len("_reg")] if name in REGISTERS else name
+
+
+def n_registers(name):
+    return REGISTERS.get(name, 0)
 
 
 def synthetic_places(n_db, n_qu, h, w, seed=42, device="cpu"):

@@ -7,7 +7,8 @@ implementation needs only the *state dict* (hub key names).  Resolution order:
 1. a state dict registered in-process with :func:`register_state_dict`
    (tests / benchmarks inject seeded synthetic weights this way);
 2. ``$ANYLOC_DINOV2_WEIGHTS`` -- a ``.pth`` file, or a directory holding
-   ``<name>_pretrain.pth`` (the file names facebookresearch publishes);
+   ``<name>_pretrain.pth`` (the file names facebookresearch publishes;
+   ``<base>_reg4_pretrain.pth`` for a ``<base>_reg`` model with registers);
 3. the torch hub checkpoint cache (``torch.hub.get_dir()/checkpoints``), where
    a previous ``torch.hub.load`` of the real model would have left it;
 4. ``$ANYLOC_SYNTHETIC_WEIGHTS=<seed>`` -- seeded random weights (explicit opt-in);
@@ -17,10 +18,16 @@ import os
 
 import torch
 
-from .synth import ARCH, synthetic_state_dict
+from .synth import ARCH, base_model, n_registers, synthetic_state_dict
 
 _REGISTERED = {}
-_URL = "https://dl.fbaipublicfiles.com/dinov2/{short}/{short}_pretrain.pth"
+_URL = "https://dl.fbaipublicfiles.com/dinov2/{short}/{fname}"
+
+
+def checkpoint_name(name):
+    """The published checkpoint file of a hub model: ``dinov2_vits14_pretrain.pth``, ``dinov2_vits14_reg4_pretrain.pth``."""
+    r = n_registers(name)
+    return f"{base_model(name)}_reg{r}_pretrain.pth" if r else f"{name}_pretrain.pth"
 
 
 def register_state_dict(name, state_dict):
@@ -39,7 +46,7 @@ def resolve_state_dict(name):
         raise ValueError(f"unknown DINOv2 model {name!r}; expected one of {sorted(ARCH)}")
     if name in _REGISTERED:
         return _REGISTERED[name]
-    fname = f"{name}_pretrain.pth"
+    fname = checkpoint_name(name)
     cands = []
     env = os.environ.get("ANYLOC_DINOV2_WEIGHTS")
     if env:
@@ -53,7 +60,7 @@ def resolve_state_dict(name):
         print(f"[anyloc_amd] using SYNTHETIC {name} weights (seed {seed})")
         return synthetic_state_dict(name, int(seed))
     try:
-        return torch.hub.load_state_dict_from_url(_URL.format(short=name), map_location="cpu")
+        return torch.hub.load_state_dict_from_url(_URL.format(short=base_model(name), fname=fname), map_location="cpu")
     except Exception as exc:   # no network
         raise FileNotFoundError(
             f"no weights for {name}: set ANYLOC_DINOV2_WEIGHTS to a checkpoint / directory, place "

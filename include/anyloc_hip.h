@@ -481,6 +481,14 @@ int anyloc_vit_set_telemetry(anyloc_vit_t* h, float* ffn_looseness /*device [dep
 int anyloc_vit_block_ffn_exact(anyloc_vit_t* h, int32_t layer, int32_t exact);
 #define ANYLOC_VIT_SPLIT_FP16 16u    /* block GEMMs as three fp16 products, fp32-level accuracy */
 
+/* DINOv2 with registers (the hub's dinov2_vit*14_reg models).  With n_registers = R > 0 every later forward lays out
+ * each image's token rows as [CLS + pos[0], reg_0 .. reg_{R-1}, patch_p + pos[1+p]] (T = 1 + R + N; the registers get no
+ * positional term), and the taps drop the register rows: out holds the N patch rows, or CLS then the N patch rows with
+ * ANYLOC_VIT_USE_CLS -- never a register row.  register_tokens: device [R, D], caller-owned, read at forward time and alive
+ * while set.  R = 0 restores the plain layout; R outside [0, 16], or NULL with R > 0, is ANYLOC_ERR_INVALID_ARG.  The
+ * workspace queries size for T = 1 + R + N once registers are set. */
+int anyloc_vit_set_registers(anyloc_vit_t* h, const float* register_tokens /*device [R, D]*/, int32_t n_registers);
+
 #define ANYLOC_VIT_USE_CLS 1u        /* keep the CLS row (utilities.py:270-273) */
 #define ANYLOC_VIT_NORM_TAPS 2u      /* L2-normalise each tap (utilities.py:282-283) */
 #define ANYLOC_VIT_NORM_CONCAT 4u    /* L2-normalise the concatenated taps again
@@ -500,7 +508,8 @@ int anyloc_vit_forward(anyloc_vit_t* h, const float* img, int64_t batch,
 
 /* Ragged batches (ABI 10): images of DIFFERENT sizes in one forward, packed back to back.  Image i is
  * img_hw[2i] x img_hw[2i+1] pixels (each a positive multiple of 14, else ANYLOC_ERR_INVALID_ARG before any
- * device work), N_i = (H_i/14)(W_i/14) patches, T_i = N_i + 1 token rows (CLS first).  No image attends to
+ * device work), N_i = (H_i/14)(W_i/14) patches, T_i = 1 + R + N_i token rows (CLS first, then the R registers of
+ * anyloc_vit_set_registers; R = 0 without them).  No image attends to
  * another; flags, taps, anyloc_vit_block_ffn_exact and the telemetry mean what they mean for
  * anyloc_vit_forward (per_image = 1: ffn_looseness[depth][n_img]).  The call is stream-ordered and never
  * synchronises with the host: the sizes are read from the HOST array (grids, workspace, validation), the
@@ -512,8 +521,8 @@ int anyloc_vit_forward(anyloc_vit_t* h, const float* img, int64_t batch,
  *     [3][i] H_i,  [4][i] W_i                       ([1..4][n_img] unused)
  *   img   the CHW images, image i at img + dev_meta[1][i]
  *   pos   packed positional tables, [1 + N_i, D] for image i at row dev_meta[2][i]
- *   out   [sum rows_i, n_taps*D], rows_i = N_i (+1 with USE_CLS); image i's rows start at dev_meta[0][i] - i
- *         (dev_meta[0][i] with USE_CLS) -- offsets anyloc_vlad_hard / anyloc_vlad_soft take as they are */
+ *   out   [sum rows_i, n_taps*D], rows_i = N_i (+1 with USE_CLS); image i's rows start at dev_meta[0][i] - i(1+R)
+ *         (dev_meta[0][i] - iR with USE_CLS) -- offsets anyloc_vlad_hard / anyloc_vlad_soft take as they are */
 size_t anyloc_vit_workspace_bytes_ragged(const anyloc_vit_t* h, int32_t n_img,
                                          const int32_t* img_hw /*host [n_img][2]*/);
 int anyloc_vit_forward_ragged(anyloc_vit_t* h, const float* img, int32_t n_img,
