@@ -1,6 +1,6 @@
 """Benchmark of the AnyLoc-VLAD-DINOv2 hot path on MI355X (driver contract).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One *step* = one pass of the hot path over one batch of synthetic input, per rank:
     B query images (322x322, resident in HBM) -> DINOv2 ViT-G/14 layer-31 'value' tokens
@@ -9,14 +9,21 @@ One *step* = one pass of the hot path over one batch of synthetic input, per ran
      per-shard top-k gathered to rank 0 and merged on the host).
 Workload = BASELINE.json configs[1].  ``value`` = images/second of the whole job.
 
-The JSON line also carries
+A plain run does only what ``value`` needs: setup, W warm-up steps, the K timed steps, ``--dump-outputs`` and the JSON
+line (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``, the configuration, ``setup_s``).
+With ``--full`` the same timed steps are followed by everything else the benchmark measures and checks; the JSON line
+then also carries ``recall``, ``rccl`` and
   * roofline of the dominant kernel: per-launch ALGORITHMIC FLOPs / average launch duration measured with HIP
     events on the launch stream in the timed region, against the peak of the arithmetic the block GEMMs run in
     (--gemm h3, default: fp16 MFMA peak / 3 products; x6: bf16 MFMA peak / 6; f32: fp32 MFMA peak) and, always,
     against the fp32-MFMA peak (`vs_fp32_mfma_peak`);
   * cpu_baseline (rank 0, N=1): the CPU oracle (reference algorithm restated, torch CPU)
     timed on this box's host cores on a bounded sample of the same workload, doubling as
-    the parity check of the GPU run (``parity``).
+    the parity check of the GPU run (``parity``);
+  * (N=1) ``retrieval_check`` against a float64 flat search, ``modes`` (the other two GEMM arithmetics) and ``stages``
+    (the other BASELINE.json configurations and the HBM-bound kernels), each with its own ``--no-*`` switch.
+The dominant kernel's launches are bracketed by HIP events in the timed steps of both kinds of run, so that a plain
+and a full run time the same steps.
 """
 import argparse
 import json
@@ -473,6 +480,11 @@ def main():
     # 61 images = 32 330 token rows = 252.6 row-tiles of 128: the 253 x {12,36,64} GEMM tile grids are
     # within 1.2 % of whole multiples of the 512 resident thread blocks (2 per CU) -- no tail wave
     ap.add_argument("--batch", type=int, default=61, help="query images per step per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything else (recall, roofline and per-kernel "
+                         "table, power, RCCL legs, float64 retrieval check, CPU baseline + parity, other GEMM modes, stages; "
+                         "the --no-* switches below drop parts of it); off: the headline line alone.  --workload config3 "
+                         "prints its whole line either way")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--gemm", choices=["x6", "h3", "f32"], default=os.environ.get("ANYLOC_GEMM", DEFAULT_GEMM),
                     help="block GEMMs: x6 = exact 3-way bf16 split, six bf16 MFMA products, fp32 accumulate "
@@ -581,6 +593,32 @@ def main():
     prof_dom = ops.profile_dump()
     ops.profile_filter(None)
     elapsed = max_over_ranks(elapsed, dist, dev)
+    images = steps * B * world
+    value = images / elapsed
+    headline = {
+        "metric": "images/sec (DINOv2->VLAD->top-k), ViT-G/14 L31 value K=32", "value": round(value, 3),
+        "unit": "images/s", "n_gpus": world, "steps": steps, "warmup": warm,
+        "ms_per_step": round(elapsed / steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": {"x6": "f32 (GEMM operands as exact 3-way bf16 splits, 6 bf16 MFMA products, fp32 accumulate)",
+                  "h3": "f32 (GEMM and attention operands as power-of-two-scaled 2-term fp16 splits = 22 bits, "
+                        "3 fp16 MFMA products, fp32 accumulate; softmax, LayerNorm, residuals in fp32)",
+                  "f32": "f32"}[args.gemm], "data": "synthetic",
+        "config": {"workload": "BASELINE.json configs[1]: DINOv2 ViT-G/14 layer31 'value' K=32 VLAD, "
+                               "322x322, top-20 vs 10k-row database per GPU", "batch_per_gpu": B, "gemm": args.gemm,
+                   "images_per_step": B * world, "db_rows_per_gpu": N_DB, "vlad_dim": K_CLUSTERS * 1536,
+                   "weights": "random-init, hub layout (no checkpoint available offline)",
+                   "parallelism": f"dp{world}+db-shard{world}" if dist is not None else "single"},
+        "setup_s": round(t_setup, 1),
+    }
+    if args.dump_outputs and rank == 0:      # the last timed step: its query VLADs (N = 1) and the (merged) top-k lists
+        dump_outputs(args.dump_outputs, dict(zip(("topk_distances", "topk_indices", "query_vlads"), results[-1])))
+    if not args.full:                        # a plain run ends here: the headline line, nothing else measured or checked
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     rccl_legs, rccl_legs_all = {}, None
     if dist is not None:                     # one instrumented retrieval of a step's queries, every rank (collectives inside)
         q_probe = vlad.generate_multi(ext(qu_img[:B]))
@@ -589,9 +627,6 @@ def main():
         rccl_legs_all = [None] * world
         dist.all_gather_object(rccl_legs_all, rccl_legs)
     timed_results = list(results)            # (the untimed steps below and the `modes` block re-use and clear `results`)
-    if args.dump_outputs and rank == 0:      # the last timed step: its query VLADs (N = 1) and the (merged) top-k lists
-        last = timed_results[-1]
-        dump_outputs(args.dump_outputs, dict(zip(("topk_distances", "topk_indices", "query_vlads"), last)))
     # Socket power / shader clock: sampled over EXTRA, untimed steps identical to the timed ones, right after them -- the
     # sampler reads the GPU's own hwmon nodes (an SMU query each), so it never runs while `value` is being measured
     sampler, power_timed = None, None
@@ -628,8 +663,6 @@ def main():
         dist.destroy_process_group()
         return
 
-    images = steps * B * world
-    value = images / elapsed
     # Recall@1 of the timed queries (rank 0's share): query i depicts place i of its own rank
     if dist is None:
         idx_all = torch.cat([r[1] for r in timed_results]).cpu().numpy()
@@ -655,23 +688,8 @@ def main():
     # socket power / shader clock over the timed region (hwmon samples of a host thread): the evidence behind `power_limited`
     roofline["power"] = power_timed
 
-    out = {
-        "metric": "images/sec (DINOv2->VLAD->top-k), ViT-G/14 L31 value K=32", "value": round(value, 3),
-        "unit": "images/s", "n_gpus": world, "steps": steps, "warmup": warm,
-        "ms_per_step": round(elapsed / steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": {"x6": "f32 (GEMM operands as exact 3-way bf16 splits, 6 bf16 MFMA products, fp32 accumulate)",
-                  "h3": "f32 (GEMM and attention operands as power-of-two-scaled 2-term fp16 splits = 22 bits, "
-                        "3 fp16 MFMA products, fp32 accumulate; softmax, LayerNorm, residuals in fp32)",
-                  "f32": "f32"}[args.gemm], "data": "synthetic",
-        "config": {"workload": "BASELINE.json configs[1]: DINOv2 ViT-G/14 layer31 'value' K=32 VLAD, "
-                               "322x322, top-20 vs 10k-row database per GPU", "batch_per_gpu": B, "gemm": args.gemm,
-                   "images_per_step": B * world, "db_rows_per_gpu": N_DB, "vlad_dim": K_CLUSTERS * 1536,
-                   "weights": "random-init, hub layout (no checkpoint available offline)",
-                   "parallelism": f"dp{world}+db-shard{world}" if dist is not None else "single"},
-        "recall": rec, "setup_s": round(t_setup, 1), "roofline": roofline,
-        "rccl": rccl_record(dist, world, rccl_legs, elapsed / steps * 1e3, rccl_legs_all),
-    }
+    out = dict(headline, recall=rec, roofline=roofline,
+               rccl=rccl_record(dist, world, rccl_legs, elapsed / steps * 1e3, rccl_legs_all))
 
     # ---------------- CPU baseline + parity on a bounded sample (N=1 only) -----------------
     # ---------------- the other two GEMM arithmetics, timed briefly in the same run (N=1) -------

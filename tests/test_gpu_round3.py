@@ -37,7 +37,7 @@ def test_bench_gpus2_plain_invocation_spawns_its_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                          "--no-cpu-baseline", "--batch", "8"], env=env, capture_output=True, text=True, timeout=900)
+                          "--no-cpu-baseline", "--batch", "8", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]

@@ -323,7 +323,7 @@ def test_sharded_step_on_real_rccl_with_one_rank(workload):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"]
     if workload == "config2":
-        cmd += ["--batch", "8", "--no-cpu-baseline", "--no-modes", "--no-stages"]
+        cmd += ["--batch", "8", "--full", "--no-cpu-baseline", "--no-modes", "--no-stages"]
     else:
         cmd += ["--workload", "config3", "--queries", "300", "--shard-rows", "4096"]
     def run(e):
