@@ -10,7 +10,7 @@
 // last tap, and when a q/k/v tap sits in the last executed block only that
 // facet's third of the QKV projection is computed.
 //
-// Per block (all GEMMs on gemm_f32.hip, fp32 MFMA, fused epilogues):
+// Per block (every GEMM in the arithmetic of the call -- Arith below -- with a fused epilogue; shown for fp32):
 //   y   = LN1(x)                                    layernorm
 //   qkv = y Wqkv^T + b                              EPI_STORE
 //   a   = softmax((q/8) k^T) v                      attention.hip
@@ -90,88 +90,127 @@ VitWs carve(void* ws, size_t cap, const anyloc_vit_config& c, int64_t M, int64_t
   return w;
 }
 
-int linear(const float* A, int64_t lda, const float* Wt, int64_t K, const float* bias, float* C, int64_t ldc, int64_t M,
-           int64_t N, int epi, const float* gamma, const char* tag, hipStream_t stream) {
-  GemmProblem g{};
-  g.A = A; g.lda = lda;
-  g.W = Wt; g.ldw = K;
-  g.C = C; g.ldc = ldc;
-  g.M = M; g.N = N; g.K = K;
-  g.bias = bias;
-  g.gamma = gamma;
-  g.resid = C;
-  g.tag = tag;
-  return gemm_nt(g, epi, stream);
-}
+// which kernels the GEMMs of a forward run on: fp32 MFMA (gemm_f32.hip), six bf16 products of three-plane images (gemm_x6.hip),
+// three fp16 products of row-scaled two-plane images (gemm_h3.hip)
+enum class Arith { F32, X6, H3 };
 
-// options (common.hpp): x6_fuse / h3_fuse = 0 keep fp32 activations and quantise them in front of every GEMM (the round-1
-// data flows; A/B measurements and tests).  The two-term fp16 forward has no row threshold by default: with q | k | v, the
-// attention output and the FFN activation kept in fp16 planes it beats the fp32-MFMA kernels at every batch (B=1: 9.6 vs
-// 16.5 ms, profiles/r02_extractor_vs_batch.log); the split-bf16 forward switches at 1600 rows.
-
-// y = act(A W^T + b) on the six-product bf16 GEMM.  A is given as fp32 (split into planes here) or, when A == nullptr,
-// a3 already holds its plane image (written by the producer).  c3 != nullptr: the activation is written as the plane
-// image of the next GEMM instead of fp32 C.
-int linear_x6(const float* A, int64_t K, unsigned char* a3, const void* w3, int64_t w_rows, int64_t w_row0,
-              const float* bias, float* C, int64_t ldc, int64_t M, int64_t N, int epi, const float* gamma,
-              const char* tag, hipStream_t stream, unsigned char* c3 = nullptr) {
-  if (A) ANYLOC_TRY(split_x3(A, K, M, K, a3, stream));
-  X6Problem g{};
-  g.C3 = c3; g.RC = M;
-  g.A3 = a3; g.RA = M;
-  g.W3 = static_cast<const unsigned char*>(w3) + w_row0 * 32; g.RW = w_rows;
-  g.w_off = w_row0 * 32;
-  g.C = C; g.ldc = ldc;
-  g.M = M; g.N = N; g.K16 = (int)((K + 15) / 16);
-  g.bias = bias;
-  g.gamma = gamma;
-  g.resid = C;
-  g.tag = tag;
-  return gemm_x6(g, epi, stream);
-}
-
-// the same linear layer on the row-scaled two-term fp16 GEMM (gemm_h3.hip).  A == nullptr: a2 / ainv already hold the
-// quantised operand (written by layernorm_h2); otherwise A (fp32, row-major, width K) is quantised here first.
-// a LayerNorm whose output is the GEMM's own operand image (a2 / ainv; with `bound` also the FFN bound into c_inv)
-struct LnFront {
-  const float *x, *w, *b;
-  const float* bound;       // HOST [4] or null
-  unsigned* tickets;        // zeroed words of this launch, one per 128-row tile (VitWs::ln_tk)
+// an activation operand [M, K]: its fp32 rows and the place of its operand image (x6: three bf16 planes; h3: two fp16 planes
+// and 2^-e per row in inv).  quantised: the producer wrote the image (the fp32 rows do not exist); otherwise the GEMM's
+// arithmetic quantises the rows into it first
+struct Act {
+  const float* rows;
+  unsigned char* img;
+  float* inv;
+  int64_t M, K;
+  bool quantised;
 };
 
-int linear_h3(const float* A, int64_t K, unsigned char* a2, float* ainv, const void* w2, const float* winv, int64_t w_rows,
-              int64_t w_row0, const float* bias, float* C, int64_t ldc, int64_t M, int64_t N, int epi, const float* gamma,
-              const char* tag, hipStream_t stream, unsigned char* c2 = nullptr, const float* c_inv = nullptr,
-              unsigned char* qkv_planes = nullptr, float* qkv_inv = nullptr, int heads = 0, const VitWs* ws = nullptr,
-              int kind = H3_KIND_OTHER, unsigned* c_max = nullptr, const LnFront* ln = nullptr) {
-  if (A) ANYLOC_TRY(split_h2(A, K, M, K, a2, ainv, stream));
-  H3Problem g{};
-  if (ws) { g.sk_part = ws->sk_part; g.sk_tickets = ws->sk_tickets; }
-  g.kind = kind;
-  g.C2 = c2; g.RC = M; g.c_inv = c_inv; g.c_max = c_max;
-  g.qkv_planes = qkv_planes; g.qkv_inv = qkv_inv; g.heads = heads; g.groups = (M + 31) / 32;
-  g.A2 = a2; g.RA = M; g.a_inv = ainv;
-  g.W2 = static_cast<const unsigned char*>(w2) + w_row0 * 32; g.RW = w_rows; g.w_inv = winv + w_row0;
-  g.w_off = w_row0 * 32;
-  g.C = C; g.ldc = ldc;
-  g.M = M; g.N = N; g.K16 = (int)(K / 16);
-  g.bias = bias;
-  g.gamma = gamma;
-  g.resid = C;
-  g.tag = tag;
-  if (ln) {
-    // LayerNorm in front of this GEMM: as the lead role of the GEMM's own launch where the small-M plan has it (one image per
-    // call: LN1 + qkv, LN2 + w12), as a launch of its own otherwise -- the same arithmetic, the same bits
-    if (h3_ln_lead_feasible(g, epi)) {
-      g.ln_x = ln->x; g.ln_w = ln->w; g.ln_b = ln->b; g.ln_eps = 1e-6f; g.ln_dim = (int)K;
-      g.ln_has_bound = ln->bound != nullptr;
-      for (int i = 0; i < 4; ++i) g.ln_bound[i] = ln->bound ? ln->bound[i] : 0.0f;
-      g.ln_tickets = ln->tickets;
-    } else {
-      ANYLOC_TRY(layernorm_h2(ln->x, ln->w, ln->b, M, (int)K, 1e-6f, a2, ainv, stream, ln->bound, ln->bound ? const_cast<float*>(c_inv) : nullptr));
+// a weight matrix [rows, K] in the form each arithmetic reads (those the call does not use may be null)
+struct Weights {
+  const float* f32;
+  const void* x3;
+  const void* h2;
+  const float* h2_inv;
+  int64_t rows;
+};
+
+// One linear layer of the forward, C = epi(A W^T + bias): `describe` fills the problem of the call's arithmetic with what
+// every such GEMM has, the call site sets by name what only this GEMM has, `run` launches it.
+struct BlockGemm {
+  Arith arith;
+  Act a;
+  GemmProblem f32;
+  X6Problem x6;
+  H3Problem h3;
+  // h3, optional: the LayerNorm whose output IS the operand image (a.img / a.inv; with ln_bound, HOST [4], also the FFN bound
+  // into h3.c_inv).  ln_tickets: zeroed words of this launch, one per 128-row tile (VitWs::ln_tk)
+  const float *ln_x, *ln_w, *ln_b, *ln_bound;
+  unsigned* ln_tickets;
+};
+
+// N output columns from rows row0 .. row0 + N of wt.  kind (H3_KIND_*) other than OTHER also hands an h3 launch the split-K
+// buffers: the small-M plans belong to the fused data flow; the unfused one (A/B runs, layers with a q / k / v tap) keeps
+// the fixed tile shapes it was measured with
+BlockGemm describe(Arith arith, const char* tag, const Act& a, const Weights& wt, int64_t row0, int64_t N, const float* bias,
+                   float* C, int64_t ldc, int kind, const VitWs& ws) {
+  BlockGemm g{};
+  g.arith = arith;
+  g.a = a;
+  auto shared = [&](auto& p) {
+    p.C = C; p.ldc = ldc;
+    p.M = a.M; p.N = N;
+    p.bias = bias;
+    p.resid = C;
+    p.tag = tag;
+  };
+  switch (arith) {
+    case Arith::F32:
+      shared(g.f32);
+      g.f32.A = a.rows; g.f32.lda = a.K;
+      g.f32.W = wt.f32 + row0 * a.K; g.f32.ldw = a.K;
+      g.f32.K = a.K;
+      break;
+    case Arith::X6:
+      shared(g.x6);
+      g.x6.A3 = a.img; g.x6.RA = g.x6.RC = a.M;
+      g.x6.W3 = static_cast<const unsigned char*>(wt.x3) + row0 * 32; g.x6.RW = wt.rows; g.x6.w_off = row0 * 32;
+      g.x6.K16 = (int)((a.K + 15) / 16);
+      break;
+    case Arith::H3:
+      shared(g.h3);
+      g.h3.A2 = a.img; g.h3.RA = g.h3.RC = a.M; g.h3.a_inv = a.inv;
+      g.h3.W2 = static_cast<const unsigned char*>(wt.h2) + row0 * 32; g.h3.RW = wt.rows; g.h3.w_off = row0 * 32;
+      g.h3.w_inv = wt.h2_inv + row0;
+      g.h3.K16 = (int)(a.K / 16);
+      g.h3.groups = (a.M + 31) / 32;
+      g.h3.kind = kind;
+      if (kind != H3_KIND_OTHER) { g.h3.sk_part = ws.sk_part; g.h3.sk_tickets = ws.sk_tickets; }
+      break;
+  }
+  return g;
+}
+
+// gamma: the LayerScale of EPI_LS_RESID (x += gamma * (A W^T + bias), in place)
+int run(BlockGemm& g, int epi, hipStream_t stream, const float* gamma = nullptr) {
+  const Act& a = g.a;
+  switch (g.arith) {
+    case Arith::F32:
+      g.f32.gamma = gamma;
+      return gemm_nt(g.f32, epi, stream);
+    case Arith::X6:
+      if (!a.quantised) ANYLOC_TRY(split_x3(a.rows, a.K, a.M, a.K, a.img, stream));
+      g.x6.gamma = gamma;
+      return gemm_x6(g.x6, epi, stream);
+    case Arith::H3: {
+      H3Problem& p = g.h3;
+      if (!a.quantised) ANYLOC_TRY(split_h2(a.rows, a.K, a.M, a.K, a.img, a.inv, stream));
+      p.gamma = gamma;
+      if (g.ln_x && h3_ln_lead_feasible(p, epi)) {
+        // the LayerNorm as the lead role of the GEMM's own launch (one image per call: LN1 + qkv, LN2 + w12) ...
+        p.ln_x = g.ln_x; p.ln_w = g.ln_w; p.ln_b = g.ln_b; p.ln_eps = 1e-6f; p.ln_dim = (int)a.K;
+        p.ln_has_bound = g.ln_bound != nullptr;
+        for (int i = 0; i < 4; ++i) p.ln_bound[i] = g.ln_bound ? g.ln_bound[i] : 0.0f;
+        p.ln_tickets = g.ln_tickets;
+      } else if (g.ln_x) {
+        // ... or as a launch of its own in front of it: the same arithmetic, the same bits
+        ANYLOC_TRY(layernorm_h2(g.ln_x, g.ln_w, g.ln_b, a.M, (int)a.K, 1e-6f, a.img, a.inv, stream, g.ln_bound,
+                                g.ln_bound ? const_cast<float*>(p.c_inv) : nullptr));
+      }
+      return gemm_h3(p, epi, stream);
     }
   }
-  return gemm_h3(g, epi, stream);
+  return ANYLOC_ERR_INVALID_ARG;
+}
+
+// the tap list of a forward; `who` is the entry point's name in the messages
+int check_taps(const char* who, const anyloc_vit_config& c, int32_t n_taps, const int32_t* tap_layers, const int32_t* tap_facets) {
+  ANYLOC_CHECK_ARG(n_taps >= 1 && n_taps <= 64, "%s: n_taps %d", who, n_taps);
+  for (int t = 0; t < n_taps; ++t) {
+    ANYLOC_CHECK_ARG(tap_layers[t] >= 0 && tap_layers[t] < c.depth, "%s: tap layer %d outside [0,%d)", who, tap_layers[t], c.depth);
+    ANYLOC_CHECK_ARG(tap_facets[t] >= 0 && tap_facets[t] <= 3, "%s: facet %d", who, tap_facets[t]);
+    ANYLOC_CHECK_ARG(t == 0 || tap_layers[t] >= tap_layers[t - 1], "%s: tap layers must ascend", who);
+  }
+  return ANYLOC_OK;
 }
 
 }  // namespace
@@ -375,27 +414,31 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
                                 unsigned flags, float* out, void* workspace, size_t workspace_bytes, hipStream_t stream,
                                 const RaggedBatch* rg = nullptr) {
   const anyloc_vit_config& c = h->cfg;
-  const int D = c.dim, gh = rg ? 0 : (int)(img_h / c.patch), gw = rg ? 0 : (int)(img_w / c.patch), np = gh * gw;
+  const int D = c.dim, Hh = c.ffn_hidden, np = rg ? 0 : (int)(img_h / c.patch) * (int)(img_w / c.patch);
   const int R = h->n_reg;                       // register rows per image (after CLS, before the patches)
   const int T = rg ? rg->max_T : np + 1 + R;
   const int64_t M = rg ? rg->rows : batch * T, P = rg ? rg->rows - batch * (1 + R) : batch * np;
   const int64_t* meta = rg ? rg->meta : nullptr;
-  VitWs w = carve(workspace, workspace_bytes, c, M, P);
+  const VitWs w = carve(workspace, workspace_bytes, c, M, P);
   if (!workspace || w.bytes > workspace_bytes) {
     set_error("vit_forward: workspace %zu < %zu", workspace_bytes, w.bytes);
     return ANYLOC_ERR_WORKSPACE;
   }
   ANYLOC_CHECK_ARG(!(flags & ANYLOC_VIT_SPLIT_BF16) || !h->x3.empty(),
                    "vit_forward: ANYLOC_VIT_SPLIT_BF16 without anyloc_vit_attach_x3");
-  // below ~3 images of 530 tokens the GEMMs have too few 128-row tiles to fill 256 CUs twice over: the fp32-MFMA
-  // kernel with its 64-row split is faster there (measured B=1: 60 vs 40 images/s), so the split-bf16 request is
-  // honoured from option x6_min_rows rows up
   ANYLOC_CHECK_ARG(!(flags & ANYLOC_VIT_SPLIT_FP16) || !h->h2.empty(),
                    "vit_forward: ANYLOC_VIT_SPLIT_FP16 without anyloc_vit_attach_h2");
-  const bool h3m = (flags & ANYLOC_VIT_SPLIT_FP16) && M >= option(OPT_H3_MIN_ROWS);
-  const bool x6 = !h3m && (flags & ANYLOC_VIT_SPLIT_BF16) && M >= option(OPT_X6_MIN_ROWS);
-  const bool fuse_x6 = x6 && option(OPT_X6_FUSE) != 0;
-  const bool h3f = h3m && option(OPT_H3_FUSE) != 0;
+  // The arithmetic of the call.  h3 has no row threshold by default: with q | k | v, the attention output and the FFN
+  // activation kept in fp16 planes it beats the fp32-MFMA kernels at every batch (B=1: 9.6 vs 16.5 ms,
+  // profiles/r02_extractor_vs_batch.log).  x6 is honoured from option x6_min_rows (1600) rows up: below ~3 images of 530
+  // tokens its GEMMs have too few 128-row tiles to fill 256 CUs twice over and the fp32-MFMA kernel with its 64-row split is
+  // faster (measured B=1: 60 vs 40 images/s)
+  const Arith arith = (flags & ANYLOC_VIT_SPLIT_FP16) && M >= option(OPT_H3_MIN_ROWS)   ? Arith::H3
+                      : (flags & ANYLOC_VIT_SPLIT_BF16) && M >= option(OPT_X6_MIN_ROWS) ? Arith::X6
+                                                                                        : Arith::F32;
+  const bool h3 = arith == Arith::H3, x6 = arith == Arith::X6;
+  // options x6_fuse / h3_fuse = 0 (A/B measurements and tests): activations stay fp32 and are quantised in front of every GEMM
+  const bool fuse_x6 = x6 && option(OPT_X6_FUSE) != 0, fuse_h3 = h3 && option(OPT_H3_FUSE) != 0;
   const bool use_cls = flags & ANYLOC_VIT_USE_CLS;
   // the tap drops the register rows: without the CLS row a skip of 1 + R, with it a gap of R behind row 0
   const int rows_per_img = use_cls ? np + 1 : np, skip = use_cls ? 0 : 1 + R, gap = use_cls ? R : 0;
@@ -407,188 +450,130 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
     if (rg) return facet_rows_ragged(src, lds_, coff, out, ldo, ooff, meta, (int)batch, out_rows, skip, gap, D, norm_taps, 1e-12f, stream);
     return facet_rows(src, lds_, coff, out, ldo, ooff, batch, T, skip, gap, rows_per_img, D, norm_taps, 1e-12f, stream);
   };
+  // is the block output (token) / a q, k or v facet (!token) of layer l tapped?
+  auto tapped = [&](int l, bool token) {
+    for (int t = 0; t < n_taps; ++t)
+      if (tap_layers[t] == l && (tap_facets[t] == ANYLOC_FACET_TOKEN) == token) return true;
+    return false;
+  };
   const int last_layer = tap_layers[n_taps - 1];
   // split-K arrival counters; with telemetry on also the rows' maxima of every block that will run (adjacent: one memset)
-  const bool telem = h3m && h->ffn_looseness != nullptr;
-  if (h3m)
+  const bool telem = h3 && h->ffn_looseness != nullptr;
+  if (h3)
     ANYLOC_HIP(hipMemsetAsync(w.sk_tickets, 0,
                               telem ? (size_t)(reinterpret_cast<char*>(w.hmax + (size_t)(last_layer + 1) * M) - reinterpret_cast<char*>(w.sk_tickets))
                                     : (size_t)(reinterpret_cast<char*>(w.hmax) - reinterpret_cast<char*>(w.sk_tickets)),
                               stream));
-  // does any tap need the block OUTPUT of the last executed layer?
-  bool last_needs_full = false;
-  for (int t = 0; t < n_taps; ++t)
-    if (tap_layers[t] == last_layer && tap_facets[t] == ANYLOC_FACET_TOKEN) last_needs_full = true;
 
   // ---- patch embedding: conv 14x14 stride 14 == GEMM over gathered patches, + bias + pos ----
+  // h3: the gathered patches are quantised like every other operand (row maximum -> power-of-two scale), the contraction
+  // padded to whole 16-element k-blocks
+  const bool patch_h3 = h3 && h->patch_w2 && option(OPT_H3_PATCH) != 0;
+  const int kp = patch_h3 ? (c.patch_k_pad + 15) / 16 * 16 : c.patch_k_pad;
   float* col = w.qkv;
-  const bool patch_h3 = h3m && h->patch_w2 && option(OPT_H3_PATCH) != 0;
-  const int kp = patch_h3 ? (c.patch_k_pad + 15) / 16 * 16 : c.patch_k_pad;    // fp16 mode: whole 16-element k-blocks
   if (rg) ANYLOC_TRY(im2col_ragged(img, col, meta, (int)batch, R, P, c.patch, kp, stream));
   else ANYLOC_TRY(im2col(img, col, batch, (int)img_h, (int)img_w, c.patch, kp, stream));
   // ragged or with registers: the patch GEMM with its bias epilogue into w.y [P, D]; embed_rows then adds each image's
   // positional rows and writes the CLS and register rows (the same two sums as EPI_PATCH + cls_rows)
   const bool embed_pass = rg || R > 0;
-  float* patch_out = embed_pass ? w.y : w.x;
-  const int patch_epi = embed_pass ? EPI_STORE : EPI_PATCH;
-  if (patch_h3) {
-    // fp16 mode: the gathered patches are quantised like every other operand (row maximum -> power-of-two scale)
-    ANYLOC_TRY(split_h2(col, kp, P, kp, w.a3, w.ainv, stream));
-    H3Problem g{};
-    g.A2 = w.a3; g.RA = P; g.a_inv = w.ainv;
-    g.W2 = h->patch_w2; g.RW = D; g.w_inv = h->patch_inv;
-    g.C = patch_out; g.ldc = D;
-    g.M = P; g.N = D; g.K16 = kp / 16;
-    g.bias = h->patch_b;
-    g.pos = embed_pass ? nullptr : pos;
-    g.patches = np;
-    g.tag = "vit_patch_embed_gemm";
-    ANYLOC_TRY(gemm_h3(g, patch_epi, stream));
-  } else {
-    GemmProblem g{};
-    g.A = col; g.lda = c.patch_k_pad;
-    g.W = h->patch_w; g.ldw = c.patch_k_pad;
-    g.C = patch_out; g.ldc = D;
-    g.M = P; g.N = D; g.K = c.patch_k_pad;
-    g.bias = h->patch_b;
-    g.pos = embed_pass ? nullptr : pos;
-    g.patches = np;
-    g.tag = "vit_patch_embed_gemm";
-    ANYLOC_TRY(gemm_nt(g, patch_epi, stream));
-  }
+  const Act patches{col, w.a3, w.ainv, P, kp, false};
+  const Weights Wpatch{h->patch_w, nullptr, h->patch_w2, h->patch_inv, D};
+  BlockGemm pe = describe(patch_h3 ? Arith::H3 : Arith::F32, "vit_patch_embed_gemm", patches, Wpatch, 0, D, h->patch_b,
+                          embed_pass ? w.y : w.x, D, H3_KIND_OTHER, w);
+  pe.f32.pos = pe.h3.pos = embed_pass ? nullptr : pos;
+  pe.f32.patches = pe.h3.patches = np;
+  ANYLOC_TRY(run(pe, embed_pass ? EPI_STORE : EPI_PATCH, stream));
   if (embed_pass) ANYLOC_TRY(embed_rows(w.x, w.y, h->cls, h->regs, R, pos, meta, (int)batch, T, M, D, stream));
   else ANYLOC_TRY(cls_rows(w.x, h->cls, pos, batch, T, D, stream));
 
+  // y = LN(x): as the operand image of the GEMM that follows (h3 always, x6 when fused) or as fp32 rows in w.y
+  const bool ln_quantises = h3 || fuse_x6;
+  auto layer_norm = [&](const float* nw, const float* nb) {
+    if (h3) return layernorm_h2(w.x, nw, nb, M, D, 1e-6f, w.a3, w.ainv, stream);
+    if (fuse_x6) return layernorm_x3(w.x, nw, nb, M, D, 1e-6f, w.a3, stream);
+    return layernorm(w.x, w.y, nw, nb, M, D, 1e-6f, stream);
+  };
+  const Act y{w.y, w.a3, w.ainv, M, D, ln_quantises};
+  static const anyloc_vit_block_x3 no_x3{};
+  static const anyloc_vit_block_h2 no_h2{};
   for (int l = 0; l <= last_layer; ++l) {
     const anyloc_vit_block_weights& b = h->blocks[l];
-    const bool last = (l == last_layer);
-    // split-bf16 mode, fused producers: LayerNorm / attention / FFN activation write plane images directly
-    const bool fuse = fuse_x6;
-    bool qkv_tap0 = false;                      // (decided here already: a q / k / v tap keeps the unfused attention data flow)
-    for (int t = 0; t < n_taps; ++t)
-      if (tap_layers[t] == l && tap_facets[t] != ANYLOC_FACET_TOKEN) qkv_tap0 = true;
-    // fp16 mode, fused attention: LayerNorm 1 travels with the QKV GEMM (linear_h3's `ln`: lead role of that launch for one image
-    // per call, a launch of its own otherwise)
-    const bool ln1_with_qkv = h3f && !qkv_tap0 && D % 128 == 0 && !(last && !last_needs_full);
-    const LnFront ln1{w.x, b.norm1_w, b.norm1_b, nullptr, w.ln_tickets + (size_t)l * 2 * w.ln_tk};
-    if (h3m && !ln1_with_qkv) ANYLOC_TRY(layernorm_h2(w.x, b.norm1_w, b.norm1_b, M, D, 1e-6f, w.a3, w.ainv, stream));
-    else if (h3m) {}
-    else if (fuse) ANYLOC_TRY(layernorm_x3(w.x, b.norm1_w, b.norm1_b, M, D, 1e-6f, w.a3, stream));
-    else ANYLOC_TRY(layernorm(w.x, w.y, b.norm1_w, b.norm1_b, M, D, 1e-6f, stream));
-    const float* y_in = fuse ? nullptr : w.y;     // nullptr: the plane image is already in w.a3
-    if (last && !last_needs_full) {
-      // only q/k/v taps remain: compute just the tapped thirds of the QKV projection
+    const anyloc_vit_block_x3& b3 = x6 ? h->x3[l] : no_x3;
+    const anyloc_vit_block_h2& b2 = h3 ? h->h2[l] : no_h2;
+    const bool swiglu = c.ffn_kind == 1;
+    const Weights Wqkv{b.qkv_w, b3.qkv_w3, b2.qkv_w2, b2.qkv_inv, 3 * D}, Wproj{b.proj_w, b3.proj_w3, b2.proj_w2, b2.proj_inv, D},
+        Wfc1{b.fc1_w, b3.fc1_w3, b2.fc1_w2, b2.fc1_inv, swiglu ? 2 * Hh : Hh}, Wfc2{b.fc2_w, b3.fc2_w3, b2.fc2_w2, b2.fc2_inv, D};
+    // ---- the block's decisions ----
+    // only q / k / v taps remain: just the tapped thirds of the QKV projection are computed, and the forward ends
+    const bool facet_exit = l == last_layer && !tapped(l, true);
+    // attention fused: its output leaves as the operand image of the projection GEMM.  h3: q | k | v arrive as per-head
+    // fp16 tiles too and never exist in fp32, so a q / k / v tap of the layer keeps the unfused data flow
+    const bool fuse_attn = h3 ? fuse_h3 && !tapped(l, false) && D % 128 == 0 && !facet_exit : fuse_x6;
+    // FFN fused: fc1 / w12 writes the hidden activation as fc2's operand image.  h3: quantised against the row bound that
+    // LayerNorm 2 derives from the block's Cauchy-Schwarz constants, unless the block was switched to the exact row maximum
+    const float* fb = b2.fc1_bound;
+    const bool fuse_ffn = h3 ? fuse_h3 && (fb[0] > 0.f || fb[1] > 0.f) && !(l < (int)h->ffn_exact.size() && h->ffn_exact[l]) : fuse_x6;
+    // h3, fused: LayerNorm 1 / 2 travels with the qkv / fc1 GEMM (BlockGemm::ln_x) instead of running here
+    const bool h3_attn = h3 && fuse_attn, h3_ffn = h3 && fuse_ffn;
+
+    // ---- y = LN1(x) ----
+    if (!h3_attn) ANYLOC_TRY(layer_norm(b.norm1_w, b.norm1_b));
+    if (facet_exit) {
       for (int t = 0; t < n_taps; ++t) {
         if (tap_layers[t] != l) continue;
-        const int f = tap_facets[t];
-        if (h3m)
-          ANYLOC_TRY(linear_h3(nullptr, D, w.a3, w.ainv, h->h2[l].qkv_w2, h->h2[l].qkv_inv, 3 * D, (int64_t)f * D,
-                               b.qkv_b + (int64_t)f * D, w.qkv, D, M, D, EPI_STORE, nullptr, "vit_facet_gemm", stream, nullptr,
-                               nullptr, nullptr, nullptr, 0, &w, H3_KIND_PROJ));
-        else if (x6)
-          ANYLOC_TRY(linear_x6(y_in, D, w.a3, h->x3[l].qkv_w3, 3 * D, (int64_t)f * D, b.qkv_b + (int64_t)f * D, w.qkv, D,
-                               M, D, EPI_STORE, nullptr, "vit_facet_gemm", stream));
-        else
-          ANYLOC_TRY(linear(w.y, D, b.qkv_w + (int64_t)f * D * D, D, b.qkv_b + (int64_t)f * D, w.qkv, D, M, D,
-                            EPI_STORE, nullptr, "vit_facet_gemm", stream));
+        const int64_t row0 = (int64_t)tap_facets[t] * D;
+        BlockGemm g = describe(arith, "vit_facet_gemm", y, Wqkv, row0, D, b.qkv_b + row0, w.qkv, D, H3_KIND_PROJ, w);
+        ANYLOC_TRY(run(g, EPI_STORE, stream));
         ANYLOC_TRY(facet(w.qkv, D, 0, t * D));
       }
       break;
     }
-    bool qkv_tap = false;                       // a q / k / v tap of this layer needs the fp32 projection
-    for (int t = 0; t < n_taps; ++t)
-      if (tap_layers[t] == l && tap_facets[t] != ANYLOC_FACET_TOKEN) qkv_tap = true;
-    const bool fuse_attn = h3f && !qkv_tap && D % 128 == 0;
-    if (fuse_attn) {
-      // fp16 mode, fused: the QKV GEMM writes per-head two-plane fp16 tiles, attention_h3 consumes them by DMA and writes
-      // the image of the projection GEMM -- q, k, v and the attention output never exist in fp32
-      ANYLOC_TRY(linear_h3(nullptr, D, w.a3, w.ainv, h->h2[l].qkv_w2, h->h2[l].qkv_inv, 3 * D, 0, b.qkv_b, nullptr, 3 * D, M,
-                           3 * D, EPI_QKV_PLANES, nullptr, "vit_qkv_gemm", stream, nullptr, nullptr,
-                           reinterpret_cast<unsigned char*>(w.qkv), w.qinv, c.heads, &w, H3_KIND_QKV, nullptr, &ln1));
-      if (rg)
-        ANYLOC_TRY(attention_h3_ragged(reinterpret_cast<const unsigned char*>(w.qkv), w.qinv, (int)batch, T, meta, M, D, c.heads,
-                                       w.a3, w.ainv, stream));
-      else
-        ANYLOC_TRY(attention_h3(reinterpret_cast<const unsigned char*>(w.qkv), w.qinv, batch, T, D, c.heads, w.a3, w.ainv, stream));
-      ANYLOC_TRY(linear_h3(nullptr, D, w.a3, w.ainv, h->h2[l].proj_w2, h->h2[l].proj_inv, D, 0, b.proj_b, w.x, D, M, D,
-                           EPI_LS_RESID, b.ls1, "vit_proj_gemm", stream, nullptr, nullptr, nullptr, nullptr, 0, &w, H3_KIND_PROJ));
-    } else {
-      if (h3m)
-        ANYLOC_TRY(linear_h3(nullptr, D, w.a3, w.ainv, h->h2[l].qkv_w2, h->h2[l].qkv_inv, 3 * D, 0, b.qkv_b, w.qkv, 3 * D, M,
-                             3 * D, EPI_STORE, nullptr, "vit_qkv_gemm", stream));
-      else if (x6)
-        ANYLOC_TRY(linear_x6(y_in, D, w.a3, h->x3[l].qkv_w3, 3 * D, 0, b.qkv_b, w.qkv, 3 * D, M, 3 * D, EPI_STORE, nullptr,
-                             "vit_qkv_gemm", stream));
-      else
-        ANYLOC_TRY(linear(w.y, D, b.qkv_w, D, b.qkv_b, w.qkv, 3 * D, M, 3 * D, EPI_STORE, nullptr, "vit_qkv_gemm", stream));
-      for (int t = 0; t < n_taps; ++t)
-        if (tap_layers[t] == l && tap_facets[t] != ANYLOC_FACET_TOKEN)
-          ANYLOC_TRY(facet(w.qkv, 3 * D, tap_facets[t] * D, t * D));
-      if (rg) ANYLOC_TRY(attention_ragged(w.qkv, w.y, (int)batch, T, meta, M, D, c.heads, stream, fuse ? w.a3 : nullptr, x6 || h3m));
-      else ANYLOC_TRY(attention(w.qkv, w.y, batch, T, D, c.heads, stream, fuse ? w.a3 : nullptr, x6 || h3m));
-      if (h3m)     // the attention output is fp32: its rows span all heads, the row maximum is only known now
-        ANYLOC_TRY(linear_h3(w.y, D, w.a3, w.ainv, h->h2[l].proj_w2, h->h2[l].proj_inv, D, 0, b.proj_b, w.x, D, M, D,
-                             EPI_LS_RESID, b.ls1, "vit_proj_gemm", stream));
-      else if (x6)
-        ANYLOC_TRY(linear_x6(y_in, D, w.a3, h->x3[l].proj_w3, D, 0, b.proj_b, w.x, D, M, D, EPI_LS_RESID, b.ls1,
-                             "vit_proj_gemm", stream));
-      else
-        ANYLOC_TRY(linear(w.y, D, b.proj_w, D, b.proj_b, w.x, D, M, D, EPI_LS_RESID, b.ls1, "vit_proj_gemm", stream));
+    // ---- qkv = y Wqkv^T + b: fp32 [M, 3D], or (h3, fused) the per-head tiles attention_h3 reads by DMA ----
+    BlockGemm qkv = describe(arith, "vit_qkv_gemm", y, Wqkv, 0, 3 * D, b.qkv_b, h3_attn ? nullptr : w.qkv, 3 * D,
+                             h3_attn ? H3_KIND_QKV : H3_KIND_OTHER, w);
+    if (h3_attn) {
+      qkv.h3.qkv_planes = reinterpret_cast<unsigned char*>(w.qkv); qkv.h3.qkv_inv = w.qinv; qkv.h3.heads = c.heads;
+      qkv.ln_x = w.x; qkv.ln_w = b.norm1_w; qkv.ln_b = b.norm1_b;
+      qkv.ln_tickets = w.ln_tickets + (size_t)l * 2 * w.ln_tk;
     }
-    const float* fb = h3f ? h->h2[l].fc1_bound : nullptr;
-    const bool fuse_ffn = fb && (fb[0] > 0.f || fb[1] > 0.f) && !(l < (int)h->ffn_exact.size() && h->ffn_exact[l]);
-    // (fused FFN: LayerNorm 2 travels with the fc1 / w12 GEMM the same way)
-    const bool ln2_with_fc1 = h3m && fuse_ffn;
-    const LnFront ln2{w.x, b.norm2_w, b.norm2_b, fb, w.ln_tickets + ((size_t)l * 2 + 1) * w.ln_tk};
-    if (h3m && !ln2_with_fc1) ANYLOC_TRY(layernorm_h2(w.x, b.norm2_w, b.norm2_b, M, D, 1e-6f, w.a3, w.ainv, stream, nullptr, w.hinv));
-    else if (h3m) {}
-    else if (fuse) ANYLOC_TRY(layernorm_x3(w.x, b.norm2_w, b.norm2_b, M, D, 1e-6f, w.a3, stream));
-    else ANYLOC_TRY(layernorm(w.x, w.y, b.norm2_w, b.norm2_b, M, D, 1e-6f, stream));
-    const int Hh = c.ffn_hidden;
-    if (h3m && fuse_ffn) {
-      // the hidden activation is quantised in the epilogue against the row bound LayerNorm 2 left in w.hinv
-      if (c.ffn_kind == 0)
-        ANYLOC_TRY(linear_h3(nullptr, D, w.a3, w.ainv, h->h2[l].fc1_w2, h->h2[l].fc1_inv, Hh, 0, b.fc1_b, nullptr, Hh, M, Hh,
-                             EPI_GELU_H2, nullptr, "vit_fc1_gemm", stream, w.h3, w.hinv, nullptr, nullptr, 0, &w, H3_KIND_FC1,
-                             telem ? w.hmax + (size_t)l * M : nullptr, &ln2));
-      else
-        ANYLOC_TRY(linear_h3(nullptr, D, w.a3, w.ainv, h->h2[l].fc1_w2, h->h2[l].fc1_inv, 2 * Hh, 0,
-                             h->h2[l].fc1_b2 ? h->h2[l].fc1_b2 : b.fc1_b, nullptr, Hh, M, 2 * Hh,
-                             h->h2[l].fc1_layout == 1 ? EPI_SWIGLU_T_H2 : EPI_SWIGLU_H2, nullptr, "vit_w12_gemm", stream, w.h3,
-                             w.hinv, nullptr, nullptr, 0, &w, H3_KIND_FC1, telem ? w.hmax + (size_t)l * M : nullptr, &ln2));
-      ANYLOC_TRY(linear_h3(nullptr, Hh, w.h3, w.hinv, h->h2[l].fc2_w2, h->h2[l].fc2_inv, D, 0, b.fc2_b, w.x, D, M, D,
-                           EPI_LS_RESID, b.ls2, "vit_fc2_gemm", stream, nullptr, nullptr, nullptr, nullptr, 0, &w, H3_KIND_FC2));
-    } else if (h3m) {
-      if (c.ffn_kind == 0)
-        ANYLOC_TRY(linear_h3(nullptr, D, w.a3, w.ainv, h->h2[l].fc1_w2, h->h2[l].fc1_inv, Hh, 0, b.fc1_b, w.h, Hh, M, Hh,
-                             EPI_GELU, nullptr, "vit_fc1_gemm", stream));
-      else
-        ANYLOC_TRY(linear_h3(nullptr, D, w.a3, w.ainv, h->h2[l].fc1_w2, h->h2[l].fc1_inv, 2 * Hh, 0,
-                             h->h2[l].fc1_b2 ? h->h2[l].fc1_b2 : b.fc1_b, w.h, Hh, M, 2 * Hh,
-                             h->h2[l].fc1_layout == 1 ? EPI_SWIGLU_T : EPI_SWIGLU, nullptr, "vit_w12_gemm", stream));
-      ANYLOC_TRY(linear_h3(w.h, Hh, w.h3, w.hinv, h->h2[l].fc2_w2, h->h2[l].fc2_inv, D, 0, b.fc2_b, w.x, D, M, D,
-                           EPI_LS_RESID, b.ls2, "vit_fc2_gemm", stream));
-    } else if (x6) {
-      unsigned char* c3 = fuse ? w.h3 : nullptr;
-      if (c.ffn_kind == 0)
-        ANYLOC_TRY(linear_x6(y_in, D, w.a3, h->x3[l].fc1_w3, Hh, 0, b.fc1_b, w.h, Hh, M, Hh, EPI_GELU, nullptr,
-                             "vit_fc1_gemm", stream, c3));
-      else
-        ANYLOC_TRY(linear_x6(y_in, D, w.a3, h->x3[l].fc1_w3, 2 * Hh, 0, b.fc1_b, w.h, Hh, M, 2 * Hh, EPI_SWIGLU, nullptr,
-                             "vit_w12_gemm", stream, c3));
-      ANYLOC_TRY(linear_x6(fuse ? nullptr : w.h, Hh, w.h3, h->x3[l].fc2_w3, D, 0, b.fc2_b, w.x, D, M, D, EPI_LS_RESID,
-                           b.ls2, "vit_fc2_gemm", stream));
-    } else {
-      if (c.ffn_kind == 0) {
-        ANYLOC_TRY(linear(w.y, D, b.fc1_w, D, b.fc1_b, w.h, Hh, M, Hh, EPI_GELU, nullptr, "vit_fc1_gemm", stream));
-      } else {
-        ANYLOC_TRY(linear(w.y, D, b.fc1_w, D, b.fc1_b, w.h, Hh, M, 2 * Hh, EPI_SWIGLU, nullptr, "vit_w12_gemm", stream));
-      }
-      ANYLOC_TRY(linear(w.h, Hh, b.fc2_w, Hh, b.fc2_b, w.x, D, M, D, EPI_LS_RESID, b.ls2, "vit_fc2_gemm", stream));
-    }
+    ANYLOC_TRY(run(qkv, h3_attn ? EPI_QKV_PLANES : EPI_STORE, stream));
     for (int t = 0; t < n_taps; ++t)
-      if (tap_layers[t] == l && tap_facets[t] == ANYLOC_FACET_TOKEN)
-        ANYLOC_TRY(facet(w.x, D, 0, t * D));
+      if (tap_layers[t] == l && tap_facets[t] != ANYLOC_FACET_TOKEN) ANYLOC_TRY(facet(w.qkv, 3 * D, tap_facets[t] * D, t * D));
+    // ---- a = softmax((q/8) k^T) v ----
+    const unsigned char* tiles = reinterpret_cast<const unsigned char*>(w.qkv);
+    unsigned char* a_img = fuse_attn ? w.a3 : nullptr;     // x6: the output as the plane image instead of fp32 rows in w.y
+    if (h3_attn && rg) ANYLOC_TRY(attention_h3_ragged(tiles, w.qinv, (int)batch, T, meta, M, D, c.heads, w.a3, w.ainv, stream));
+    else if (h3_attn) ANYLOC_TRY(attention_h3(tiles, w.qinv, batch, T, D, c.heads, w.a3, w.ainv, stream));
+    else if (rg) ANYLOC_TRY(attention_ragged(w.qkv, w.y, (int)batch, T, meta, M, D, c.heads, stream, a_img, x6 || h3));
+    else ANYLOC_TRY(attention(w.qkv, w.y, batch, T, D, c.heads, stream, a_img, x6 || h3));
+    // ---- x += ls1 * (a Wproj^T + b)  (h3, unfused: a is fp32 -- its rows span all heads, the row maximum is only known now) ----
+    const Act attn{w.y, w.a3, w.ainv, M, D, fuse_attn};
+    BlockGemm proj = describe(arith, "vit_proj_gemm", attn, Wproj, 0, D, b.proj_b, w.x, D, h3_attn ? H3_KIND_PROJ : H3_KIND_OTHER, w);
+    ANYLOC_TRY(run(proj, EPI_LS_RESID, stream, b.ls1));
+    // ---- y = LN2(x) ----
+    if (!h3_ffn) ANYLOC_TRY(layer_norm(b.norm2_w, b.norm2_b));
+    // ---- h = gelu(y W1^T + b)  |  silu(y Wg^T + b) * (y Wv^T + b): fp32 [M, H], or the image of it ----
+    BlockGemm fc1 = describe(arith, swiglu ? "vit_w12_gemm" : "vit_fc1_gemm", y, Wfc1, 0, Wfc1.rows,
+                             swiglu && b2.fc1_b2 ? b2.fc1_b2 : b.fc1_b, h3_ffn ? nullptr : w.h, Hh,
+                             h3_ffn ? H3_KIND_FC1 : H3_KIND_OTHER, w);
+    if (h3_ffn) {
+      // quantised in the epilogue against the row bound LayerNorm 2 leaves in w.hinv
+      fc1.h3.C2 = w.h3; fc1.h3.c_inv = w.hinv;
+      fc1.h3.c_max = telem ? w.hmax + (size_t)l * M : nullptr;
+      fc1.ln_x = w.x; fc1.ln_w = b.norm2_w; fc1.ln_b = b.norm2_b; fc1.ln_bound = fb;
+      fc1.ln_tickets = w.ln_tickets + ((size_t)l * 2 + 1) * w.ln_tk;
+    }
+    if (x6 && fuse_ffn) fc1.x6.C3 = w.h3;
+    ANYLOC_TRY(run(fc1, !swiglu              ? (h3_ffn ? EPI_GELU_H2 : EPI_GELU)
+                        : b2.fc1_layout == 1 ? (h3_ffn ? EPI_SWIGLU_T_H2 : EPI_SWIGLU_T)
+                                             : (h3_ffn ? EPI_SWIGLU_H2 : EPI_SWIGLU),
+                   stream));
+    // ---- x += ls2 * (h W2^T + b) ----
+    const Act hid{w.h, w.h3, w.hinv, M, Hh, fuse_ffn};
+    BlockGemm fc2 = describe(arith, "vit_fc2_gemm", hid, Wfc2, 0, D, b.fc2_b, w.x, D, h3_ffn ? H3_KIND_FC2 : H3_KIND_OTHER, w);
+    ANYLOC_TRY(run(fc2, EPI_LS_RESID, stream, b.ls2));
+    for (int t = 0; t < n_taps; ++t)
+      if (tap_layers[t] == l && tap_facets[t] == ANYLOC_FACET_TOKEN) ANYLOC_TRY(facet(w.x, D, 0, t * D));
   }
   if (flags & ANYLOC_VIT_NORM_CONCAT)
     ANYLOC_TRY(l2norm_rows(out, ldo, out, ldo, out_rows, ldo, 1e-12f, stream));
@@ -609,13 +594,7 @@ int anyloc_vit_forward(anyloc_vit_t* h, const float* img, int64_t batch, int64_t
   ANYLOC_CHECK_ARG(img_h >= c.patch && img_w >= c.patch && img_h % c.patch == 0 && img_w % c.patch == 0,
                    "vit_forward: image %lldx%lld is not a positive multiple of the patch size %d", (long long)img_h,
                    (long long)img_w, c.patch);
-  ANYLOC_CHECK_ARG(n_taps >= 1 && n_taps <= 64, "vit_forward: n_taps %d", n_taps);
-  for (int t = 0; t < n_taps; ++t) {
-    ANYLOC_CHECK_ARG(tap_layers[t] >= 0 && tap_layers[t] < c.depth, "vit_forward: tap layer %d outside [0,%d)",
-                     tap_layers[t], c.depth);
-    ANYLOC_CHECK_ARG(tap_facets[t] >= 0 && tap_facets[t] <= 3, "vit_forward: facet %d", tap_facets[t]);
-    ANYLOC_CHECK_ARG(t == 0 || tap_layers[t] >= tap_layers[t - 1], "vit_forward: tap layers must ascend");
-  }
+  ANYLOC_TRY(check_taps("vit_forward", c, n_taps, tap_layers, tap_facets));
   return vit_forward_launches(h, img, batch, img_h, img_w, pos, n_taps, tap_layers, tap_facets, flags, out, workspace,
                               workspace_bytes, stream);
 }
@@ -661,14 +640,7 @@ int anyloc_vit_forward_ragged(anyloc_vit_t* h, const float* img, int32_t n_img, 
   int max_T = 0;
   ANYLOC_TRY(ragged_shape(h, n_img, img_hw, &rows, &max_T, "vit_forward_ragged"));
   ANYLOC_CHECK_ARG(img && dev_meta && pos && out && tap_layers && tap_facets, "vit_forward_ragged: null pointer");
-  const anyloc_vit_config& c = h->cfg;
-  ANYLOC_CHECK_ARG(n_taps >= 1 && n_taps <= 64, "vit_forward_ragged: n_taps %d", n_taps);
-  for (int t = 0; t < n_taps; ++t) {
-    ANYLOC_CHECK_ARG(tap_layers[t] >= 0 && tap_layers[t] < c.depth, "vit_forward_ragged: tap layer %d outside [0,%d)",
-                     tap_layers[t], c.depth);
-    ANYLOC_CHECK_ARG(tap_facets[t] >= 0 && tap_facets[t] <= 3, "vit_forward_ragged: facet %d", tap_facets[t]);
-    ANYLOC_CHECK_ARG(t == 0 || tap_layers[t] >= tap_layers[t - 1], "vit_forward_ragged: tap layers must ascend");
-  }
+  ANYLOC_TRY(check_taps("vit_forward_ragged", h->cfg, n_taps, tap_layers, tap_facets));
   const RaggedBatch rg{dev_meta, rows, max_T};
   return vit_forward_launches(h, img, n_img, 0, 0, pos, n_taps, tap_layers, tap_facets, flags, out, workspace, workspace_bytes,
                               stream, &rg);

@@ -322,21 +322,15 @@ class HipDinoV2:
             tok, out_off, pix = ragged_offsets(sizes, use_cls, registers=self.n_reg)
             if flat.numel() != pix[-1]:
                 raise ValueError(f"packed buffer holds {flat.numel()} floats, the sizes need {int(pix[-1])}")
-            taps = list(taps)
-            for layer, facet in taps:
-                if not 0 <= layer < self.depth:
-                    raise IndexError(f"layer {layer} outside the {self.depth} loaded blocks")
-            order = sorted(range(len(taps)), key=lambda i: taps[i][0])
+            taps, inv = self._ascending(taps)
             offsets = torch.from_numpy(out_off).to(self.device)
             chunks = ragged_chunks(sizes, self.max_rows, registers=self.n_reg)
-            inv = [order.index(i) for i in range(len(taps))] if order != list(range(len(taps))) else None
             # one chunk (the common case): the forward writes the caller's result directly; several: into slices of it
             out = None if len(chunks) == 1 and inv is None else \
                 torch.empty(int(out_off[-1]), len(taps) * self.dim, dtype=torch.float32, device=self.device)
             for a, b in chunks:
                 r0, r1 = int(out_off[a]), int(out_off[b])
-                res = self._forward_ragged(flat[int(pix[a]):int(pix[b])], sizes[a:b], [taps[i] for i in order], use_cls,
-                                           norm_taps, norm_concat)
+                res = self._forward_ragged(flat[int(pix[a]):int(pix[b])], sizes[a:b], taps, use_cls, norm_taps, norm_concat)
                 if out is None:
                     return res, offsets
                 if inv is not None:
@@ -374,24 +368,53 @@ class HipDinoV2:
         if ws_bytes == 0:
             raise _lib.AnylocHipError(f"anyloc_vit_workspace_bytes_ragged: {lib.anyloc_last_error().decode()}")
         ws = _lib.workspace(ws_bytes, self.device, "vit")
-        layers = (C.c_int32 * n_taps)(*[t[0] for t in taps])
-        facets = (C.c_int32 * n_taps)(*[ops.FACETS[t[1]] for t in taps])
-        flags = (ops.VIT_USE_CLS if use_cls else 0) | (ops.VIT_NORM_TAPS if norm_taps else 0) | \
-            (ops.VIT_NORM_CONCAT if norm_concat else 0) | (ops.VIT_SPLIT_BF16 if self.gemm == "x6" else 0) | \
-            (ops.VIT_SPLIT_FP16 if self.gemm == "h3" else 0)
+        n_taps, layers, facets, flags = self._tap_args(taps, use_cls, norm_taps, norm_concat)
 
         def forward(y):
             _lib.check(lib.anyloc_vit_forward_ragged(self._handle, _lib.ptr(flat), n_img, hw_host, _lib.ptr(dev_meta),
                                                      _lib.ptr(pos), n_taps, layers, facets, flags, _lib.ptr(y), _lib.ptr(ws),
                                                      ws.numel(), _lib.stream_ptr()), "anyloc_vit_forward_ragged")
+        def rows(members):                    # the images' rows of the packed output
+            return torch.from_numpy(np.concatenate([np.arange(out_off[b], out_off[b + 1]) for b in members])).to(self.device)
+        return self._ffn_checked(forward, out, n_img, taps[-1][0] + 1, rows)
+
+    def _tap_args(self, taps, use_cls, norm_taps, norm_concat):
+        """-> (n_taps, layers, facets, flags) of the C call."""
+        n_taps = len(taps)
+        layers = (C.c_int32 * n_taps)(*[t[0] for t in taps])
+        facets = (C.c_int32 * n_taps)(*[ops.FACETS[t[1]] for t in taps])
+        flags = (ops.VIT_USE_CLS if use_cls else 0) | (ops.VIT_NORM_TAPS if norm_taps else 0) | \
+            (ops.VIT_NORM_CONCAT if norm_concat else 0) | (ops.VIT_SPLIT_BF16 if self.gemm == "x6" else 0) | \
+            (ops.VIT_SPLIT_FP16 if self.gemm == "h3" else 0)
+        return n_taps, layers, facets, flags
+
+    def _ascending(self, taps):
+        """Range-check ``taps`` -> (the taps in ascending layer order, as the forward visits them; the permutation that gives
+        the caller its feature blocks back in the order it asked for, or None when that is the order already)."""
+        taps = list(taps)
+        for layer, facet in taps:
+            if not 0 <= layer < self.depth:
+                raise IndexError(f"layer {layer} outside the {self.depth} loaded blocks")
+        order = sorted(range(len(taps)), key=lambda i: taps[i][0])
+        inv = [order.index(i) for i in range(len(taps))] if order != list(range(len(taps))) else None
+        return [taps[i] for i in order], inv
+
+    def _ffn_checked(self, forward, out, n_img, n_blocks, rows):
+        """``forward(out)`` under the FFN-bound check (h3 with ``ffn_check``; otherwise just the call).  ``forward(y)`` runs
+        the whole call into ``y``; ``n_blocks`` blocks execute; ``rows(members)`` -> index tensor of the dim-0 entries of the
+        output that belong to the images ``members``."""
         if self.gemm != "h3" or not self.ffn_check:
             forward(out)
             return out
-        # the FFN-bound check of _forward_taps, per image of the ragged batch: images that trip blocks are grouped by the
-        # set they trip, the WHOLE call runs again with exactly that set exact, and only the group's rows are taken from it
-        loose = self._telemetry_call(lambda: forward(out), n_img, taps[-1][0] + 1)
+        # the call with the FFN-bound telemetry on: one figure per (executed block, image)
+        loose = self._telemetry_call(lambda: forward(out), n_img, n_blocks)
         bad = loose > FFN_LOOSENESS_MAX
         if bad.any():
+            # images grouped by the set of blocks THEY trip: for each such set the call runs again with exactly those
+            # blocks exact -- the WHOLE batch, same row count and batch positions, because the kernels' summation orders
+            # depend on both (small-M plans, the global 32-row key groups of attention) -- and only the group's images
+            # take their rows from it.  So an image's bits depend on the image, its position and the call's shape, never
+            # on what its batch mates contain; the switches are cleared before the call returns.
             groups = {}
             for b in range(n_img):
                 key = tuple(int(l) for l in np.nonzero(bad[:, b])[0])
@@ -400,8 +423,8 @@ class HipDinoV2:
             res = torch.empty_like(out)
             for key, members in groups.items():
                 self._with_exact(key, lambda: forward(res))
-                rows = torch.from_numpy(np.concatenate([np.arange(out_off[b], out_off[b + 1]) for b in members])).to(self.device)
-                out.index_copy_(0, rows, res.index_select(0, rows))
+                idx = rows(members)
+                out.index_copy_(0, idx, res.index_select(0, idx))
                 self.ffn_exact_blocks.update(key)
                 self.ffn_reruns += len(members)
         return out
@@ -446,70 +469,40 @@ class HipDinoV2:
     def _forward_taps(self, img, taps, use_cls, norm_taps, norm_concat):
         if img.ndim != 4 or img.shape[1] != 3:
             raise ValueError(f"expected an image batch [B,3,H,W], got {tuple(img.shape)}")
-        B, _, H, W = img.shape
+        H, W = img.shape[2:]
         assert H % PATCH == 0, f"Input image height {H} is not a multiple of patch height {PATCH}"
         assert W % PATCH == 0, f"Input image width {W} is not a multiple of patch width: {PATCH}"
-        img = ops._f32c(img, self.device)
-        taps = list(taps)
-        for layer, facet in taps:
-            if not 0 <= layer < self.depth:
-                raise IndexError(f"layer {layer} outside the {self.depth} loaded blocks")
-        order = sorted(range(len(taps)), key=lambda i: taps[i][0])        # the forward visits layers in ascending order
-        if order != list(range(len(taps))):
-            # ... and the caller gets its feature blocks in the order it asked for ("l n d -> n (l d)", reference
-            # scripts/dino_v2_vlad_viz.py:175-196); every normalisation is invariant to the block order
-            res = self._forward_taps(img, [taps[i] for i in order], use_cls, norm_taps, norm_concat)
-            blocks = res.reshape(res.shape[0], res.shape[1], len(taps), self.dim)
-            inv = [order.index(i) for i in range(len(taps))]
-            return blocks[:, :, inv].reshape(res.shape[0], res.shape[1], -1).contiguous()
-        n_taps = len(taps)
+        taps, inv = self._ascending(taps)
+        res = self._forward_uniform(ops._f32c(img, self.device), taps, use_cls, norm_taps, norm_concat)
+        if inv is None:
+            return res
+        # the caller's tap order ("l n d -> n (l d)", reference scripts/dino_v2_vlad_viz.py:175-196); every normalisation
+        # is invariant to the block order
+        blocks = res.reshape(res.shape[0], res.shape[1], len(taps), self.dim)
+        return blocks[:, :, inv].reshape(res.shape[0], res.shape[1], -1).contiguous()
+
+    def _forward_uniform(self, img, taps, use_cls, norm_taps, norm_concat):
+        """One batch of equal-sized images (taps ascending) -> [B, N(+1), len(taps)*D]."""
+        B, _, H, W = img.shape
         np_ = (H // PATCH) * (W // PATCH)
-        rows = np_ + 1 if use_cls else np_
-        out = torch.empty(B, rows, n_taps * self.dim, dtype=torch.float32, device=self.device)
+        out = torch.empty(B, np_ + 1 if use_cls else np_, len(taps) * self.dim, dtype=torch.float32, device=self.device)
         if B == 0:
             return out
         chunk = max(1, self.max_rows // (np_ + 1 + self.n_reg))
         if self.gemm in ("x6", "h3") and B > chunk:
             for s0 in range(0, B, chunk):
-                out[s0:s0 + chunk] = self._forward_taps(img[s0:s0 + chunk], taps, use_cls, norm_taps, norm_concat)
+                out[s0:s0 + chunk] = self._forward_uniform(img[s0:s0 + chunk], taps, use_cls, norm_taps, norm_concat)
             return out
         lib = _lib.load()
         ws_bytes = lib.anyloc_vit_workspace_bytes(self._handle, B, H, W)
         ws = _lib.workspace(ws_bytes, self.device, "vit")
-        layers = (C.c_int32 * n_taps)(*[t[0] for t in taps])
-        facets = (C.c_int32 * n_taps)(*[ops.FACETS[t[1]] for t in taps])
-        flags = (ops.VIT_USE_CLS if use_cls else 0) | (ops.VIT_NORM_TAPS if norm_taps else 0) | \
-            (ops.VIT_NORM_CONCAT if norm_concat else 0) | (ops.VIT_SPLIT_BF16 if self.gemm == "x6" else 0) | \
-            (ops.VIT_SPLIT_FP16 if self.gemm == "h3" else 0)
-        def forward(x, y):
-            _lib.check(lib.anyloc_vit_forward(self._handle, _lib.ptr(x), x.shape[0], H, W, _lib.ptr(self.pos_table(H, W)),
+        n_taps, layers, facets, flags = self._tap_args(taps, use_cls, norm_taps, norm_concat)
+
+        def forward(y):
+            _lib.check(lib.anyloc_vit_forward(self._handle, _lib.ptr(img), B, H, W, _lib.ptr(self.pos_table(H, W)),
                                               n_taps, layers, facets, flags, _lib.ptr(y), _lib.ptr(ws),
                                               ws.numel(), _lib.stream_ptr()), "anyloc_vit_forward")
-        if self.gemm != "h3" or not self.ffn_check:
-            forward(img, out)
-            return out
-        # the call with the FFN-bound telemetry on: one figure per (executed block, image)
-        loose = self._telemetry_call(lambda: forward(img, out), B, taps[-1][0] + 1)
-        bad = loose > FFN_LOOSENESS_MAX
-        if bad.any():
-            # images grouped by the set of blocks THEY trip: for each such set the call runs again with exactly those
-            # blocks exact -- the WHOLE batch, same row count and batch positions, because the kernels' summation orders
-            # depend on both (small-M plans, the global 32-row key groups of attention) -- and only the group's images
-            # take their rows from it.  So an image's bits depend on the image, its position and the call's shape, never
-            # on what its batch mates contain; the switches are cleared before the call returns.
-            groups = {}
-            for b in range(B):
-                key = tuple(int(l) for l in np.nonzero(bad[:, b])[0])
-                if key:
-                    groups.setdefault(key, []).append(b)
-            res = torch.empty_like(out)
-            for key, members in groups.items():
-                self._with_exact(key, lambda: forward(img, res))
-                idx = torch.tensor(members, device=self.device)
-                out.index_copy_(0, idx, res.index_select(0, idx))
-                self.ffn_exact_blocks.update(key)
-                self.ffn_reruns += len(members)
-        return out
+        return self._ffn_checked(forward, out, B, taps[-1][0] + 1, lambda members: torch.tensor(members, device=self.device))
 
 
 def hub_load(repo_or_dir, model, *args, **kwargs):
