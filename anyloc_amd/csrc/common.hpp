@@ -340,6 +340,11 @@ int screen_compact(const float* scores, int64_t ld, int64_t ncols, int64_t nq, i
 bool screen_rescore_supported(int64_t dim);
 int screen_rescore(const float* queries, const float* db, int64_t dim, int64_t nq, int cmax, const int* cand, const int* count,
                    int metric, const float* qn, const float* dn, const float* dnorm, float* cand_v, hipStream_t stream);
+// the same from the two planes of a prepared index (img + p * slot: the image of panel p; dinv: the 2^-e of ALL rows; the
+// candidates are columns of the range that starts at database row s0; dn / dnorm already point at that range)
+int screen_rescore_planes(const float* queries, const unsigned char* img, size_t slot, int64_t panel, int64_t ndb, int64_t s0,
+                          const float* dinv, int64_t dim, int64_t nq, int cmax, const int* cand, const int* count, int metric,
+                          const float* qn, const float* dn, const float* dnorm, float* cand_v, hipStream_t stream);
 int screen_select(const int* cand, const float* cand_v, const int* count, int cmax, int64_t col_base, int64_t nq, int k, float* run_v,
                   int64_t* run_i, int first, hipStream_t stream);
 

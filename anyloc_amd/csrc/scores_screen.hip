@@ -21,6 +21,7 @@
 // Kernels: gemm_screen_kernel (256 x 256 tiles, 8 waves, v_mfma_f32_16x16x32_f16, leading planes only, 4-deep DMA ring of
 // 32-k stages), screen_compact_kernel (threshold filter of a query's screened row -> candidate columns),
 // screen_rescore_kernel (one workgroup per query: the query in registers, four candidate rows per step, float64 sums),
+// screen_rescore_planes_kernel (the same from the two fp16 planes of a prepared index: no fp32 rows needed),
 // screen_select_kernel (candidates + running list -> new running list, rank by counting 64-bit keys).
 #include "common.hpp"
 #include "tile_order.hpp"
@@ -231,6 +232,109 @@ __global__ __launch_bounds__(512) void screen_rescore_kernel(const float* __rest
   }
 }
 
+// ------------------------------------------------------------------------------------------ re-score from the index
+// The same re-scoring WITHOUT the fp32 rows (ANYLOC_TOPK_RESCORE_PLANES): a candidate row is read from the two fp16 planes of
+// the prepared index (topk.hip: index_view), whose sum (hi + lo) 2^-e IS the database the index holds -- every element within
+// 2^-23 of its row's maximum, the operands the unscreened indexed search scores.  Candidate column c of the range that starts
+// at database row s0 is global row r = s0 + c = panel p, local row lr; panel p's image starts at img + p * slot and has
+// R_p = min(panel, ndb - p * panel) rows; k-block kb, plane pl of the row is the 32 bytes at ((kb * 2 + pl) * R_p + lr) * 32,
+// 16-byte halves swapped when (lr >> 3) & 1 (gemm_h3.hip).  Thread t holds query columns 8 u .. 8 u + 7 of the units
+// u = t + 512 j, j < NU (dim <= 4096 NU): unit u = half (u & 1) of k-block u >> 1, so a thread fetches 16 bytes of the leading
+// plane and the matching 16 of the residual plane (a lane pair reads one 32-byte piece, pieces 2 R_p * 32 bytes apart: the
+// bytes of the fp32 row in dim / 16 * 2 pieces).  Plain 64-bit global loads: the index may be far larger than a buffer
+// descriptor's range.  (double)hi + (double)lo is exact, products and sums in float64, the fixed tree of the sibling, and the
+// row's 2^-e (a power of two: exact) on the sum.
+template <int NU>
+__global__ __launch_bounds__(512) void screen_rescore_planes_kernel(const float* __restrict__ queries, const unsigned char* __restrict__ img,
+                                                                    size_t slot, int64_t panel, int64_t ndb, int64_t s0,
+                                                                    const float* __restrict__ dinv, int64_t dim, int cmax,
+                                                                    const int* __restrict__ cand, const int* __restrict__ count, int metric,
+                                                                    const float* __restrict__ qn, const float* __restrict__ dn,
+                                                                    const float* __restrict__ dnorm, float* __restrict__ cand_v) {
+  __shared__ double red[8][RS_G];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t q = blockIdx.x;
+  const int n = min(count[q], cmax);
+  const int n8 = (int)(dim >> 3);
+  f32x4 qa[NU], qb[NU];
+#pragma unroll
+  for (int j = 0; j < NU; ++j) {
+    const int u = tid + 512 * j;
+    const f32x4* qr = reinterpret_cast<const f32x4*>(queries + q * dim);
+    qa[j] = u < n8 ? qr[2 * u] : f32x4{0.f, 0.f, 0.f, 0.f};
+    qb[j] = u < n8 ? qr[2 * u + 1] : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const float qq = metric ? qn[q] : 0.f;
+  for (int i0 = 0; i0 < n; i0 += RS_G) {
+    // the row inside its panel image (the same for the whole workgroup: a 64-bit base) + this thread's 16 bytes of k-block
+    // tid >> 1, leading plane (an image stays inside 2 GiB: 32-bit offsets)
+    const unsigned char* dr[RS_G];
+    unsigned plane[RS_G], off0[RS_G];                      // bytes of one plane of the row's image: R_p * 32
+#pragma unroll
+    for (int g = 0; g < RS_G; ++g) {
+      const int64_t r = s0 + cand[q * cmax + min(i0 + g, n - 1)];   // (a short last group re-reads its last row; the copy is not stored)
+      const int64_t p = r / panel, lr = r - p * panel;
+      plane[g] = (unsigned)(min(panel, ndb - p * panel) * 32);
+      dr[g] = img + (size_t)p * slot + lr * 32;
+      off0[g] = (unsigned)(((tid & 1) ^ (int)((lr >> 3) & 1)) << 4) + (unsigned)(tid >> 1) * 2u * plane[g];
+    }
+    double s[RS_G];
+#pragma unroll
+    for (int g = 0; g < RS_G; ++g) s[g] = 0.0;
+    // the loads of unit j + 1 fly over the arithmetic of unit j (the compiler may not hoist further ones past the fence:
+    // the whole row's loads in flight would not fit the registers next to the query)
+    sc_f16x8 hi[RS_G], lo[RS_G], hi_n[RS_G], lo_n[RS_G];
+    auto load = [&](int j, sc_f16x8 (&h)[RS_G], sc_f16x8 (&l)[RS_G]) {
+      if (tid + 512 * j < n8) {
+#pragma unroll
+        for (int g = 0; g < RS_G; ++g) {
+          const unsigned o = off0[g] + (unsigned)(512 * j) * plane[g];       // k-block (tid >> 1) + 256 j
+          h[g] = *reinterpret_cast<const sc_f16x8*>(dr[g] + o);
+          l[g] = *reinterpret_cast<const sc_f16x8*>(dr[g] + (o + plane[g]));
+        }
+      }
+    };
+    load(0, hi, lo);
+    // (the query stays fp32 in its registers: without this the float64 conversions of all of it are hoisted out of the loop
+    // over the candidates, twice the registers)
+#pragma unroll
+    for (int j = 0; j < NU; ++j) asm volatile("" : "+v"(qa[j]), "+v"(qb[j]));
+#pragma unroll
+    for (int j = 0; j < NU; ++j) {
+      if (j + 1 < NU) load(j + 1, hi_n, lo_n);
+      asm volatile("" ::: "memory");
+      if (tid + 512 * j < n8) {
+#pragma unroll
+        for (int g = 0; g < RS_G; ++g) {
+          double v[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] = (double)(float)hi[g][e] + (double)(float)lo[g][e];
+          s[g] += (((double)qa[j][0] * v[0] + (double)qa[j][1] * v[1]) + ((double)qa[j][2] * v[2] + (double)qa[j][3] * v[3])) +
+                  (((double)qb[j][0] * v[4] + (double)qb[j][1] * v[5]) + ((double)qb[j][2] * v[6] + (double)qb[j][3] * v[7]));
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < RS_G; ++g) {
+        hi[g] = hi_n[g];
+        lo[g] = lo_n[g];
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < RS_G; ++g) {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) s[g] += __shfl_xor(s[g], off, 64);
+      if (lane == 0) red[wave][g] = s[g];
+    }
+    __syncthreads();
+    if (tid < RS_G && i0 + tid < n) {
+      const int c = cand[q * cmax + i0 + tid];
+      const double tot = ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid])) + ((red[4][tid] + red[5][tid]) + (red[6][tid] + red[7][tid]));
+      cand_v[q * cmax + i0 + tid] = screen_value((float)(tot * (double)dinv[s0 + c]), c, metric, qq, dn, dnorm);
+    }
+    __syncthreads();
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------ select
 // One workgroup per query: the re-scored candidates of this column range (global index col_base + column) and the running
 // list (first == 0) -> the best k by (value, then lower index) -> the running list.  Rank by counting over 64-bit keys
@@ -433,6 +537,25 @@ int screen_rescore(const float* queries, const float* db, int64_t dim, int64_t n
   else ANYLOC_RESCORE(24);
 #undef ANYLOC_RESCORE
   return launch_status("screen_rescore_kernel");
+}
+
+int screen_rescore_planes(const float* queries, const unsigned char* img, size_t slot, int64_t panel, int64_t ndb, int64_t s0,
+                          const float* dinv, int64_t dim, int64_t nq, int cmax, const int* cand, const int* count, int metric,
+                          const float* qn, const float* dn, const float* dnorm, float* cand_v, hipStream_t stream) {
+  ANYLOC_CHECK_ARG(dim % 16 == 0 && screen_rescore_supported(dim), "screen_rescore_planes: dim %lld not served", (long long)dim);
+  ANYLOC_CHECK_ARG(img && dinv && panel > 0 && s0 >= 0 && s0 < ndb, "screen_rescore_planes: bad index");
+  ProfScope prof("topk_screen_rescore_planes", stream, 0.0, 0.0);
+  const int nu = (int)((dim / 8 + 511) / 512);
+#define ANYLOC_RESCORE_PLANES(NU)                                                                                                \
+  hipLaunchKernelGGL((screen_rescore_planes_kernel<NU>), dim3((unsigned)nq), dim3(512), 0, stream, queries, img, slot, panel, ndb, s0, \
+                     dinv, dim, cmax, cand, count, metric, qn, dn, dnorm, cand_v)
+  if (nu <= 1) ANYLOC_RESCORE_PLANES(1);
+  else if (nu <= 2) ANYLOC_RESCORE_PLANES(2);
+  else if (nu <= 4) ANYLOC_RESCORE_PLANES(4);
+  else if (nu <= 8) ANYLOC_RESCORE_PLANES(8);
+  else ANYLOC_RESCORE_PLANES(12);
+#undef ANYLOC_RESCORE_PLANES
+  return launch_status("screen_rescore_planes_kernel");
 }
 
 size_t screen_select_lds(int cmax, int k) { return (size_t)(cmax + k) * 8 + (size_t)((cmax + k + 1) & ~1) * 4 + (size_t)(cmax + k) * 8 + 16; }

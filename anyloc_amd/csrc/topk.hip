@@ -403,7 +403,7 @@ static int topk_impl(const float* queries, int64_t nq, const float* db, int64_t 
   ANYLOC_CHECK_ARG(metric == 0 || metric == 1, "topk: metric %d", metric);
   ANYLOC_CHECK_ARG(dim >= 4 && dim % 4 == 0, "topk: dim %lld must be a positive multiple of 4", (long long)dim);
   ANYLOC_CHECK_ARG(nq < (1ll << 31), "topk: too many queries");
-  ANYLOC_CHECK_ARG((flags & ~ANYLOC_TOPK_NORMALIZE_DB) == 0, "topk: unknown flags %u", flags);
+  ANYLOC_CHECK_ARG((flags & ~(ANYLOC_TOPK_NORMALIZE_DB | (indexed ? ANYLOC_TOPK_RESCORE_PLANES : 0u))) == 0, "topk: unknown flags %u", flags);
   TopkWs w = carve(workspace, workspace_bytes, nq, ndb, dim, indexed, k);
   const bool norm_db = (flags & ANYLOC_TOPK_NORMALIZE_DB) != 0;
   const bool few = !indexed && few_queries(nq, dim);
@@ -422,8 +422,11 @@ static int topk_impl(const float* queries, int64_t nq, const float* db, int64_t 
   // screened search (scores_screen.hip): the panels are scored on the leading fp16 planes alone, the rows their error bound
   // cannot rule out are re-scored exactly from the fp32 rows -- needs those rows (a prepared index WITH its rows:
   // anyloc_topk_search_index_rows).  The bound of a query is one number: its own norm and residual x the LARGEST row norm the
-  // compared value sees -- 1 with ANYLOC_TOPK_NORMALIZE_DB, the largest raw row norm of the database without it
-  const bool screen = allow_screen && h3 && w.sc_cols > 0 && db != nullptr && ndb > 0;
+  // compared value sees -- 1 with ANYLOC_TOPK_NORMALIZE_DB, the largest raw row norm of the database without it.
+  // ANYLOC_TOPK_RESCORE_PLANES: the candidates are re-scored from the two planes of the index instead (the 22-bit rows the
+  // index holds, which the unscreened indexed search scores too) -- no rows needed, and none read when they are given
+  const bool rescore_planes = indexed && (flags & ANYLOC_TOPK_RESCORE_PLANES) != 0;
+  const bool screen = allow_screen && h3 && w.sc_cols > 0 && (db != nullptr || rescore_planes) && ndb > 0;
   if (metric == 1 || screen) {
     hipLaunchKernelGGL(rownorm_sq_kernel, dim3((unsigned)nq), dim3(256), 0, stream, queries, dim, w.qn);
     ANYLOC_TRY(launch_status("rownorm_sq_kernel(q)"));
@@ -521,8 +524,12 @@ static int topk_impl(const float* queries, int64_t nq, const float* db, int64_t 
       const float* dnorm_s = dnorm_all ? dnorm_all + s0 : nullptr;
       ANYLOC_TRY(screen_compact(w.sbuf, sn, sn, nq, (int)k, metric, w.qn, w.dn + s0, dnorm_s, w.scr_v, w.margin, SCREEN_CMAX, w.cand,
                                 w.count, w.overflow, stream));
-      ANYLOC_TRY(screen_rescore(queries, db + s0 * dim, dim, nq, SCREEN_CMAX, w.cand, w.count, metric, w.qn, w.dn + s0, dnorm_s,
-                                w.cand_v, stream));
+      if (rescore_planes)
+        ANYLOC_TRY(screen_rescore_planes(queries, iv.img, iv.slot, iv.panel, ndb, s0, iv.dinv, dim, nq, SCREEN_CMAX, w.cand, w.count,
+                                         metric, w.qn, w.dn + s0, dnorm_s, w.cand_v, stream));
+      else
+        ANYLOC_TRY(screen_rescore(queries, db + s0 * dim, dim, nq, SCREEN_CMAX, w.cand, w.count, metric, w.qn, w.dn + s0, dnorm_s,
+                                  w.cand_v, stream));
       ANYLOC_TRY(screen_select(w.cand, w.cand_v, w.count, SCREEN_CMAX, index_base + s0, nq, (int)k, dist, idx, first_exact, stream));
       first_exact = 0;
     }
@@ -635,6 +642,8 @@ extern "C" {
 int anyloc_topk(const float* queries, int64_t nq, const float* db, int64_t ndb, int64_t dim, int64_t k, int metric,
                 unsigned flags, int64_t index_base, float* dist, int64_t* idx, void* workspace, size_t workspace_bytes,
                 void* stream) {
+  ANYLOC_CHECK_ARG((flags & ANYLOC_TOPK_RESCORE_PLANES) == 0,
+                   "topk: ANYLOC_TOPK_RESCORE_PLANES needs a prepared index (anyloc_topk_search_index / anyloc_topk_search_index_rows)");
   return topk_impl(queries, nq, db, ndb, dim, k, metric, flags, index_base, dist, idx, workspace, workspace_bytes, nullptr,
                    static_cast<hipStream_t>(stream));
 }
@@ -649,7 +658,6 @@ size_t anyloc_topk_index_bytes(int64_t ndb, int64_t dim) {
 }
 
 int anyloc_topk_index_build(const float* db, int64_t ndb, int64_t dim, void* index, size_t index_bytes, void* stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
   ANYLOC_CHECK_ARG(db && index && ndb > 0, "topk_index_build: null pointer / empty database");
   if (!index_supported(ndb, dim)) {
     set_error("topk_index_build: dim %lld is not served by the fp16 score panels", (long long)dim);
@@ -660,10 +668,37 @@ int anyloc_topk_index_build(const float* db, int64_t ndb, int64_t dim, void* ind
     set_error("topk_index_build: index buffer %zu < %zu", index_bytes, iv.bytes);
     return ANYLOC_ERR_WORKSPACE;
   }
-  for (int64_t c0 = 0; c0 < ndb; c0 += iv.panel) {
-    const int64_t pc = std::min<int64_t>(iv.panel, ndb - c0);
-    ANYLOC_TRY(split_h2_wide(db + c0 * dim, dim, pc, dim, iv.img + (size_t)(c0 / iv.panel) * iv.slot, iv.dinv + c0, iv.dss + c0, stream));
-    ANYLOC_TRY(screen_resid(iv.img + (size_t)(c0 / iv.panel) * iv.slot, pc, (int)(dim / 16), pc, iv.dinv + c0, iv.dss + c0, iv.drho + c0, nullptr, stream));
+  return anyloc_topk_index_build_range(db, 0, ndb, ndb, dim, index, index_bytes, stream_);
+}
+
+int64_t anyloc_topk_index_panel(int64_t dim) { return index_supported(1, dim) ? index_panel(dim) : 0; }
+
+int anyloc_topk_index_build_range(const float* rows, int64_t row0, int64_t nrows, int64_t ndb, int64_t dim, void* index,
+                                  size_t index_bytes, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (!index_supported(ndb, dim)) {
+    set_error("topk_index_build_range: a [%lld, %lld] database is not served by the fp16 score panels", (long long)ndb, (long long)dim);
+    return ANYLOC_ERR_UNSUPPORTED;
+  }
+  const IndexView iv = index_view(index, ndb, dim);
+  ANYLOC_CHECK_ARG(row0 >= 0 && nrows > 0 && nrows <= ndb && row0 <= ndb - nrows,
+                   "topk_index_build_range: rows [%lld, %lld + %lld) are not inside the %lld rows of the database", (long long)row0,
+                   (long long)row0, (long long)nrows, (long long)ndb);
+  ANYLOC_CHECK_ARG(row0 % iv.panel == 0, "topk_index_build_range: row0 %lld is not a multiple of the panel (%lld rows)", (long long)row0,
+                   (long long)iv.panel);
+  ANYLOC_CHECK_ARG(nrows % iv.panel == 0 || row0 + nrows == ndb,
+                   "topk_index_build_range: nrows %lld is neither a multiple of the panel (%lld rows) nor ends at the last row",
+                   (long long)nrows, (long long)iv.panel);
+  if (iv.bytes > index_bytes) {
+    set_error("topk_index_build_range: index buffer %zu < %zu", index_bytes, iv.bytes);
+    return ANYLOC_ERR_WORKSPACE;
+  }
+  ANYLOC_CHECK_ARG(rows && index, "topk_index_build_range: null pointer");
+  for (int64_t c0 = row0; c0 < row0 + nrows; c0 += iv.panel) {
+    const int64_t pc = std::min<int64_t>(iv.panel, ndb - c0);     // (a range ends on a panel boundary or at the last row)
+    unsigned char* img = iv.img + (size_t)(c0 / iv.panel) * iv.slot;
+    ANYLOC_TRY(split_h2_wide(rows + (c0 - row0) * dim, dim, pc, dim, img, iv.dinv + c0, iv.dss + c0, stream));
+    ANYLOC_TRY(screen_resid(img, pc, (int)(dim / 16), pc, iv.dinv + c0, iv.dss + c0, iv.drho + c0, nullptr, stream));
   }
   return ANYLOC_OK;
 }

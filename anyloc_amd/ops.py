@@ -429,6 +429,7 @@ def kmeans_update(sums, counts, centers_old):
 
 
 TOPK_NORMALIZE_DB = 1
+TOPK_RESCORE_PLANES = 2    # indexed searches only: the screened search re-scores from the planes of the index (no fp32 rows)
 
 
 def topk(queries, db, k, metric="ip", index_base=0, normalize_db=False):
@@ -475,9 +476,30 @@ def topk_index_build(db):
     return index
 
 
-def topk_indexed(queries, index, ndb, k, metric="ip", index_base=0, normalize_db=False, db=None):
+def topk_index_panel(dim):
+    """Rows per panel of a prepared index of ``dim`` columns (0: the fp16 score panels do not serve ``dim``)."""
+    return int(_lib.load().anyloc_topk_index_panel(int(dim)))
+
+
+def topk_index_build_range(index, rows, row0, ndb):
+    """faiss' ``index.add(chunk)``: quantise database rows ``[row0, row0 + len(rows))`` into ``index``, the uint8 buffer of
+    ``topk_index_bytes(ndb, dim)`` bytes of an ``ndb``-row database (anyloc_topk_index_build_range).  ``row0`` is a multiple of
+    ``topk_index_panel(dim)``; the range is whole panels or ends at ``ndb``.  Once every panel is written the index is the one
+    ``topk_index_build`` makes of all rows at once, bit for bit."""
+    _need_cuda(index, rows)
+    rows = _f32c(rows)
+    nrows, dim = rows.shape
+    _lib.check(_lib.load().anyloc_topk_index_build_range(_lib.ptr(rows), int(row0), nrows, int(ndb), dim, _lib.ptr(index),
+                                                         index.numel(), _lib.stream_ptr()), "anyloc_topk_index_build_range")
+    return index
+
+
+def topk_indexed(queries, index, ndb, k, metric="ip", index_base=0, normalize_db=False, db=None, rescore_planes=False):
     """``topk`` against a database prepared by ``topk_index_build`` (same results; the fp32 rows are not read).  ``db``: the
-    fp32 rows the index was built from -- with them the screened search (option ``topk_screen``) can re-score its candidates."""
+    fp32 rows the index was built from -- with them the screened search (option ``topk_screen``) can re-score its candidates.
+    ``rescore_planes`` (ANYLOC_TOPK_RESCORE_PLANES): the screened search re-scores from the planes of the index instead -- it
+    runs without ``db`` (and does not read it when given); the lists are the float64-exact ones over the 22-bit rows the index
+    holds."""
     _need_cuda(queries, index)
     queries = _f32c(queries)
     if db is not None:
@@ -494,7 +516,8 @@ def topk_indexed(queries, index, ndb, k, metric="ip", index_base=0, normalize_db
     ws = _lib.workspace(lib.anyloc_topk_index_workspace_bytes(nq, ndb, dim, k), queries.device, "topk")
     _lib.check(lib.anyloc_topk_search_index_rows(_lib.ptr(queries), nq, _lib.ptr(db) if db is not None else None, _lib.ptr(index),
                                                  int(ndb), dim, k, 0 if metric == "ip" else 1,
-                                                 TOPK_NORMALIZE_DB if normalize_db else 0, index_base, _lib.ptr(dist), _lib.ptr(idx),
+                                                 (TOPK_NORMALIZE_DB if normalize_db else 0) | (TOPK_RESCORE_PLANES if rescore_planes else 0),
+                                                 index_base, _lib.ptr(dist), _lib.ptr(idx),
                                                  _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
                "anyloc_topk_search_index_rows")
     return dist, idx

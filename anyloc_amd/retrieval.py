@@ -44,17 +44,31 @@ class FlatIndex:
 
     ``planes``: "auto" builds the images when the shape is served (dim % 16 == 0) and the device has the memory to spare,
     True insists, False never (every search quantises on the fly, as ``search``).  ``keep_fp32=False`` drops the reference
-    to the fp32 rows once the images exist (every search then runs on the panels)."""
+    to the fp32 rows once the images exist (every search then runs on the panels).
 
-    def __init__(self, db, method="cosine", norm_descs=True, planes="auto", keep_fp32=True):
+    ``rescore``: where the SCREENED search (option ``topk_screen``) takes the exact scores of its candidates from.  "rows"
+    (default): the fp32 rows, so an index without them searches unscreened.  "planes": the two planes of the index
+    (ANYLOC_TOPK_RESCORE_PLANES) -- insists on the planes, and with ``keep_fp32=False`` the index is ONE copy of the database
+    (4 bytes per element, as faiss keeps after ``index.add``) that still searches screened; its lists are the float64-exact
+    ones over the 22-bit rows the planes hold (every element within 2^-23 of its row's maximum)."""
+
+    def __init__(self, db, method="cosine", norm_descs=True, planes="auto", keep_fp32=True, rescore="rows"):
         if method not in ("cosine", "l2"):
             raise NotImplementedError(f"Method: {method}")
+        if rescore not in ("rows", "planes"):
+            raise ValueError(f"rescore: {rescore!r} (\"rows\" or \"planes\")")
         dev = _lib.require_gpu()
         self.method, self.norm_descs = method, bool(norm_descs)
         self.db = ops._f32c(torch.as_tensor(db), dev)
         self.ntotal, self.dim = int(self.db.shape[0]), int(self.db.shape[1])
         self.planes = None
+        self.rescore = rescore
         nbytes = ops.topk_index_bytes(self.ntotal, self.dim) if self.ntotal else 0
+        if rescore == "planes":
+            if nbytes == 0 or planes is False:
+                raise ValueError(f"FlatIndex(rescore=\"planes\") needs the planes: a [{self.ntotal}, {self.dim}] database "
+                                 f"{'has none (dim % 16)' if nbytes == 0 else 'was given planes=False'}")
+            planes = True
         if planes == "auto":
             planes = nbytes > 0 and torch.cuda.mem_get_info(dev)[0] > nbytes + (8 << 30)
         if planes:
@@ -77,8 +91,49 @@ class FlatIndex:
         metric = "ip" if self.method == "cosine" else "l2"
         if self.planes is not None and (self.db is None or
                                         _lib.load().anyloc_topk_path(int(qu_d.shape[0]), self.ntotal, self.dim) == 2):
-            return ops.topk_indexed(qu_d, self.planes, self.ntotal, int(k), metric, normalize_db=self.norm_descs, db=self.db)
+            return ops.topk_indexed(qu_d, self.planes, self.ntotal, int(k), metric, normalize_db=self.norm_descs, db=self.db,
+                                    rescore_planes=self.rescore == "planes")
         return ops.topk(qu_d, self.db, int(k), metric, normalize_db=self.norm_descs)
+
+    @classmethod
+    def from_chunks(cls, chunks, ntotal, dim, method="cosine", norm_descs=True):
+        """A rows-free index (``rescore="planes"``, ``db is None``) of an ``ntotal`` x ``dim`` database that arrives as an
+        iterable of ``[n_i, dim]`` tensors (CPU or GPU, any lengths, ``sum n_i == ntotal``) -- faiss' ``index.add`` called
+        chunk by chunk (reference ``utilities.py:441-442, :446-447``).  The rows are staged one panel at a time
+        (``ops.topk_index_panel(dim)`` rows: 1.6 GB at 49 152 columns) and quantised into the index
+        (``ops.topk_index_build_range``): the ``ntotal`` fp32 rows never exist on the device together.  Bit for bit the index
+        ``FlatIndex(db, ..., keep_fp32=False, rescore="planes")`` builds of the whole database."""
+        if method not in ("cosine", "l2"):
+            raise NotImplementedError(f"Method: {method}")
+        dev = _lib.require_gpu()
+        ntotal, dim = int(ntotal), int(dim)
+        nbytes = ops.topk_index_bytes(ntotal, dim) if ntotal > 0 else 0
+        if nbytes == 0:
+            raise ValueError(f"FlatIndex.from_chunks: a [{ntotal}, {dim}] database has no planes (dim % 16, at least one row)")
+        panel = ops.topk_index_panel(dim)
+        self = cls.__new__(cls)
+        self.method, self.norm_descs = method, bool(norm_descs)
+        self.db, self.ntotal, self.dim, self.rescore = None, ntotal, dim, "planes"
+        self.planes = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        stage = torch.empty(min(panel, ntotal), dim, dtype=torch.float32, device=dev)
+        done = fill = 0                                   # rows quantised; rows waiting in the stage
+        for chunk in chunks:
+            chunk = torch.as_tensor(chunk)
+            if chunk.dim() != 2 or chunk.shape[1] != dim:
+                raise ValueError(f"FlatIndex.from_chunks: chunk {tuple(chunk.shape)} is not [n, {dim}]")
+            if done + fill + chunk.shape[0] > ntotal:
+                raise ValueError(f"FlatIndex.from_chunks: more than ntotal = {ntotal} rows")
+            c0 = 0
+            while c0 < chunk.shape[0]:
+                take = min(chunk.shape[0] - c0, stage.shape[0] - fill)
+                stage[fill:fill + take].copy_(chunk[c0:c0 + take])
+                fill, c0 = fill + take, c0 + take
+                if fill == stage.shape[0] or done + fill == ntotal:
+                    ops.topk_index_build_range(self.planes, stage[:fill], done, ntotal)
+                    done, fill = done + fill, 0
+        if done != ntotal:
+            raise ValueError(f"FlatIndex.from_chunks: the chunks hold {done + fill} rows, ntotal = {ntotal}")
+        return self
 
 
 def search(db, qu, k, method="cosine", norm_descs=True):

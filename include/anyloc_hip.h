@@ -380,6 +380,28 @@ int anyloc_topk_search_index(const float* queries, int64_t nq, const void* index
 int anyloc_topk_search_index_rows(const float* queries, int64_t nq, const float* db, const void* index, int64_t ndb, int64_t dim,
                                   int64_t k, int metric, unsigned flags, int64_t index_base, float* dist, int64_t* idx,
                                   void* workspace, size_t workspace_bytes, void* stream);
+/* The screened search WITHOUT the fp32 rows (additive to ABI 10; an older library answers the flag with ANYLOC_ERR_INVALID_ARG,
+ * "unknown flags").  replaces: the same `index.search(qu, k)` (utilities.py:450) on the ONE copy of the database faiss keeps
+ * after `index.add` (:441-442 / :446-447, called with the descriptors of :449-450).
+ *   flags: ANYLOC_TOPK_RESCORE_PLANES -- anyloc_topk_search_index and anyloc_topk_search_index_rows only.  The candidates of the
+ *   screened search are re-scored from the two fp16 planes of the index: (hi + lo) 2^-e, the 22-bit rows the index holds and the
+ *   unscreened indexed search scores (every element within 2^-23 of its row's maximum: a normalised score moves by < 1e-8),
+ *   in float64.  `db` is then not needed and not read, so a prepared index costs 4 bytes per element and keeps the screened
+ *   speed; the lists are the float64-exact lists over those rows.  Everything else as above (bound, 512-candidate cap and the
+ *   unscreened search of the same call beyond it, workspace of anyloc_topk_index_workspace_bytes).  anyloc_topk (no index)
+ *   rejects the flag with ANYLOC_ERR_INVALID_ARG. */
+#define ANYLOC_TOPK_RESCORE_PLANES 2u
+/* An index built piece by piece -- `index.add(chunk)` called repeatedly (utilities.py:441-442 / :446-447), for a database whose
+ * fp32 rows never exist in one place (1 M x 49 152 rows are 196.6 GB; rows + index do not fit one device).
+ * anyloc_topk_index_panel: rows per panel of the index for `dim` columns (0 where the fp16 panels do not serve `dim`).
+ * anyloc_topk_index_build_range: quantises database rows [row0, row0 + nrows), given as rows[nrows, dim], into the index of an
+ * `ndb`-row database (a buffer of anyloc_topk_index_bytes(ndb, dim)).  row0 must be a multiple of the panel; nrows a multiple of
+ * the panel, or the range ends at ndb.  It writes exactly what anyloc_topk_index_build writes for those panels (images, 2^-e, sums
+ * of squares, residual norms); anyloc_topk_index_build is this call over [0, ndb).  Ranges may come in any order; the index
+ * is complete once every panel has been written. */
+int64_t anyloc_topk_index_panel(int64_t dim);
+int anyloc_topk_index_build_range(const float* rows, int64_t row0, int64_t nrows, int64_t ndb, int64_t dim, void* index,
+                                  size_t index_bytes, void* stream);
 
 /* ---------------------------------------------------------------- ViT ----
  * DINOv2 ViT forward with early exit at the last tapped layer.
