@@ -401,6 +401,17 @@ inline int fused_parts(int64_t n_img, int64_t total) {
 // option vlad_two_pass = 1 selects the two-pass path even where the fused kernel applies (A/B tests)
 inline bool two_pass_forced() { return option(OPT_VLAD_TWO_PASS) != 0; }
 
+// The workgroups-per-image decision of a hard-VLAD call; asked: the caller's ANYLOC_VLAD_PARTS count (0 = ours).  run: what
+// the call launches with -- the caller's count when it gave one, else ours; 1 on the two-pass path.  sized: what the size
+// functions carve for -- the larger of ours and the caller's (clipped to 64), whatever option vlad_two_pass says.
+struct PartsPlan { bool fused; int run, sized; };
+PartsPlan plan_parts(int64_t D, int64_t K, int64_t n_img, int64_t total, int asked) {
+  if (!fused_supported(D, K) || n_img <= 0) return {false, 1, 1};
+  const int own = fused_parts(n_img, total), sized = asked > own ? std::min(asked, 64) : own;
+  if (two_pass_forced()) return {false, 1, sized};
+  return {true, asked > 0 ? asked : own, sized};
+}
+
 struct VladWs {
   float *chat, *cb, *scores, *rowsq, *nrm;
   int* lab32;
@@ -410,7 +421,7 @@ struct VladWs {
 };
 VladWs carve(void* ws, size_t cap, int64_t n, int64_t D, int64_t K, int64_t n_img = 0, int parts = 1) {
   Arena a(ws, cap);
-  VladWs w;
+  VladWs w{};
   const int64_t kp = kpad_of(K);
   w.chat = a.take<float>(kp * D);
   w.cb = a.take<float>(kp);
@@ -418,14 +429,30 @@ VladWs carve(void* ws, size_t cap, int64_t n, int64_t D, int64_t K, int64_t n_im
   w.rowsq = a.take<float>(n > 0 ? n : 1);
   w.nrm = a.take<float>(n > 0 ? n : 1);
   w.lab32 = a.take<int>(n > 0 ? n : 1);
-  w.part_buf = nullptr;
-  w.tickets = nullptr;
   if (parts > 1) {
     w.part_buf = a.take<float>(n_img * parts * K * D);
     w.tickets = a.take<unsigned>(n_img);
   }
   w.bytes = a.off;
   return w;
+}
+// anyloc_vlad_assigned keeps the [0, n] offsets of its one image in the first 16 bytes of the (>= 128-byte) bias slot
+inline int64_t* one_image_offsets(const VladWs& w) { return reinterpret_cast<int64_t*>(w.cb); }
+
+int check_workspace(const char* who, const void* ws, size_t have, size_t need) {
+  if (ws && need <= have) return ANYLOC_OK;
+  set_error("%s: workspace %zu < %zu", who, have, need);
+  return ANYLOC_ERR_WORKSPACE;
+}
+
+// ---- one launch site per kernel: each helper owns its kernel's grid, LDS bytes and dynamic-LDS limit; the profiler scopes
+// stay with the callers (the same kernel is tagged in one entry point and untagged in another)
+inline int flag(unsigned flags, unsigned bit) { return (flags & bit) ? 1 : 0; }
+
+int prep_centers(const float* centers, const VladWs& w, int64_t K, int64_t D, int metric, hipStream_t stream) {
+  hipLaunchKernelGGL(center_prep_kernel, dim3((unsigned)kpad_of(K)), dim3(256), 0, stream, centers, w.chat, w.cb, (int)K,
+                     (int)D, metric);
+  return launch_status("center_prep_kernel");
 }
 
 int run_scores(const float* x, int64_t n, int64_t D, const VladWs& w, int64_t K, bool with_bias, hipStream_t stream,
@@ -441,6 +468,84 @@ int run_scores(const float* x, int64_t n, int64_t D, const VladWs& w, int64_t K,
   return gemm_nt(g, EPI_STORE, stream);
 }
 
+int launch_assign(const VladWs& w, int64_t K, int64_t n, int64_t* labels, float* nrm, int norm_descs, hipStream_t stream) {
+  hipLaunchKernelGGL(assign_kernel, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, stream, w.scores, (int)kpad_of(K), (int)K,
+                     w.rowsq, n, w.lab32, labels, nrm, norm_descs);
+  return launch_status("assign_kernel");
+}
+
+// accumulate_kernel keeps K * sl floats in LDS: full-width column slices up to K = 128, half-width up to 256
+inline int acc_slice(int64_t K) { return K > 128 ? SL / 2 : SL; }
+constexpr int ACC_LDS_MAX = 256 * (SL / 2) * (int)sizeof(float);
+constexpr int KMEANS_ACC_LDS_MAX = ACC_LDS_MAX + 256 * (int)sizeof(unsigned);      // + the label histogram
+constexpr int SOFT_ACC_LDS_MAX = 64 * SLS * (int)(sizeof(double) + sizeof(float));  // K <= 64
+static_assert(ACC_LDS_MAX == 131072 && KMEANS_ACC_LDS_MAX == 129 * 1024 && SOFT_ACC_LDS_MAX == 98304, "dynamic-LDS limits");
+
+// hard-assignment sums of n_img images from w.lab32 / w.nrm (offsets: n_img + 1 device entries)
+int launch_accumulate(const float* x, const int64_t* offsets, int64_t n_img, int64_t total, int64_t D, int64_t K,
+                      const VladWs& w, const float* centers, float* out, hipStream_t stream) {
+  static DynLds dyn_lds_once;
+  ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(accumulate_kernel<false>), ACC_LDS_MAX));
+  const int sl = acc_slice(K);
+  const size_t lds = (size_t)K * sl * sizeof(float);
+  // grid.y is limited to 65535: loop over image groups
+  for (int64_t i0 = 0; i0 < n_img; i0 += 65535) {
+    const int64_t cnt = std::min<int64_t>(65535, n_img - i0);
+    hipLaunchKernelGGL(accumulate_kernel<false>, dim3((unsigned)((D + sl - 1) / sl), (unsigned)cnt), dim3(sl), lds, stream, x,
+                       offsets + i0, (int64_t)0, total, (int)D, (int)K, w.lab32, w.nrm, centers, out + i0 * K * D,
+                       (unsigned*)nullptr);
+    ANYLOC_TRY(launch_status("accumulate_kernel"));
+  }
+  return ANYLOC_OK;
+}
+
+// per-chunk sums and label counts of the k-means step: one grid row per chunk of `rows` rows
+int launch_kmeans_accumulate(const float* x, int64_t rows, int64_t chunks, int64_t n, int64_t D, int64_t K, const VladWs& w,
+                             float* part, unsigned* cnt_part, hipStream_t stream) {
+  static DynLds dyn_lds_once;
+  ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(accumulate_kernel<true>), KMEANS_ACC_LDS_MAX));
+  const int sl = acc_slice(K);
+  const size_t lds = (size_t)K * sl * sizeof(float) + (size_t)K * sizeof(unsigned);
+  hipLaunchKernelGGL(accumulate_kernel<true>, dim3((unsigned)((D + sl - 1) / sl), (unsigned)chunks), dim3(sl), lds, stream, x,
+                     (const int64_t*)nullptr, rows, n, (int)D, (int)K, w.lab32, (const float*)nullptr, (const float*)nullptr,
+                     part, cnt_part);
+  return launch_status("accumulate_kernel<kmeans>");
+}
+
+// soft-assignment sums; weights: [*, kpad] rows (the padded scores of soft_scores, or a caller's dense [N, K])
+int launch_soft_accumulate(const float* x, const int64_t* offsets, int64_t n_img, int64_t D, int64_t K, int kpad,
+                           const float* weights, const float* nrm, const float* centers, float* out, hipStream_t stream) {
+  static DynLds dyn_lds_once;
+  ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(soft_accumulate_kernel), SOFT_ACC_LDS_MAX));
+  const size_t lds = (size_t)K * SLS * (sizeof(double) + sizeof(float));
+  for (int64_t i0 = 0; i0 < n_img; i0 += 65535) {
+    const int64_t cnt = std::min<int64_t>(65535, n_img - i0);
+    hipLaunchKernelGGL(soft_accumulate_kernel, dim3((unsigned)((D + SLS - 1) / SLS), (unsigned)cnt), dim3(SLS), lds, stream, x,
+                       offsets + i0, (int)D, (int)K, kpad, weights, nrm, centers, out + i0 * K * D);
+    ANYLOC_TRY(launch_status("soft_accumulate_kernel"));
+  }
+  return ANYLOC_OK;
+}
+
+int launch_finalize(float* out, int64_t n_img, int64_t K, int64_t D, int intra, hipStream_t stream) {
+  hipLaunchKernelGGL(vlad_finalize_kernel, dim3((unsigned)n_img), dim3(1024), 0, stream, out, (int)K, (int)D, intra);
+  return launch_status("vlad_finalize_kernel");
+}
+
+// w.scores[n, kpad] = softmax_k(temp * cos(x_n, c_k)) and w.nrm; the GEMM's W operand: the raw centres padded with zero rows
+int soft_scores(const float* x, int64_t n, int64_t D, const float* centers, int64_t K, float temp, int norm_descs,
+                const VladWs& w, hipStream_t stream) {
+  const int kp = (int)kpad_of(K);
+  ANYLOC_HIP(hipMemsetAsync(w.chat, 0, sizeof(float) * kp * D, stream));
+  ANYLOC_HIP(hipMemcpyAsync(w.chat, centers, sizeof(float) * K * D, hipMemcpyDeviceToDevice, stream));
+  hipLaunchKernelGGL(rowsq_kernel, dim3((unsigned)K), dim3(256), 0, stream, centers, (int)D, w.cb);
+  ANYLOC_TRY(launch_status("rowsq_kernel"));
+  ANYLOC_TRY(run_scores(x, n, D, w, K, false, stream, "vlad_soft_scores_gemm"));
+  hipLaunchKernelGGL(soft_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w.scores, kp, (int)K, w.rowsq,
+                     w.cb, n, temp, w.nrm, norm_descs);
+  return launch_status("soft_weights_kernel");
+}
+
 }  // namespace
 }  // namespace anyloc
 
@@ -449,22 +554,16 @@ using namespace anyloc;
 extern "C" {
 
 size_t anyloc_vlad_workspace_bytes(int64_t total_tokens, int64_t n_img, int64_t D, int64_t K) {
-  const int parts = (fused_supported(D, K) && n_img > 0) ? fused_parts(n_img, total_tokens) : 1;
-  return carve(nullptr, 0, total_tokens, D, K, n_img, parts).bytes + 256;
+  return anyloc_vlad_workspace_bytes_parts(total_tokens, n_img, D, K, 0);
 }
 
 // the same for a call that passes ANYLOC_VLAD_PARTS(parts): sized for the larger of the library's count and the caller's
 size_t anyloc_vlad_workspace_bytes_parts(int64_t total_tokens, int64_t n_img, int64_t D, int64_t K, int32_t parts) {
-  int p = 1;
-  if (fused_supported(D, K) && n_img > 0) {
-    p = fused_parts(n_img, total_tokens);
-    if (parts > p) p = parts > 64 ? 64 : parts;
-  }
-  return carve(nullptr, 0, total_tokens, D, K, n_img, p).bytes + 256;
+  return carve(nullptr, 0, total_tokens, D, K, n_img, plan_parts(D, K, n_img, total_tokens, parts).sized).bytes + 256;
 }
 
 int anyloc_vlad_auto_parts(int64_t total_tokens, int64_t n_img, int64_t D, int64_t K) {
-  return (fused_supported(D, K) && n_img > 0 && !two_pass_forced()) ? fused_parts(n_img, total_tokens) : 1;
+  return plan_parts(D, K, n_img, total_tokens, 0).run;
 }
 
 static int vlad_common_checks(const float* tokens, const int64_t* offsets, int64_t n_img, int64_t total, int64_t D,
@@ -484,75 +583,43 @@ int anyloc_vlad_hard(const float* tokens, const int64_t* offsets, int64_t n_img,
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   ANYLOC_TRY(vlad_common_checks(tokens, offsets, n_img, total_tokens, D, centers, K, out));
   if (n_img == 0) return ANYLOC_OK;
-  const bool fused = fused_supported(D, K) && !two_pass_forced();
   const int asked = (int)((flags >> 8) & 0x7fu);                 // ANYLOC_VLAD_PARTS(p): the caller's count (0 = ours)
   ANYLOC_CHECK_ARG(asked <= 64, "vlad_hard: ANYLOC_VLAD_PARTS(%d) outside 1..64", asked);
-  const int parts = !fused ? 1 : asked > 0 ? asked : fused_parts(n_img, total_tokens);
-  VladWs w = carve(workspace, workspace_bytes, total_tokens, D, K, n_img, parts);
-  if (!workspace || w.bytes > workspace_bytes) {
-    set_error("vlad_hard: workspace %zu < %zu", workspace_bytes, w.bytes);
-    return ANYLOC_ERR_WORKSPACE;
-  }
-  const int kp = (int)kpad_of(K);
+  // The fused kernel wherever it applies (K <= 32, the ViT widths); option vlad_two_pass = 1 selects the general path.
+  const PartsPlan plan = plan_parts(D, K, n_img, total_tokens, asked);
+  VladWs w = carve(workspace, workspace_bytes, total_tokens, D, K, n_img, plan.run);
+  ANYLOC_TRY(check_workspace("vlad_hard", workspace, workspace_bytes, w.bytes));
   // labels = kmeans.predict(tokens) in the metric the vocabulary was built with (reference utilities.py:849 with
   // VLAD(dist_mode=...)): fpk cosine score, or fpk euclidean similarity 2ab - a^2 - b^2 (arg-max = nearest centre)
-  const int metric = (flags & ANYLOC_VLAD_EUCLIDEAN) ? 1 : 0;
-  // The fused kernel wherever it applies (K <= 32, the ViT widths); option vlad_two_pass = 1 selects the general path.
-  if (fused) {
-    // single-pass fused kernel (vlad_fused.hip): tokens are read from HBM once
-    {
-      ProfScope prof("vlad_center_prep", stream, 3.0 * K * D, 8.0 * K * D);
-      hipLaunchKernelGGL(center_prep_kernel, dim3(kp), dim3(256), 0, stream, centers, w.chat, w.cb, (int)K, (int)D, metric);
-      ANYLOC_TRY(launch_status("center_prep_kernel"));
-    }
+  const int metric = flag(flags, ANYLOC_VLAD_EUCLIDEAN), norm_descs = flag(flags, ANYLOC_VLAD_NORM_DESCS);
+  const int intra = flag(flags, ANYLOC_VLAD_INTRA_NORM);
+  if (plan.fused || total_tokens > 0) {            // (the two-pass path has no use for the centres of a call without tokens)
+    ProfScope prof("vlad_center_prep", stream, 3.0 * K * D, 8.0 * K * D);
+    ANYLOC_TRY(prep_centers(centers, w, K, D, metric, stream));
+  }
+  if (plan.fused) {
+    // single-pass fused kernel (vlad_fused.hip): tokens are read from HBM once; it normalises its own result
     FusedArgs fa{};
     fa.x = tokens; fa.offsets = offsets; fa.total = total_tokens;
     fa.D = (int)D; fa.K = (int)K;
     fa.chat = w.chat; fa.cbias = w.cb; fa.centers = centers; fa.metric = metric;
     fa.out = out; fa.lab64 = labels;
-    fa.norm_descs = (flags & ANYLOC_VLAD_NORM_DESCS) ? 1 : 0;
-    fa.intra = (flags & ANYLOC_VLAD_INTRA_NORM) ? 1 : 0;
-    fa.parts = parts; fa.part_buf = w.part_buf; fa.part_tickets = w.tickets;
+    fa.norm_descs = norm_descs; fa.intra = intra;
+    fa.parts = plan.run; fa.part_buf = w.part_buf; fa.part_tickets = w.tickets;
     return vlad_fused(fa, n_img, false, stream);
   }
   if (total_tokens > 0) {
-    {
-      ProfScope prof("vlad_center_prep", stream, 3.0 * K * D, 8.0 * K * D);
-      hipLaunchKernelGGL(center_prep_kernel, dim3(kp), dim3(256), 0, stream, centers, w.chat, w.cb, (int)K, (int)D, metric);
-      ANYLOC_TRY(launch_status("center_prep_kernel"));
-    }
     ANYLOC_TRY(run_scores(tokens, total_tokens, D, w, K, metric == 1, stream, "vlad_scores_gemm"));
-    {
-      ProfScope prof("vlad_assign", stream, 0.0, 4.0 * total_tokens * (kp + 4));
-      hipLaunchKernelGGL(assign_kernel, dim3((unsigned)((total_tokens + 7) / 8)), dim3(256), 0, stream, w.scores,
-                         kp, (int)K, w.rowsq, total_tokens, w.lab32, labels, w.nrm,
-                         (flags & ANYLOC_VLAD_NORM_DESCS) ? 1 : 0);
-      ANYLOC_TRY(launch_status("assign_kernel"));
-    }
+    ProfScope prof("vlad_assign", stream, 0.0, 4.0 * total_tokens * (kpad_of(K) + 4));
+    ANYLOC_TRY(launch_assign(w, K, total_tokens, labels, w.nrm, norm_descs, stream));
   }
   {
-    const int sl = K > 128 ? SL / 2 : SL;           // K up to 256: half-width column slices keep K * sl floats in LDS
-    const size_t lds = (size_t)K * sl * sizeof(float);
-    static DynLds dyn_lds_once;
-    ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(accumulate_kernel<false>), (int)(256 * SL * (int)sizeof(float) / 2)));
     const double bytes = 4.0 * ((double)total_tokens * D + 2.0 * (double)n_img * K * D);
     ProfScope prof("vlad_accumulate", stream, 2.0 * total_tokens * D, bytes);
-    // grid.y is limited to 65535: loop over image groups
-    for (int64_t i0 = 0; i0 < n_img; i0 += 65535) {
-      const int64_t cnt = std::min<int64_t>(65535, n_img - i0);
-      hipLaunchKernelGGL(accumulate_kernel<false>, dim3((unsigned)((D + sl - 1) / sl), (unsigned)cnt), dim3(sl), lds,
-                         stream, tokens, offsets + i0, (int64_t)0, total_tokens, (int)D, (int)K, w.lab32, w.nrm,
-                         centers, out + i0 * K * D, (unsigned*)nullptr);
-      ANYLOC_TRY(launch_status("accumulate_kernel"));
-    }
+    ANYLOC_TRY(launch_accumulate(tokens, offsets, n_img, total_tokens, D, K, w, centers, out, stream));
   }
-  {
-    ProfScope prof("vlad_finalize", stream, 6.0 * n_img * K * D, 12.0 * n_img * K * D);
-    hipLaunchKernelGGL(vlad_finalize_kernel, dim3((unsigned)n_img), dim3(1024), 0, stream, out, (int)K, (int)D,
-                       (flags & ANYLOC_VLAD_INTRA_NORM) ? 1 : 0);
-    ANYLOC_TRY(launch_status("vlad_finalize_kernel"));
-  }
-  return ANYLOC_OK;
+  ProfScope prof("vlad_finalize", stream, 6.0 * n_img * K * D, 12.0 * n_img * K * D);
+  return launch_finalize(out, n_img, K, D, intra, stream);
 }
 
 int anyloc_vlad_soft(const float* tokens, const int64_t* offsets, int64_t n_img, int64_t total_tokens, int64_t D,
@@ -563,41 +630,15 @@ int anyloc_vlad_soft(const float* tokens, const int64_t* offsets, int64_t n_img,
   if (n_img == 0) return ANYLOC_OK;
   ANYLOC_CHECK_ARG(K <= 64, "vlad_soft: num_clusters %lld > 64 unsupported", (long long)K);
   VladWs w = carve(workspace, workspace_bytes, total_tokens, D, K);
-  if (!workspace || w.bytes > workspace_bytes) {
-    set_error("vlad_soft: workspace %zu < %zu", workspace_bytes, w.bytes);
-    return ANYLOC_ERR_WORKSPACE;
-  }
-  const int kp = (int)kpad_of(K);
-  if (total_tokens > 0) {
-    // raw centres padded with zero rows as the GEMM's W operand; cb holds ||c_k||^2
-    ANYLOC_HIP(hipMemsetAsync(w.chat, 0, sizeof(float) * kp * D, stream));
-    ANYLOC_HIP(hipMemcpyAsync(w.chat, centers, sizeof(float) * K * D, hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(rowsq_kernel, dim3((unsigned)K), dim3(256), 0, stream, centers, (int)D, w.cb);
-    ANYLOC_TRY(launch_status("rowsq_kernel"));
-    ANYLOC_TRY(run_scores(tokens, total_tokens, D, w, K, false, stream, "vlad_soft_scores_gemm"));
-    hipLaunchKernelGGL(soft_weights_kernel, dim3((unsigned)((total_tokens + 255) / 256)), dim3(256), 0, stream,
-                       w.scores, kp, (int)K, w.rowsq, w.cb, total_tokens, soft_temp, w.nrm,
-                       (flags & ANYLOC_VLAD_NORM_DESCS) ? 1 : 0);
-    ANYLOC_TRY(launch_status("soft_weights_kernel"));
-  }
+  ANYLOC_TRY(check_workspace("vlad_soft", workspace, workspace_bytes, w.bytes));
+  if (total_tokens > 0)
+    ANYLOC_TRY(soft_scores(tokens, total_tokens, D, centers, K, soft_temp, flag(flags, ANYLOC_VLAD_NORM_DESCS), w, stream));
   {
-    const size_t lds = (size_t)K * SLS * (sizeof(double) + sizeof(float));
-    static DynLds dyn_lds_once;
-    ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(soft_accumulate_kernel), (int)(64 * SLS * 12)));
     ProfScope prof("vlad_soft_accumulate", stream, 2.0 * total_tokens * D * K * K, 4.0 * total_tokens * D);
-    for (int64_t i0 = 0; i0 < n_img; i0 += 65535) {
-      const int64_t cnt = std::min<int64_t>(65535, n_img - i0);
-      hipLaunchKernelGGL(soft_accumulate_kernel, dim3((unsigned)((D + SLS - 1) / SLS), (unsigned)cnt), dim3(SLS), lds,
-                         stream, tokens, offsets + i0, (int)D, (int)K, kp, w.scores, w.nrm, centers,
-                         out + i0 * K * D);
-      ANYLOC_TRY(launch_status("soft_accumulate_kernel"));
-    }
+    ANYLOC_TRY(launch_soft_accumulate(tokens, offsets, n_img, D, K, (int)kpad_of(K), w.scores, w.nrm, centers, out, stream));
   }
-  hipLaunchKernelGGL(vlad_finalize_kernel, dim3((unsigned)n_img), dim3(1024), 0, stream, out, (int)K, (int)D,
-                     (flags & ANYLOC_VLAD_INTRA_NORM) ? 1 : 0);
-  return launch_status("vlad_finalize_kernel");
+  return launch_finalize(out, n_img, K, D, flag(flags, ANYLOC_VLAD_INTRA_NORM), stream);
 }
-
 
 int anyloc_vlad_soft_weights(const float* tokens, int64_t n_tok, int64_t D, const float* centers, int64_t K, float soft_temp,
                              float* weights, void* workspace, size_t workspace_bytes, void* stream_) {
@@ -606,21 +647,10 @@ int anyloc_vlad_soft_weights(const float* tokens, int64_t n_tok, int64_t D, cons
   ANYLOC_CHECK_ARG(n_tok >= 0 && K >= 1 && K <= 64 && D >= 4 && D % 4 == 0, "vlad_soft_weights: bad shape (K <= 64)");
   if (n_tok == 0) return ANYLOC_OK;
   VladWs w = carve(workspace, workspace_bytes, n_tok, D, K);
-  if (!workspace || w.bytes > workspace_bytes) {
-    set_error("vlad_soft_weights: workspace %zu < %zu", workspace_bytes, w.bytes);
-    return ANYLOC_ERR_WORKSPACE;
-  }
-  const int kp = (int)kpad_of(K);
-  ANYLOC_HIP(hipMemsetAsync(w.chat, 0, sizeof(float) * kp * D, stream));
-  ANYLOC_HIP(hipMemcpyAsync(w.chat, centers, sizeof(float) * K * D, hipMemcpyDeviceToDevice, stream));
-  hipLaunchKernelGGL(rowsq_kernel, dim3((unsigned)K), dim3(256), 0, stream, centers, (int)D, w.cb);
-  ANYLOC_TRY(launch_status("rowsq_kernel"));
-  ANYLOC_TRY(run_scores(tokens, n_tok, D, w, K, false, stream, "vlad_soft_scores_gemm"));
-  hipLaunchKernelGGL(soft_weights_kernel, dim3((unsigned)((n_tok + 255) / 256)), dim3(256), 0, stream, w.scores, kp, (int)K,
-                     w.rowsq, w.cb, n_tok, soft_temp, w.nrm, 0);
-  ANYLOC_TRY(launch_status("soft_weights_kernel"));
-  ANYLOC_HIP(hipMemcpy2DAsync(weights, sizeof(float) * K, w.scores, sizeof(float) * kp, sizeof(float) * K, (size_t)n_tok,
-                              hipMemcpyDeviceToDevice, stream));
+  ANYLOC_TRY(check_workspace("vlad_soft_weights", workspace, workspace_bytes, w.bytes));
+  ANYLOC_TRY(soft_scores(tokens, n_tok, D, centers, K, soft_temp, 0, w, stream));
+  ANYLOC_HIP(hipMemcpy2DAsync(weights, sizeof(float) * K, w.scores, sizeof(float) * kpad_of(K), sizeof(float) * K,
+                              (size_t)n_tok, hipMemcpyDeviceToDevice, stream));
   return ANYLOC_OK;
 }
 
@@ -632,10 +662,11 @@ int anyloc_vlad_residuals(const float* tokens, int64_t n_tok, int64_t D, const f
   if (n_tok == 0) return ANYLOC_OK;
   ProfScope prof("vlad_residuals", stream, (double)n_tok * K * D, 4.0 * ((double)n_tok * D * (K + 1) + (double)K * D));
   hipLaunchKernelGGL(residuals_kernel, dim3((unsigned)n_tok), dim3(256), 0, stream, tokens, (int)D, (int)K, centers,
-                     (flags & ANYLOC_VLAD_NORM_DESCS) ? 1 : 0, out);
+                     flag(flags, ANYLOC_VLAD_NORM_DESCS), out);
   return launch_status("residuals_kernel");
 }
 
+// the one-image case of the accumulate helpers, from a GIVEN assignment; no profiler scopes
 int anyloc_vlad_assigned(const float* tokens, int64_t n_tok, int64_t D, const float* centers, int64_t K,
                          const int64_t* labels, const float* soft_weights, unsigned flags, float* out, void* workspace,
                          size_t workspace_bytes, void* stream_) {
@@ -645,38 +676,20 @@ int anyloc_vlad_assigned(const float* tokens, int64_t n_tok, int64_t D, const fl
   ANYLOC_CHECK_ARG(n_tok >= 0 && n_tok < (1ll << 31) && K >= 1 && K <= 256 && D >= 4 && D % 4 == 0, "vlad_assigned: bad shape");
   ANYLOC_CHECK_ARG(labels || K <= 64, "vlad_assigned: soft weights need K <= 64");
   VladWs w = carve(workspace, workspace_bytes, n_tok, D, K);
-  if (!workspace || w.bytes > workspace_bytes) {
-    set_error("vlad_assigned: workspace %zu < %zu", workspace_bytes, w.bytes);
-    return ANYLOC_ERR_WORKSPACE;
-  }
-  int64_t* offsets = reinterpret_cast<int64_t*>(w.cb);        // 16 bytes of the (>= 128-byte) bias slot
+  ANYLOC_TRY(check_workspace("vlad_assigned", workspace, workspace_bytes, w.bytes));
   if (n_tok == 0) {
     ANYLOC_HIP(hipMemsetAsync(out, 0, sizeof(float) * K * D, stream));
     return ANYLOC_OK;
   }
-  const int norm = (flags & ANYLOC_VLAD_NORM_DESCS) ? 1 : 0;
-  hipLaunchKernelGGL(assigned_prep_kernel, dim3((unsigned)n_tok), dim3(256), 0, stream, tokens, (int)D, n_tok, (int)K, labels, norm,
-                     w.nrm, w.lab32, offsets);
+  int64_t* offsets = one_image_offsets(w);
+  hipLaunchKernelGGL(assigned_prep_kernel, dim3((unsigned)n_tok), dim3(256), 0, stream, tokens, (int)D, n_tok, (int)K, labels,
+                     flag(flags, ANYLOC_VLAD_NORM_DESCS), w.nrm, w.lab32, offsets);
   ANYLOC_TRY(launch_status("assigned_prep_kernel"));
-  if (labels) {
-    const int sl = K > 128 ? SL / 2 : SL;
-    const size_t lds = (size_t)K * sl * sizeof(float);
-    ANYLOC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(accumulate_kernel<false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 256 * SL * (int)sizeof(float) / 2));
-    hipLaunchKernelGGL(accumulate_kernel<false>, dim3((unsigned)((D + sl - 1) / sl), 1u), dim3(sl), lds, stream, tokens, offsets,
-                       (int64_t)0, n_tok, (int)D, (int)K, w.lab32, w.nrm, centers, out, (unsigned*)nullptr);
-    ANYLOC_TRY(launch_status("accumulate_kernel"));
-  } else {
-    const size_t lds = (size_t)K * SLS * (sizeof(double) + sizeof(float));
-    ANYLOC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(soft_accumulate_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 64 * SLS * 12));
-    hipLaunchKernelGGL(soft_accumulate_kernel, dim3((unsigned)((D + SLS - 1) / SLS), 1u), dim3(SLS), lds, stream, tokens, offsets,
-                       (int)D, (int)K, (int)K, soft_weights, w.nrm, centers, out);
-    ANYLOC_TRY(launch_status("soft_accumulate_kernel"));
-  }
-  hipLaunchKernelGGL(vlad_finalize_kernel, dim3(1u), dim3(1024), 0, stream, out, (int)K, (int)D,
-                     (flags & ANYLOC_VLAD_INTRA_NORM) ? 1 : 0);
-  return launch_status("vlad_finalize_kernel");
+  if (labels)
+    ANYLOC_TRY(launch_accumulate(tokens, offsets, 1, n_tok, D, K, w, centers, out, stream));
+  else       // the caller's weights are dense [N, K]: row stride K, not the padded kpad
+    ANYLOC_TRY(launch_soft_accumulate(tokens, offsets, 1, D, K, (int)K, soft_weights, w.nrm, centers, out, stream));
+  return launch_finalize(out, 1, K, D, flag(flags, ANYLOC_VLAD_INTRA_NORM), stream);
 }
 
 // ------------------------------------------------------------------ k-means
@@ -701,13 +714,21 @@ static int64_t kmeans_chunk_rows(int64_t n) {
   return rows < 1024 ? 1024 : rows;
 }
 
-size_t anyloc_kmeans_workspace_bytes(int64_t n, int64_t D, int64_t K) {
-  size_t b = carve(nullptr, 0, n, D, K).bytes;
-  const int64_t rows = kmeans_chunk_rows(n), chunks = (n + rows - 1) / rows;
-  b += align_up((size_t)(chunks > 0 ? chunks : 1) * K * D * sizeof(float), 256);
-  b += align_up((size_t)(chunks > 0 ? chunks : 1) * K * sizeof(unsigned), 256);
-  return b + 256;
+// the VLAD slots, then one partial [K, D] sum and one [K] label histogram per chunk: the size function and the step both
+// carve with this
+struct KmeansWs : VladWs { int64_t rows, chunks; float* part; unsigned* cnt_part; };
+static KmeansWs carve_kmeans(void* ws, size_t cap, int64_t n, int64_t D, int64_t K) {
+  KmeansWs k{carve(ws, cap, n, D, K)};
+  k.rows = kmeans_chunk_rows(n);
+  k.chunks = std::max<int64_t>(1, (n + k.rows - 1) / k.rows);
+  Arena tail(static_cast<char*>(ws) + k.bytes, 0);
+  k.part = tail.take<float>(k.chunks * K * D);
+  k.cnt_part = tail.take<unsigned>(k.chunks * K);
+  k.bytes += tail.off;
+  return k;
 }
+
+size_t anyloc_kmeans_workspace_bytes(int64_t n, int64_t D, int64_t K) { return carve_kmeans(nullptr, 0, n, D, K).bytes + 256; }
 
 int anyloc_kmeans_update(const float* sums, const float* counts, const float* centers_old, int64_t K, int64_t D,
                          float* centers_new, double* err, void* stream_) {
@@ -719,6 +740,18 @@ int anyloc_kmeans_update(const float* sums, const float* counts, const float* ce
   return launch_status("kmeans_update_kernel");
 }
 
+// sums and counts from the per-chunk partials, in chunk order: the tail of both paths of the step
+static int reduce_partials(const KmeansWs& k, int64_t K, int64_t D, float* sums, float* counts, hipStream_t stream) {
+  {
+    ProfScope prof("kmeans_reduce", stream, 1.0 * k.chunks * K * D, 4.0 * (k.chunks + 1.0) * K * D);
+    hipLaunchKernelGGL(reduce_chunks_kernel, dim3((unsigned)((K * D + 255) / 256)), dim3(256), 0, stream, k.part, k.chunks,
+                       K * D, sums);
+    ANYLOC_TRY(launch_status("reduce_chunks_kernel"));
+  }
+  hipLaunchKernelGGL(reduce_counts_kernel, dim3((unsigned)K), dim3(64), 0, stream, k.cnt_part, k.chunks, (int)K, counts);
+  return launch_status("reduce_counts_kernel");
+}
+
 int anyloc_kmeans_step(const float* x, int64_t n, int64_t D, const float* centers, int64_t K, int mode, float* sums,
                        float* counts, int64_t* labels, void* workspace, size_t workspace_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -727,62 +760,26 @@ int anyloc_kmeans_step(const float* x, int64_t n, int64_t D, const float* center
   ANYLOC_CHECK_ARG(K >= 1 && K <= 256, "kmeans_step: K %lld outside [1,256]", (long long)K);
   ANYLOC_CHECK_ARG(D >= 4 && D % 4 == 0, "kmeans_step: D %lld must be a positive multiple of 4", (long long)D);
   ANYLOC_CHECK_ARG(mode == 0 || mode == 1, "kmeans_step: mode %d", mode);
-  const size_t need = anyloc_kmeans_workspace_bytes(n, D, K);
-  if (!workspace || need > workspace_bytes) {
-    set_error("kmeans_step: workspace %zu < %zu", workspace_bytes, need);
-    return ANYLOC_ERR_WORKSPACE;
-  }
-  VladWs w = carve(workspace, workspace_bytes, n, D, K);
-  Arena tail(static_cast<char*>(workspace) + w.bytes, workspace_bytes - w.bytes);
-  const int64_t rows = kmeans_chunk_rows(n), chunks = (n + rows - 1) / rows;
-  float* part = tail.take<float>(chunks * K * D);
-  unsigned* cnt_part = tail.take<unsigned>(chunks * K);
-  const int kp = (int)kpad_of(K);
-
-  hipLaunchKernelGGL(center_prep_kernel, dim3(kp), dim3(256), 0, stream, centers, w.chat, w.cb, (int)K, (int)D, mode);
-  ANYLOC_TRY(launch_status("center_prep_kernel"));
+  const KmeansWs k = carve_kmeans(workspace, workspace_bytes, n, D, K);
+  ANYLOC_TRY(check_workspace("kmeans_step", workspace, workspace_bytes, k.bytes + 256));   // = anyloc_kmeans_workspace_bytes
+  ANYLOC_TRY(prep_centers(centers, k, K, D, mode, stream));
   if (fused_supported(D, K) && !two_pass_forced()) {
     FusedArgs fa{};
-    fa.x = x; fa.chunk_rows = rows; fa.total = n;
+    fa.x = x; fa.chunk_rows = k.rows; fa.total = n;
     fa.D = (int)D; fa.K = (int)K;
-    fa.chat = w.chat; fa.cbias = w.cb; fa.metric = mode;
-    fa.out = part; fa.cnt_part = cnt_part; fa.lab64 = labels;
-    ANYLOC_TRY(vlad_fused(fa, chunks, true, stream));
+    fa.chat = k.chat; fa.cbias = k.cb; fa.metric = mode;
+    fa.out = k.part; fa.cnt_part = k.cnt_part; fa.lab64 = labels;
+    ANYLOC_TRY(vlad_fused(fa, k.chunks, true, stream));
+  } else {
+    ANYLOC_TRY(run_scores(x, n, D, k, K, mode == 1, stream, "kmeans_scores_gemm"));
     {
-      ProfScope prof("kmeans_reduce", stream, 1.0 * chunks * K * D, 4.0 * (chunks + 1.0) * K * D);
-      hipLaunchKernelGGL(reduce_chunks_kernel, dim3((unsigned)((K * D + 255) / 256)), dim3(256), 0, stream, part,
-                         chunks, K * D, sums);
-      ANYLOC_TRY(launch_status("reduce_chunks_kernel"));
+      ProfScope prof("kmeans_assign", stream, 0.0, 4.0 * n * (kpad_of(K) + 2));
+      ANYLOC_TRY(launch_assign(k, K, n, labels, nullptr, 0, stream));
     }
-    hipLaunchKernelGGL(reduce_counts_kernel, dim3((unsigned)K), dim3(64), 0, stream, cnt_part, chunks, (int)K, counts);
-    return launch_status("reduce_counts_kernel");
+    ProfScope prof("kmeans_accumulate", stream, 1.0 * n * D, 4.0 * ((double)n * D + (double)k.chunks * K * D));
+    ANYLOC_TRY(launch_kmeans_accumulate(x, k.rows, k.chunks, n, D, K, k, k.part, k.cnt_part, stream));
   }
-  ANYLOC_TRY(run_scores(x, n, D, w, K, mode == 1, stream, "kmeans_scores_gemm"));
-  {
-    ProfScope prof("kmeans_assign", stream, 0.0, 4.0 * n * (kp + 2));
-    hipLaunchKernelGGL(assign_kernel, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, stream, w.scores, kp, (int)K,
-                       w.rowsq, n, w.lab32, labels, (float*)nullptr, 0);
-    ANYLOC_TRY(launch_status("assign_kernel"));
-  }
-  {
-    const int sl = K > 128 ? SL / 2 : SL;
-    const size_t lds = (size_t)K * sl * sizeof(float) + (size_t)K * sizeof(unsigned);
-    static DynLds dyn_lds_once;
-    ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(accumulate_kernel<true>), (int)(129 * 1024)));
-    ProfScope prof("kmeans_accumulate", stream, 1.0 * n * D, 4.0 * ((double)n * D + (double)chunks * K * D));
-    hipLaunchKernelGGL(accumulate_kernel<true>, dim3((unsigned)((D + sl - 1) / sl), (unsigned)chunks), dim3(sl), lds,
-                       stream, x, (const int64_t*)nullptr, rows, n, (int)D, (int)K, w.lab32, (const float*)nullptr,
-                       (const float*)nullptr, part, cnt_part);
-    ANYLOC_TRY(launch_status("accumulate_kernel<kmeans>"));
-  }
-  {
-    ProfScope prof("kmeans_reduce", stream, 1.0 * chunks * K * D, 4.0 * (chunks + 1.0) * K * D);
-    hipLaunchKernelGGL(reduce_chunks_kernel, dim3((unsigned)((K * D + 255) / 256)), dim3(256), 0, stream, part, chunks,
-                       K * D, sums);
-    ANYLOC_TRY(launch_status("reduce_chunks_kernel"));
-  }
-  hipLaunchKernelGGL(reduce_counts_kernel, dim3((unsigned)K), dim3(64), 0, stream, cnt_part, chunks, (int)K, counts);
-  return launch_status("reduce_counts_kernel");
+  return reduce_partials(k, K, D, sums, counts, stream);
 }
 
 }  // extern "C"

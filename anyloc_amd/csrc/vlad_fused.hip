@@ -1102,10 +1102,27 @@ __global__ __launch_bounds__(64 * SW) void fused3_kernel(FusedArgs a) {
 
 #undef x_rsrc
 
+// What the launches of both kernels share: the dynamic-LDS limit (dyn: the memo of this kernel instantiation), the profiler
+// figures, the ticket reset and grid scale-up of a VLAD launch with several workgroups per image, launch and status.
+using FusedKernel = void (*)(FusedArgs);
+int launch_units(FusedKernel kern, DynLds& dyn, int block, size_t lds, const char* what, bool kmeans, const FusedArgs& a,
+                 int64_t units, hipStream_t stream) {
+  ANYLOC_TRY(ensure_dyn_lds(dyn, reinterpret_cast<const void*>(kern), (int)lds));
+  ProfScope prof(kmeans ? "kmeans_fused" : "vlad_fused", stream, 2.0 * a.total * a.D * 32,
+                 4.0 * ((double)a.total * a.D + 2.0 * (double)units * a.K * a.D));
+  unsigned grid = (unsigned)units;
+  if (!kmeans && a.parts > 1) {
+    ANYLOC_CHECK_ARG(a.part_buf && a.part_tickets, "vlad_fused: parts without a partials buffer");
+    ANYLOC_HIP(hipMemsetAsync(a.part_tickets, 0, sizeof(unsigned) * units, stream));
+    grid = (unsigned)(units * a.parts);
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, stream, a);
+  return launch_status(what);
+}
+
 template <int NV, int SW, bool KMEANS, int GV = 0>
 int launch_fused3(const FusedArgs& a, int64_t units, hipStream_t stream) {
   constexpr int D = NV * 128;
-  const size_t lds = sizeof(float) * (TT * (D + 4) + SW * TT * 32 + SW * TT + TT + TT + TT + SW * 32 + 4 + TT * 32);
   if constexpr (NV == 12 && SW == 8 && !KMEANS && GV == 0) {
     switch ((int)option(OPT_VLAD_GATHER_V)) {                 // hazard study (tools/stress_vlad.py): see fused3_kernel
       case 1: return launch_fused3<NV, SW, KMEANS, 1>(a, units, stream);
@@ -1121,39 +1138,33 @@ int launch_fused3(const FusedArgs& a, int64_t units, hipStream_t stream) {
       default: break;
     }
   }
-  auto kern = fused3_kernel<NV, SW, KMEANS, GV>;
   static DynLds dyn_lds_once;
-  ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(kern), (int)((int)lds)));
-  ProfScope prof(KMEANS ? "kmeans_fused" : "vlad_fused", stream, 2.0 * a.total * D * 32,
-                 4.0 * ((double)a.total * D + 2.0 * (double)units * a.K * D));
-  unsigned grid = (unsigned)units;
-  if (!KMEANS && a.parts > 1) {
-    ANYLOC_CHECK_ARG(a.part_buf && a.part_tickets, "vlad_fused: parts without a partials buffer");
-    ANYLOC_HIP(hipMemsetAsync(a.part_tickets, 0, sizeof(unsigned) * units, stream));
-    grid = (unsigned)(units * a.parts);
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * SW), lds, stream, a);
-  return launch_status("fused3_kernel");
+  return launch_units(fused3_kernel<NV, SW, KMEANS, GV>, dyn_lds_once, 64 * SW,
+                      sizeof(float) * (TT * (D + 4) + SW * TT * 32 + SW * TT + TT + TT + TT + SW * 32 + 4 + TT * 32),
+                      "fused3_kernel", KMEANS, a, units, stream);
 }
 
 template <int NV, bool KMEANS>
 int launch_fused(const FusedArgs& a, int64_t units, hipStream_t stream) {
   constexpr int D = NV * 128;
   constexpr int SW = 8;
-  const size_t lds = sizeof(float) * (TT * (D + 4) + SW * TT * 32 + SW * TT + TT + TT + 32);
-  auto kern = vlad_fused_kernel<NV, KMEANS>;
   static DynLds dyn_lds_once;
-  ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(kern), (int)((int)lds)));
-  const double bytes = 4.0 * ((double)a.total * D + 2.0 * (double)units * a.K * D);
-  ProfScope prof(KMEANS ? "kmeans_fused" : "vlad_fused", stream, 2.0 * a.total * D * 32, bytes);
-  unsigned grid = (unsigned)units;
-  if (!KMEANS && a.parts > 1) {
-    ANYLOC_CHECK_ARG(a.part_buf && a.part_tickets, "vlad_fused: parts without a partials buffer");
-    ANYLOC_HIP(hipMemsetAsync(a.part_tickets, 0, sizeof(unsigned) * units, stream));
-    grid = (unsigned)(units * a.parts);
+  return launch_units(vlad_fused_kernel<NV, KMEANS>, dyn_lds_once, NTH,
+                      sizeof(float) * (TT * (D + 4) + SW * TT * 32 + SW * TT + TT + TT + 32), "vlad_fused_kernel", KMEANS, a,
+                      units, stream);
+}
+
+// options kmeans_fused_v / vlad_fused_v (A/B, tests): 0 (default) = fused3_kernel -- 8 waves where D / 128 is even, 4 waves
+// otherwise -- at every parts count (round 4: with the CW-wide hand-off 0.135 vs 0.154 ms at 61 images x 4 parts);
+// 1 = vlad_fused_kernel (both modes), 3 = fused3 with 4 waves, 4 = fused3 with 8
+template <int NV>
+int launch_version(const FusedArgs& a, int64_t units, bool kmeans, hipStream_t stream) {
+  const int ver = (int)option(kmeans ? OPT_KMEANS_FUSED_V : OPT_VLAD_FUSED_V);
+  if (ver != 0 && ver < 3) return kmeans ? launch_fused<NV, true>(a, units, stream) : launch_fused<NV, false>(a, units, stream);
+  if constexpr (NV % 2 == 0) {
+    if (ver != 3) return kmeans ? launch_fused3<NV, 8, true>(a, units, stream) : launch_fused3<NV, 8, false>(a, units, stream);
   }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NTH), lds, stream, a);
-  return launch_status("vlad_fused_kernel");
+  return kmeans ? launch_fused3<NV, 4, true>(a, units, stream) : launch_fused3<NV, 4, false>(a, units, stream);
 }
 
 }  // namespace
@@ -1165,31 +1176,15 @@ bool fused_supported(int64_t D, int64_t K) {
 int vlad_fused(const FusedArgs& a, int64_t units, bool kmeans, hipStream_t stream) {
   if (units <= 0) return ANYLOC_OK;
   ANYLOC_CHECK_ARG(units < (1ll << 31), "vlad_fused: too many units");
-  // options kmeans_fused_v / vlad_fused_v (A/B, tests): 0 (default) = fused3_kernel -- 8 waves where D / 128 is even, 4 waves
-  // otherwise -- at every parts count (round 4: with the CW-wide hand-off 0.135 vs 0.154 ms at 61 images x 4 parts);
-  // 1 = vlad_fused_kernel (both modes), 3 = fused3 with 4 waves, 4 = fused3 with 8
-  const int ver = (int)option(kmeans ? OPT_KMEANS_FUSED_V : OPT_VLAD_FUSED_V);
-  const bool f3 = ver == 0 ? true : ver >= 3;
-#define ANYLOC_FUSED_CASE(NV)                                                                         \
-  case NV * 128:                                                                                      \
-    if (f3) {                                                                                         \
-      if constexpr (NV % 2 == 0) {                                                                    \
-        if (ver != 3)                                                                                 \
-          return kmeans ? launch_fused3<NV, 8, true>(a, units, stream) : launch_fused3<NV, 8, false>(a, units, stream); \
-      }                                                                                               \
-      return kmeans ? launch_fused3<NV, 4, true>(a, units, stream) : launch_fused3<NV, 4, false>(a, units, stream);     \
-    }                                                                                                 \
-    return kmeans ? launch_fused<NV, true>(a, units, stream) : launch_fused<NV, false>(a, units, stream);
   switch (a.D) {
-    ANYLOC_FUSED_CASE(3)
-    ANYLOC_FUSED_CASE(6)
-    ANYLOC_FUSED_CASE(8)
-    ANYLOC_FUSED_CASE(12)
+    case 384: return launch_version<3>(a, units, kmeans, stream);
+    case 768: return launch_version<6>(a, units, kmeans, stream);
+    case 1024: return launch_version<8>(a, units, kmeans, stream);
+    case 1536: return launch_version<12>(a, units, kmeans, stream);
     default:
       set_error("vlad_fused: unsupported D=%d", a.D);
       return ANYLOC_ERR_UNSUPPORTED;
   }
-#undef ANYLOC_FUSED_CASE
 }
 
 }  // namespace anyloc
