@@ -285,6 +285,30 @@ __global__ __launch_bounds__(256) void soft_weights_kernel(float* __restrict__ s
   nrm[i] = norm_descs ? fmaxf(sqrtf(rowsq[i]), 1e-12f) : 1.0f;
 }
 
+// scores[n,k] = x_n . c_k (raw centres) and rowsq[n] = ||x_n||^2 for the soft-max: one block per token, wave w takes the
+// centres w, w + 4, ...; every lane sums D / 64 products, then a 64-lane tree.  The soft-max multiplies the cosine's error
+// by up to temp / 4, and the fp32 MFMA GEMM of the hard path adds its D / 2 partial products one after the other
+// (~1.4e-6 of a cosine at D = 1536, 3 ... 6 times the reference's own error): fine for an arg-max, not for these weights.
+__global__ __launch_bounds__(256) void soft_dots_kernel(const float* __restrict__ x, const float* __restrict__ c, int D, int K,
+                                                        int kpad, float* __restrict__ scores, float* __restrict__ rowsq) {
+  const int64_t n = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* r = x + n * D;
+  if (wave == 0) {
+    float ss = 0.f;
+    for (int i = lane; i < D; i += 64) ss += r[i] * r[i];
+    ss = wave_sum(ss);
+    if (lane == 0) rowsq[n] = ss;
+  }
+  for (int k = wave; k < K; k += 4) {
+    const float* ck = c + (int64_t)k * D;
+    float s = 0.f;
+    for (int i = lane; i < D; i += 64) s += r[i] * ck[i];
+    s = wave_sum(s);
+    if (lane == 0) scores[n * kpad + k] = s;
+  }
+}
+
 __global__ __launch_bounds__(256) void rowsq_kernel(const float* __restrict__ x, int D, float* __restrict__ out) {
   __shared__ float red[4];
   const float* r = x + (int64_t)blockIdx.x * D;
@@ -532,15 +556,15 @@ int launch_finalize(float* out, int64_t n_img, int64_t K, int64_t D, int intra, 
   return launch_status("vlad_finalize_kernel");
 }
 
-// w.scores[n, kpad] = softmax_k(temp * cos(x_n, c_k)) and w.nrm; the GEMM's W operand: the raw centres padded with zero rows
+// w.scores[n, kpad] = softmax_k(temp * cos(x_n, c_k)) in the columns k < K (the padded ones stay unwritten and unread) and w.nrm
 int soft_scores(const float* x, int64_t n, int64_t D, const float* centers, int64_t K, float temp, int norm_descs,
                 const VladWs& w, hipStream_t stream) {
+  ANYLOC_CHECK_ARG(n < (1ll << 31), "vlad_soft: %lld tokens in one call", (long long)n);
   const int kp = (int)kpad_of(K);
-  ANYLOC_HIP(hipMemsetAsync(w.chat, 0, sizeof(float) * kp * D, stream));
-  ANYLOC_HIP(hipMemcpyAsync(w.chat, centers, sizeof(float) * K * D, hipMemcpyDeviceToDevice, stream));
   hipLaunchKernelGGL(rowsq_kernel, dim3((unsigned)K), dim3(256), 0, stream, centers, (int)D, w.cb);
   ANYLOC_TRY(launch_status("rowsq_kernel"));
-  ANYLOC_TRY(run_scores(x, n, D, w, K, false, stream, "vlad_soft_scores_gemm"));
+  hipLaunchKernelGGL(soft_dots_kernel, dim3((unsigned)n), dim3(256), 0, stream, x, centers, (int)D, (int)K, kp, w.scores, w.rowsq);
+  ANYLOC_TRY(launch_status("soft_dots_kernel"));
   hipLaunchKernelGGL(soft_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w.scores, kp, (int)K, w.rowsq,
                      w.cb, n, temp, w.nrm, norm_descs);
   return launch_status("soft_weights_kernel");
@@ -672,9 +696,11 @@ int anyloc_vlad_assigned(const float* tokens, int64_t n_tok, int64_t D, const fl
                          size_t workspace_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   ANYLOC_CHECK_ARG(centers && out && (tokens || n_tok == 0), "vlad_assigned: null pointer");
-  ANYLOC_CHECK_ARG((labels != nullptr) != (soft_weights != nullptr), "vlad_assigned: pass labels (hard) or soft weights, not both");
+  // (an assignment of no tokens has no address: both may be NULL then, and the result is the zero vector either way)
+  ANYLOC_CHECK_ARG(n_tok == 0 || (labels != nullptr) != (soft_weights != nullptr),
+                   "vlad_assigned: pass labels (hard) or soft weights, not both");
   ANYLOC_CHECK_ARG(n_tok >= 0 && n_tok < (1ll << 31) && K >= 1 && K <= 256 && D >= 4 && D % 4 == 0, "vlad_assigned: bad shape");
-  ANYLOC_CHECK_ARG(labels || K <= 64, "vlad_assigned: soft weights need K <= 64");
+  ANYLOC_CHECK_ARG(n_tok == 0 || labels || K <= 64, "vlad_assigned: soft weights need K <= 64");
   VladWs w = carve(workspace, workspace_bytes, n_tok, D, K);
   ANYLOC_TRY(check_workspace("vlad_assigned", workspace, workspace_bytes, w.bytes));
   if (n_tok == 0) {

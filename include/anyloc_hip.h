@@ -301,7 +301,7 @@ int anyloc_vlad_residuals(const float* tokens, int64_t n_tok, int64_t D, const f
 
 /* VLAD of ONE image from a GIVEN assignment -- the cache-hit branches of VLAD.generate
  * (utilities.py:843-847 hard: labels int64 [n_tok]; :864-868 soft: weights fp32 [n_tok, K]; pass exactly one,
- * the other NULL): per-cluster sums of normalise(x_n) - centers (hard: own cluster; soft: the reference's
+ * the other NULL; with n_tok = 0 both may be NULL and out is the zero vector): per-cluster sums of normalise(x_n) - centers (hard: own cluster; soft: the reference's
  * all-cluster sum), intra-norm, global norm.  The [n_tok, K, D] residual tensor is never formed: tokens are
  * what a lazy cache stores.  Workspace: anyloc_vlad_workspace_bytes(n_tok, 1, D, K). */
 int anyloc_vlad_assigned(const float* tokens, int64_t n_tok, int64_t D, const float* centers,

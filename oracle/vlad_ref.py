@@ -48,15 +48,19 @@ def vlad_hard(x, centers, norm_descs=True, intra_norm=True, labels=None):
     return F.normalize(out, dim=0), labels
 
 
-def vlad_soft(x, centers, soft_temp=1.0, norm_descs=True, intra_norm=True):
+def vlad_soft(x, centers, soft_temp=1.0, norm_descs=True, intra_norm=True, weights=None):
     """Soft-assignment VLAD with the reference's quirk (``utilities.py:870-887``):
     weights = softmax(temp * F.cosine_similarity(x, c)) on the tokens as
     passed; block k = sum over ALL tokens q AND ALL clusters c of
     ``w[q,k] * (xh[q] - centers[c])`` (the rearrange "(q c) d" at ``:883-884``
-    sums every cluster's residual, not only cluster k's)."""
+    sums every cluster's residual, not only cluster k's).  ``weights`` [N,K]:
+    the stored weights of a cache hit (``:864-868``) in place of the soft-max."""
     K, D = centers.shape
-    cos = F.cosine_similarity(x[:, None, :], centers[None, :, :], dim=2)
-    w = F.softmax(soft_temp * cos, dim=1)                       # [N,K]
+    if weights is None:
+        cos = F.cosine_similarity(x[:, None, :], centers[None, :, :], dim=2)
+        w = F.softmax(soft_temp * cos, dim=1)                   # [N,K]
+    else:
+        w = weights
     xh = F.normalize(x) if norm_descs else x
     res = xh[:, None, :] - centers[None, :, :]                  # [N,K,D]
     out = torch.zeros(K * D)
