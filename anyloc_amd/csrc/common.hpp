@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 #include "../../include/anyloc_hip.h"
 
@@ -123,6 +124,19 @@ inline int ensure_dyn_lds(DynLds& st, const void* fn, int bytes) {
 }
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// run-time value -> template argument: calls f(std::integral_constant<int, V>) with the smallest V of the ascending list that
+// is >= v (the last one when none is) -- the smallest compiled variant that holds v
+template <int V, int... Rest, class F>
+auto with_constant(int v, F&& f) {
+  if constexpr (sizeof...(Rest) == 0) {
+    return f(std::integral_constant<int, V>{});
+  } else {
+    if (v <= V) return f(std::integral_constant<int, V>{});
+    return with_constant<Rest...>(v, f);
+  }
+}
 
 // bump allocator over the caller's workspace
 struct Arena {
@@ -310,18 +324,31 @@ int qkv_planes_from_f32(const float* qkv, int64_t rows, int D, int heads, unsign
 // (atomicMax by the fc1 / w12 epilogue, zero = block not run fused) -> out[l * groups + g] = max over the rows of group g
 // (rows_per_group consecutive rows: an image, or all M) of 2^15 / rowmax; 0 for a block that left no maxima
 int ffn_looseness(const unsigned* rowmax, int nblocks, int64_t M, int64_t rows_per_group, float* out, hipStream_t stream);
-int gemm_h3(const H3Problem& p, int epilogue, hipStream_t stream);
 // small-M plans (gemm_h3s.hip): GEMMs of fewer than ~2 workgroups of 128 x 256 per CU -- one or a few images per call
 enum { H3_KIND_OTHER = 0, H3_KIND_QKV = 1, H3_KIND_PROJ = 2, H3_KIND_FC1 = 3, H3_KIND_FC2 = 4 };
 constexpr size_t H3_SPLIT_PART_BYTES = 48u << 20;      // partial accumulators of one split-K launch (<= 1024 workgroups x 32 KiB + slack)
 constexpr size_t H3_SPLIT_TICKETS = 4096;               // tiles of one split-K launch
 inline size_t h3_split_workspace_bytes() { return H3_SPLIT_PART_BYTES + H3_SPLIT_TICKETS * sizeof(unsigned) + 512; }
-bool h3_small_supported(int epilogue);
-// would gemm_h3 run this GEMM with the LayerNorm lead role (H3Problem::ln_x)?  The caller then skips its LayerNorm launch.
-bool h3_ln_lead_feasible(const H3Problem& p, int epilogue);       // gemm_h3.hip: small-M rule below or the batched rule
-bool h3s_ln_lead_feasible(const H3Problem& p, int epilogue);      // gemm_h3s.hip (one image per call)
+// How one GEMM runs: everything its launch needs that is not in the problem.  h3_plan (gemm_h3s.hip) is the one place that
+// decides it, from the problem, the epilogue and the options, without a HIP call.
+enum { H3_ROUTE_SMALL, H3_ROUTE_FIXED, H3_ROUTE_BATCHED };
+struct H3Plan {
+  int mfma16;            // first try the 16 x 16 x 32 MFMA kernel (gemm_h3m.hip); the rest is the launch of gemm_h3_kernel otherwise
+  int route;             // the small-M plan table | the two fixed shapes of the epilogues without small-M plans | option h3_cfg's shapes
+  int tile;              // id in kSmallTile (small-M plans) or kH3Tile (gemm_h3_kernel.hpp)
+  int kb, stages;        // k-blocks per ring stage, ring depth
+  int ksplit, kper;      // split-K: ranges of the contraction and k-blocks per range (1, K16: unsplit)
+  int lead;              // LayerNorm lead role (H3Problem::ln_x): 0 = none, 1 = small-M, 2 = batched
+  int tiles_m, tiles_n;
+  unsigned grid;
+};
+// ln_in_front: the caller has a LayerNorm whose output is this GEMM's operand image and asks whether the launch can carry it
+// as its lead role (plan.lead != 0: set H3Problem::ln_x ...; 0: the caller launches layernorm_h2 itself)
+H3Plan h3_plan(const H3Problem& p, int epilogue, bool ln_in_front);
+// plan == nullptr: planned here (with the lead role when p.ln_x is set: an error when the launch cannot carry it)
+int gemm_h3(const H3Problem& p, int epilogue, hipStream_t stream, const H3Plan* plan = nullptr);
+int gemm_h3_small(const H3Problem& p, int epilogue, const H3Plan& plan, hipStream_t stream);      // gemm_h3's launch of a small-M plan
 int h3_lead_plan_check(int tiles_m, int tiles_n, int group_m, int64_t M, unsigned* grid);
-int gemm_h3_small(const H3Problem& p, int epilogue, hipStream_t stream);
 // the same GEMM on v_mfma_f32_16x16x32_f16 (gemm_h3m.hip); ANYLOC_ERR_UNSUPPORTED for epilogues it does not have
 int gemm_h3m(const H3Problem& p, int epilogue, hipStream_t stream);
 // screened retrieval (scores_screen.hip)

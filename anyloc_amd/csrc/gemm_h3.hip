@@ -420,15 +420,13 @@ int split_h2(const float* x, int64_t ldx, int64_t rows, int64_t K, void* h2, flo
   const dim3 grid((unsigned)((rows + 15) / 16));
   unsigned char* out = static_cast<unsigned char*>(h2);
   const int nv = (int)((K / 4 + 63) / 64);
-#define ANYLOC_SPLIT_H2(NVV) \
-  hipLaunchKernelGGL(split_h2_kernel<NVV>, grid, dim3(256), 0, stream, x, ldx, (int)K, rows, out, inv_scale, rows)
-  if (nv <= 1) ANYLOC_SPLIT_H2(1);
-  else if (nv <= 2) ANYLOC_SPLIT_H2(2);
-  else if (nv <= 4) ANYLOC_SPLIT_H2(4);
-  else if (nv <= 6) ANYLOC_SPLIT_H2(6);
-  else if (nv <= 8) ANYLOC_SPLIT_H2(8);
-  else hipLaunchKernelGGL(split_h2_stream_kernel, grid, dim3(256), 0, stream, x, ldx, (int)K, rows, out, inv_scale, rows);
-#undef ANYLOC_SPLIT_H2
+  if (nv > 8) {
+    hipLaunchKernelGGL(split_h2_stream_kernel, grid, dim3(256), 0, stream, x, ldx, (int)K, rows, out, inv_scale, rows);
+  } else {
+    with_constant<1, 2, 4, 6, 8>(nv, [&](auto c) {
+      hipLaunchKernelGGL(split_h2_kernel<decltype(c)::value>, grid, dim3(256), 0, stream, x, ldx, (int)K, rows, out, inv_scale, rows);
+    });
+  }
   return launch_status("split_h2_kernel");
 }
 
@@ -448,16 +446,10 @@ int layernorm_h2(const float* x, const float* w, const float* b, int64_t rows, i
   if (forced == 0 && rows < option(OPT_LN_DIRECT_ROWS)) {
     // a few hundred rows: one single-wave workgroup per row, image written straight from registers
     const dim3 grid((unsigned)rows);
-#define ANYLOC_LN_H2_D(NVV)                                                                                              \
-  hipLaunchKernelGGL((layernorm_h2_direct_kernel<NVV>), grid, dim3(64), 0, stream, x, w, b, dim, rows, eps, out, inv_scale, \
-                     rows, b4, bound ? bound_inv : nullptr)
-    if (nv <= 1) ANYLOC_LN_H2_D(1);
-    else if (nv <= 2) ANYLOC_LN_H2_D(2);
-    else if (nv <= 3) ANYLOC_LN_H2_D(3);
-    else if (nv <= 4) ANYLOC_LN_H2_D(4);
-    else if (nv <= 6) ANYLOC_LN_H2_D(6);
-    else ANYLOC_LN_H2_D(8);
-#undef ANYLOC_LN_H2_D
+    with_constant<1, 2, 3, 4, 6, 8>(nv, [&](auto c) {
+      hipLaunchKernelGGL((layernorm_h2_direct_kernel<decltype(c)::value>), grid, dim3(64), 0, stream, x, w, b, dim, rows, eps, out,
+                         inv_scale, rows, b4, bound ? bound_inv : nullptr);
+    });
     return launch_status("layernorm_h2_direct_kernel");
   }
   const int rpw = (forced == 1 || forced == 2 || forced == 4) ? (int)forced : (rows < option(OPT_LN_SMALL_ROWS) ? 1 : 2);
@@ -467,24 +459,18 @@ int layernorm_h2(const float* x, const float* w, const float* b, int64_t rows, i
   // copy in this pattern takes 80 us per call against LayerNorm's 87-89: tools/micro/ln_store_pattern.hip)
   const int nw = (rpw == 2 && option(OPT_LN_WAVES) == 8) ? 8 : 4;
   const dim3 grid((unsigned)((rows + nw * rpw - 1) / (nw * rpw)));
-#define ANYLOC_LN_H2_R(NVV, RPWV, NWV)                                                                                   \
-  hipLaunchKernelGGL((layernorm_h2_kernel<NVV, RPWV, NWV>), grid, dim3(64 * NWV), 0, stream, x, w, b, dim, rows, eps, out,  \
-                     inv_scale, rows, b4, bound ? bound_inv : nullptr)
-#define ANYLOC_LN_H2(NVV)              \
-  do {                                 \
-    if (rpw == 1) ANYLOC_LN_H2_R(NVV, 1, 4);      \
-    else if (rpw == 2 && nw == 8) ANYLOC_LN_H2_R(NVV, 2, 8); \
-    else if (rpw == 2) ANYLOC_LN_H2_R(NVV, 2, 4); \
-    else ANYLOC_LN_H2_R(NVV, 4, 4);               \
-  } while (0)
-  if (nv <= 1) ANYLOC_LN_H2(1);
-  else if (nv <= 2) ANYLOC_LN_H2(2);
-  else if (nv <= 3) ANYLOC_LN_H2(3);
-  else if (nv <= 4) ANYLOC_LN_H2(4);
-  else if (nv <= 6) ANYLOC_LN_H2(6);
-  else ANYLOC_LN_H2(8);
-#undef ANYLOC_LN_H2_R
-#undef ANYLOC_LN_H2
+  with_constant<1, 2, 3, 4, 6, 8>(nv, [&](auto c) {
+    auto launch = [&](auto r, auto n) {
+      constexpr int NV = decltype(c)::value, RPW = decltype(r)::value, NW = decltype(n)::value;
+      hipLaunchKernelGGL((layernorm_h2_kernel<NV, RPW, NW>), grid, dim3(64 * NW), 0, stream, x, w, b, dim, rows, eps, out, inv_scale,
+                         rows, b4, bound ? bound_inv : nullptr);
+    };
+    using std::integral_constant;
+    if (rpw == 1) launch(integral_constant<int, 1>{}, integral_constant<int, 4>{});
+    else if (rpw == 2 && nw == 8) launch(integral_constant<int, 2>{}, integral_constant<int, 8>{});
+    else if (rpw == 2) launch(integral_constant<int, 2>{}, integral_constant<int, 4>{});
+    else launch(integral_constant<int, 4>{}, integral_constant<int, 4>{});
+  });
   return launch_status("layernorm_h2_kernel");
 }
 
@@ -537,81 +523,24 @@ LeadPlanInfo lead_plan_info(const LeadPlan& lp) {
   return info;
 }
 
+// the launch of a plan: the small-M plans' kernels are gemm_h3s.hip's, the shapes of kH3Tile this file's
 template <int EPI>
-constexpr bool lead_compiled() { return EPI == EPI_QKV_PLANES || EPI == EPI_SWIGLU_T_H2 || EPI == EPI_SWIGLU_H2 || EPI == EPI_GELU_H2; }
-
-template <int EPI>
-int dispatch_h3(const H3Problem& p, hipStream_t stream) {
-  // option h3_cfg (micro-benchmarks): 0 = 128x256 tile, 3-deep ring (default; 128x128 when there are few tiles); 1 = 2-deep;
-  // 2-5 = 256x256 tiles (see the switch)
-  const int cfg = (int)option(OPT_H3_CFG);
-#define ANYLOC_LAUNCH_H3(MI, NI, WM, WN, ST, OCC) ANYLOC_LAUNCH_H3K(MI, NI, WM, WN, ST, OCC, 1)
-#define ANYLOC_LAUNCH_H3K(MI, NI, WM, WN, ST, OCC, KB)                                                                \
-  do {                                                                                                                \
-    using Cfg = H3Cfg<MI, NI, WM, WN, ST, KB>;                                                                        \
-    const int tiles_m = (int)((p.M + Cfg::BM - 1) / Cfg::BM), tiles_n = (int)((p.N + Cfg::BN - 1) / Cfg::BN);         \
-    static DynLds dyn_lds_once; \
-    ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(&gemm_h3_kernel<MI, NI, WM, WN, ST, OCC, EPI, KB>), (int)(Cfg::LDS)));                                                                                                                 \
-    hipLaunchKernelGGL((gemm_h3_kernel<MI, NI, WM, WN, ST, OCC, EPI, KB>), dim3((unsigned)(tiles_m * tiles_n)),        \
-                       dim3(64 * WM * WN), Cfg::LDS, stream, p, tiles_m, tiles_n);                                    \
-  } while (0)
-  const bool small = ((p.M + 127) / 128) * ((p.N + 255) / 256) < 512;
-  if (small && cfg == 0) {
-    // one or a few images (the reference's scripts call the extractor per image): tile shape, ring depth and split-K
-    // factor come from the small-M plan table (gemm_h3s.hip); the unfused epilogues (A/B data flows) keep two fixed shapes
-    if constexpr (EPI == EPI_STORE || EPI == EPI_LS_RESID || EPI == EPI_QKV_PLANES || EPI == EPI_GELU_H2 ||
-                  EPI == EPI_SWIGLU_H2 || EPI == EPI_SWIGLU_T_H2) {
-      return gemm_h3_small(p, EPI, stream);
+int launch_planned(const H3Problem& p, const H3Plan& pl, hipStream_t stream) {
+  if (pl.route == H3_ROUTE_SMALL) return gemm_h3_small(p, EPI, pl, stream);
+  return with_constant<0, 1, 2, 3, 4, 5, H3_TILE_TINY, H3_TILE_128>(pl.tile, [&](auto id) -> int {
+    constexpr int ID = decltype(id)::value;
+    constexpr H3Tile T = kH3Tile[ID];
+    if constexpr (ID >= H3_TILE_TINY && small_epilogue(EPI)) {
+      ANYLOC_CHECK_ARG(false, "gemm_h3: epilogue %d runs few tiles on its small-M plans", EPI);
     } else {
-      if (((p.M + 127) / 128) * ((p.N + 127) / 128) < option(OPT_H3_TINY_MAX)) ANYLOC_LAUNCH_H3(1, 2, 2, 1, 3, 2);   // 64x64, 2 waves
-      else ANYLOC_LAUNCH_H3(2, 2, 2, 2, 3, 2);                                                                         // 128x128
-      return launch_status("gemm_h3_kernel");
+      if constexpr (ID == 0 && batched_lead_compiled(EPI)) {
+        if (pl.lead) return launch_h3<T.mi, T.ni, T.wm, T.wn, T.stages, T.occ, EPI, 1, 2>(p, pl, stream);
+      }
+      return launch_h3<T.mi, T.ni, T.wm, T.wn, T.stages, T.occ, EPI>(p, pl, stream);
     }
-  }
-  if (p.ln_x) {
-    // LayerNorm in front of this GEMM as the lead role of this launch (linear_h3 asked h3_ln_lead_feasible first)
-    if constexpr (lead_compiled<EPI>()) {
-      using Cfg = H3Cfg<2, 4, 2, 2, 3, 1>;
-      const int tiles_m = (int)((p.M + Cfg::BM - 1) / Cfg::BM), tiles_n = (int)((p.N + Cfg::BN - 1) / Cfg::BN);
-      const LeadPlanInfo info = lead_plan_info(LeadPlan{tiles_m, tiles_n, p.group_m, Cfg::BM, (long long)p.M});
-      ANYLOC_CHECK_ARG(cfg == 0 && info.ok && p.ln_tickets && p.ln_w && p.ln_b && (!p.ln_has_bound || p.c_inv) && p.ln_dim == 16 * p.K16 &&
-                           p.ln_dim <= 1536 && p.ksplit <= 1,
-                       "gemm_h3: LayerNorm lead role asked for a launch it does not fit (h3_ln_lead_feasible)");
-      static DynLds dyn_lds_lead;
-      ANYLOC_TRY(ensure_dyn_lds(dyn_lds_lead, reinterpret_cast<const void*>(&gemm_h3_kernel<2, 4, 2, 2, 3, 2, EPI, 1, 2>), (int)(Cfg::LDS)));
-      hipLaunchKernelGGL((gemm_h3_kernel<2, 4, 2, 2, 3, 2, EPI, 1, 2>), dim3(info.grid), dim3(256), Cfg::LDS, stream, p, tiles_m, tiles_n);
-      return launch_status("gemm_h3_kernel (LayerNorm lead role)");
-    } else {
-      ANYLOC_CHECK_ARG(false, "gemm_h3: LayerNorm lead role asked for an epilogue it is not compiled for (h3_ln_lead_feasible)");
-    }
-  }
-  switch (cfg) {
-    case 1: ANYLOC_LAUNCH_H3(2, 4, 2, 2, 2, 2); break;
-    case 2: ANYLOC_LAUNCH_H3(2, 4, 4, 2, 3, 2); break;     // 256x256, 8 waves (2 per SIMD, one workgroup per CU), 96 KiB ring
-    case 3: ANYLOC_LAUNCH_H3(2, 4, 4, 2, 4, 2); break;     // the same, 4-deep ring (128 KiB)
-    case 4: ANYLOC_LAUNCH_H3(4, 4, 2, 2, 4, 1); break;     // 256x256, 4 waves of 128x128 (one per SIMD), 4-deep ring
-    case 5: ANYLOC_LAUNCH_H3(4, 4, 2, 2, 3, 1); break;     // the same, 3-deep ring
-    default: ANYLOC_LAUNCH_H3(2, 4, 2, 2, 3, 2); break;
-  }
-#undef ANYLOC_LAUNCH_H3
-#undef ANYLOC_LAUNCH_H3K
-  return launch_status("gemm_h3_kernel");
+  });
 }
 
-// would gemm_h3 run this GEMM with the LayerNorm lead role (H3Problem::ln_x)?  The caller then skips its LayerNorm launch.
-// One image per call: the small-M plans' rule (gemm_h3s.hip, option h3s_ln_lead); batched: option h3_ln_lead, the default tile
-// configuration, an epilogue the role is compiled for, rows of at most 1536 columns, and a plan that passes lead_plan_info.
-bool h3_ln_lead_feasible(const H3Problem& p, int epilogue) {
-  if (option(OPT_H3_CFG) != 0) return false;
-  if (((p.M + 127) / 128) * ((p.N + 255) / 256) < 512) return h3s_ln_lead_feasible(p, epilogue);
-  if (option(OPT_H3_LN_LEAD) == 0) return false;
-  if (epilogue != EPI_QKV_PLANES && epilogue != EPI_SWIGLU_T_H2 && epilogue != EPI_SWIGLU_H2 && epilogue != EPI_GELU_H2) return false;
-  if (16 * (int64_t)p.K16 > 1536 || p.ksplit > 1) return false;
-  using Cfg = H3Cfg<2, 4, 2, 2, 3, 1>;
-  const int tiles_m = (int)((p.M + Cfg::BM - 1) / Cfg::BM), tiles_n = (int)((p.N + Cfg::BN - 1) / Cfg::BN);
-  const int gm = (int)std::max<int64_t>(1, option(OPT_H3_GROUP_M));
-  return lead_plan_info(LeadPlan{tiles_m, tiles_n, gm, Cfg::BM, (long long)p.M}).ok;
-}
 // host-side check of a lead plan (tests, no GPU needed): 1 = the plan passes, 0 = it does not (the caller keeps two launches)
 int h3_lead_plan_check(int tiles_m, int tiles_n, int group_m, int64_t M, unsigned* grid) {
   const LeadPlanInfo info = lead_plan_info(LeadPlan{tiles_m, tiles_n, group_m, 128, (long long)M});
@@ -619,53 +548,56 @@ int h3_lead_plan_check(int tiles_m, int tiles_n, int group_m, int64_t M, unsigne
   return info.ok ? 1 : 0;
 }
 
-int gemm_h3(const H3Problem& p_in, int epilogue, hipStream_t stream) {
+int gemm_h3(const H3Problem& p_in, int epilogue, hipStream_t stream, const H3Plan* plan) {
   H3Problem p = p_in;
   ANYLOC_CHECK_ARG(p.A2 && p.a_inv && p.W2 && p.w_inv && (p.C || epilogue >= EPI_QKV_PLANES), "gemm_h3: null operand");
   ANYLOC_CHECK_ARG(p.M > 0 && p.N > 0 && p.K16 > 0 && p.RA >= p.M && p.RW >= p.N, "gemm_h3: bad shape");
   ANYLOC_CHECK_ARG((size_t)p.K16 * 2 * (size_t)p.RA * 32 < (1ull << 31) && (size_t)p.K16 * 2 * (size_t)p.RW * 32 < (1ull << 31),
                    "gemm_h3: operand image exceeds the 2 GiB buffer-addressing range");
+  const H3Plan pl = plan ? *plan : h3_plan(p, epilogue, p.ln_x != nullptr);
+  ANYLOC_CHECK_ARG((pl.lead != 0) == (p.ln_x != nullptr) && (!p.ln_x || (p.ln_tickets && p.ln_w && p.ln_b && (!p.ln_has_bound || p.c_inv) &&
+                                                                          p.ln_dim == 16 * p.K16)),
+                   "gemm_h3: LayerNorm lead role asked for a launch that cannot carry it (h3_plan: lead)");
   const int64_t K = 16ll * p.K16;
   ProfScope prof(p.tag ? p.tag : "gemm_h3", stream, 2.0 * p.M * p.N * K, 4.0 * (p.M + p.N) * K + 4.0 * p.M * p.N);
   // tile-rows per scheduling group (co-resident workgroups of an XCD share A / W panels through its L2): option
   // h3_group_m, default 8
   p.group_m = (int)std::max<int64_t>(1, option(OPT_H3_GROUP_M));
-  // plain-store GEMMs of >= 256 tiles of 256 x 256 run on the 16 x 16 x 32 MFMA kernel (gemm_h3m.hip; option h3_mfma16: -1 =
-  // when the contraction is >= 4096 long -- the retrieval panels, +3.6 % -- 0 never, 1 whatever the length)
-  const int64_t m16 = option(OPT_H3_MFMA16);
-  if (epilogue == EPI_STORE && m16 != 0 && (m16 > 0 || p.K16 >= 256) && ((p.M + 255) / 256) * ((p.N + 255) / 256) >= 256) {
+  if (pl.mfma16) {
     const int rc = gemm_h3m(p, epilogue, stream);
     if (rc != ANYLOC_ERR_UNSUPPORTED) return rc;
   }
+  if (pl.route == H3_ROUTE_SMALL) { p.ksplit = pl.ksplit; p.kper = pl.kper; }
+  if (pl.lead == 1) p.ln_wgs = (int)pl.grid - pl.tiles_m * pl.tiles_n;        // the launch's first workgroups
   switch (epilogue) {
-    case EPI_STORE: return dispatch_h3<EPI_STORE>(p, stream);
-    case EPI_GELU: return dispatch_h3<EPI_GELU>(p, stream);
+    case EPI_STORE: return launch_planned<EPI_STORE>(p, pl, stream);
+    case EPI_GELU: return launch_planned<EPI_GELU>(p, pl, stream);
     case EPI_PATCH:
       ANYLOC_CHECK_ARG(p.pos && p.patches > 0 && p.M % p.patches == 0, "gemm_h3: PATCH needs pos and M = batch * patches");
-      return dispatch_h3<EPI_PATCH>(p, stream);
+      return launch_planned<EPI_PATCH>(p, pl, stream);
     case EPI_LS_RESID: {
       ANYLOC_CHECK_ARG(p.gamma && p.resid, "gemm_h3: LS_RESID needs gamma and resid");
       H3Problem q = p;
       // option h3_epi_lds = 0: the dword read-modify-write epilogue (also the fallback for unaligned C)
       q.epi_lds = option(OPT_H3_EPI_LDS) != 0 && p.N % 4 == 0 && p.ldc % 4 == 0 &&
                   (reinterpret_cast<uintptr_t>(p.C) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.resid) & 15) == 0;
-      return dispatch_h3<EPI_LS_RESID>(q, stream);
+      return launch_planned<EPI_LS_RESID>(q, pl, stream);
     }
     case EPI_SWIGLU:
       ANYLOC_CHECK_ARG(p.N % 64 == 0, "gemm_h3: SWIGLU needs N %% 64 == 0");
-      return dispatch_h3<EPI_SWIGLU>(p, stream);
+      return launch_planned<EPI_SWIGLU>(p, pl, stream);
     case EPI_QKV_PLANES:
       ANYLOC_CHECK_ARG(p.qkv_planes && p.qkv_inv && p.heads > 0 && p.N == 3ll * p.heads * 64 && (p.heads * 64) % 128 == 0 &&
                            p.groups == (p.M + 31) / 32,
                        "gemm_h3: QKV_PLANES needs N = 3 * heads * 64, D %% 128 == 0 and groups = ceil(M / 32)");
-      return dispatch_h3<EPI_QKV_PLANES>(p, stream);
+      return launch_planned<EPI_QKV_PLANES>(p, pl, stream);
     case EPI_GELU_H2:
       ANYLOC_CHECK_ARG(p.C2 && p.c_inv && p.RC >= p.M && p.N % 64 == 0, "gemm_h3: GELU_H2 needs an output image, c_inv and N %% 64 == 0");
-      return dispatch_h3<EPI_GELU_H2>(p, stream);
+      return launch_planned<EPI_GELU_H2>(p, pl, stream);
     case EPI_SWIGLU_H2:
       ANYLOC_CHECK_ARG(p.C2 && p.c_inv && p.RC >= p.M && p.N % 128 == 0, "gemm_h3: SWIGLU_H2 needs an output image, c_inv and N %% 128 == 0");
       p.fast_silu = option(OPT_H3_FAST_SILU) != 0;
-      return dispatch_h3<EPI_SWIGLU_H2>(p, stream);
+      return launch_planned<EPI_SWIGLU_H2>(p, pl, stream);
     case EPI_SWIGLU_T:
     case EPI_SWIGLU_T_H2:
       ANYLOC_CHECK_ARG(p.N % 128 == 0 && (reinterpret_cast<uintptr_t>(p.w_inv) & 15) == 0 &&
@@ -676,7 +608,7 @@ int gemm_h3(const H3Problem& p_in, int epilogue, hipStream_t stream) {
       else
         ANYLOC_CHECK_ARG(p.C && p.ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0, "gemm_h3: SWIGLU_T needs an aligned fp32 output");
       p.fast_silu = option(OPT_H3_FAST_SILU) != 0;
-      return epilogue == EPI_SWIGLU_T ? dispatch_h3<EPI_SWIGLU_T>(p, stream) : dispatch_h3<EPI_SWIGLU_T_H2>(p, stream);
+      return epilogue == EPI_SWIGLU_T ? launch_planned<EPI_SWIGLU_T>(p, pl, stream) : launch_planned<EPI_SWIGLU_T_H2>(p, pl, stream);
     default: set_error("gemm_h3: unsupported epilogue %d", epilogue); return ANYLOC_ERR_INVALID_ARG;
   }
 }

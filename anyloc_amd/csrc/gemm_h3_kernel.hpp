@@ -303,7 +303,7 @@ __device__ __forceinline__ void ln_row_direct(const float* __restrict__ x, const
 // workgroup meets, one lane adds the workgroup's rows to the ticket of their BM-row tile (relaxed, agent scope: the hand-off of the
 // split-K plans below).  A GEMM workgroup waits (one lane polls, bounded) until its row tile's ticket holds all the tile's rows,
 // then stages A with sc1 loads.  Placement-independent: lead workgroups never wait, and there are fewer GEMM workgroups than CUs
-// (h3_ln_lead_feasible), so whatever order the dispatcher picks, every lead workgroup finds a CU.
+// (h3_plan), so whatever order the dispatcher picks, every lead workgroup finds a CU.
 // LNL = 2 (batched GEMMs, gemm_h3.hip): lead workgroups of LEAD_ROWS = 16 rows (four per wave, the tiled arithmetic and store
 // order of layernorm_h2_kernel) are INTERLEAVED with the GEMM tiles per XCD (tile_order.hpp, LeadPlan: the lead work of tile-row
 // group j + 1 sits among the XCD's tiles of group j), so that LayerNorm's HBM traffic runs under the matrix work instead of in a
@@ -918,6 +918,79 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void gemm_h3_kernel(H3Problem p,
         }
       }
   }
+}
+
+// ---- host side: the tile shapes a plan (H3Plan, common.hpp) can name, and the one launch site of the kernel ----
+struct H3Tile {
+  int mi, ni, wm, wn;                          // a wave holds MI x NI blocks of 32 x 32; WM x WN waves
+  int stages, occ;                             // kH3Tile only: ring depth, workgroups per CU the registers are bounded for
+  constexpr int nw() const { return wm * wn; }
+  constexpr int bm() const { return 32 * mi * wm; }
+  constexpr int bn() const { return 32 * ni * wn; }
+  constexpr int lds(int st, int kb) const { return st * kb * 64 * (bm() + bn()); }             // H3Cfg::LDS
+  constexpr int ndma(int kb) const { return kb * 2 * (bm() / 32 + bn() / 32) / nw(); }         // H3Cfg::NDMA
+};
+// small-M plans (gemm_h3s.hip): tile id -> shape; ring depth, k-blocks per stage and split-K come from the plan table
+constexpr H3Tile kSmallTile[] = {
+    {1, 2, 2, 1},      // 0: 64 x 64, two waves of 32 x 64
+    {2, 2, 1, 2},      // 1: 64 x 128, two waves of 64 x 64
+    {1, 2, 2, 2},      // 2: 64 x 128, four waves of 32 x 64
+    {1, 4, 2, 1},      // 3: 64 x 128, two waves of 32 x 128
+    {2, 2, 2, 2},      // 4: 128 x 128, four waves of 64 x 64
+    {2, 2, 1, 4},      // 5: 64 x 256, four waves of 64 x 64
+    {1, 4, 2, 2},      // 6: 64 x 256, four waves of 32 x 128
+    {3, 2, 2, 2},      // 7: 192 x 128, four waves of 96 x 64 (530 rows = 3 row tiles)
+};
+constexpr int NSMALL = sizeof(kSmallTile) / sizeof(kSmallTile[0]);
+// gemm_h3.hip: ids 0 - 5 = option h3_cfg (micro-benchmarks; 0 = default), 6 / 7 = the two shapes of the epilogues without small-M plans
+constexpr H3Tile kH3Tile[] = {
+    {2, 4, 2, 2, 3, 2},      // 128 x 256, 3-deep ring
+    {2, 4, 2, 2, 2, 2},      // 2-deep
+    {2, 4, 4, 2, 3, 2},      // 256x256, 8 waves (2 per SIMD, one workgroup per CU), 96 KiB ring
+    {2, 4, 4, 2, 4, 2},      // the same, 4-deep ring (128 KiB)
+    {4, 4, 2, 2, 4, 1},      // 256x256, 4 waves of 128x128 (one per SIMD), 4-deep ring
+    {4, 4, 2, 2, 3, 1},      // the same, 3-deep ring
+    {1, 2, 2, 1, 3, 2},      // 64x64, 2 waves
+    {2, 2, 2, 2, 3, 2},      // 128x128
+};
+constexpr int H3_TILE_TINY = 6, H3_TILE_128 = 7;
+
+// what a small-M plan can ask of a tile: four k-blocks per ring stage where a 3-deep ring of them fits the CU's 160 KiB (two
+// otherwise), a 6-deep ring where it fits the 160 KiB and the counted wait's 6 bits
+constexpr int small_kb(H3Tile t, int kb) { return kb >= 4 ? (t.lds(3, 4) <= 160 * 1024 ? 4 : 2) : kb == 2 ? 2 : 1; }
+constexpr int small_stages(H3Tile t, int kb, int stages) {
+  return stages >= 6 && t.lds(6, kb) <= 160 * 1024 && 4 * t.ndma(kb) <= 63 ? 6 : 3;
+}
+// the epilogues that have small-M plans (the others: kH3Tile 6 / 7)
+constexpr bool small_epilogue(int epi) {
+  return epi == EPI_STORE || epi == EPI_LS_RESID || epi == EPI_QKV_PLANES || epi == EPI_GELU_H2 || epi == EPI_SWIGLU_H2 ||
+         epi == EPI_SWIGLU_T_H2;
+}
+// the plans the small-M LayerNorm lead role (LNL = 1) is compiled for: the one-image qkv plan (128 x 128, 6-deep ring) and the
+// one-image w12 plan (192 x 128, 6-deep ring), with the epilogues those two GEMMs have in the fused forward
+constexpr bool small_lead_compiled(int epi, int tile, int kb, int stages) {
+  return kb == 1 && stages == 6 && ((tile == 4 && epi == EPI_QKV_PLANES) || (tile == 7 && (epi == EPI_SWIGLU_T_H2 || epi == EPI_SWIGLU_H2)));
+}
+// the epilogues the batched lead role (LNL = 2, kH3Tile[0]) is compiled for
+constexpr bool batched_lead_compiled(int epi) {
+  return epi == EPI_QKV_PLANES || epi == EPI_SWIGLU_T_H2 || epi == EPI_SWIGLU_H2 || epi == EPI_GELU_H2;
+}
+
+// One DynLds memo per instantiation; grid and tile counts from the plan, which must be this problem's on this shape.
+template <int MI, int NI, int WM, int WN, int ST, int OCC, int EPI, int KB = 1, int LNL = 0>
+int launch_h3(const H3Problem& p, const H3Plan& pl, hipStream_t stream) {
+  using Cfg = H3Cfg<MI, NI, WM, WN, ST, KB>;
+  constexpr H3Tile T{MI, NI, WM, WN};
+  static_assert(Cfg::BM == T.bm() && Cfg::BN == T.bn() && Cfg::LDS == T.lds(ST, KB) && Cfg::NDMA == T.ndma(KB), "H3Tile restates H3Cfg");
+  static_assert(LNL != 1 || Cfg::BM % Cfg::NW == 0, "small-M lead role: the rows of a lead workgroup lie in one row tile");
+  ANYLOC_CHECK_ARG(pl.lead == LNL && pl.tiles_m == (p.M + Cfg::BM - 1) / Cfg::BM && pl.tiles_n == (p.N + Cfg::BN - 1) / Cfg::BN,
+                   "gemm_h3: the plan was made for another problem");
+  static DynLds dyn_lds_once;
+  ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(&gemm_h3_kernel<MI, NI, WM, WN, ST, OCC, EPI, KB, LNL>), (int)(Cfg::LDS)));
+  hipLaunchKernelGGL((gemm_h3_kernel<MI, NI, WM, WN, ST, OCC, EPI, KB, LNL>), dim3(pl.grid), dim3(64 * WM * WN), Cfg::LDS, stream, p,
+                     pl.tiles_m, pl.tiles_n);
+  return launch_status(pl.route == H3_ROUTE_SMALL ? (LNL ? "gemm_h3_kernel (small-M plan, LayerNorm lead role)" : "gemm_h3_kernel (small-M plan)")
+                                                  : (LNL ? "gemm_h3_kernel (LayerNorm lead role)" : "gemm_h3_kernel"));
 }
 
 }  // namespace

@@ -17,92 +17,10 @@ namespace anyloc {
 
 namespace {
 
-struct Plan {
-  int cfg, kb, ksplit;
-  int stages = 3;      // ring depth: 3 or 6 stages
-};
-
-// tile configurations: id -> (MI, NI, WM, WN); BM = 32 MI WM, BN = 32 NI WN
-constexpr int NCFG = 8;
-const int kCfgBM[NCFG] = {64, 64, 64, 64, 128, 64, 64, 192};
-const int kCfgBN[NCFG] = {64, 128, 128, 128, 128, 256, 256, 128};
-
-// the plans the LayerNorm lead role is compiled for: the one-image qkv plan (128 x 128, 6-deep ring) and the one-image w12 plan
-// (192 x 128, 6-deep ring), with the epilogues those two GEMMs have in the fused forward
-template <int EPI, int MI, int NI, int WM, int WN, int KB, int ST>
-constexpr bool ln_lead_compiled() {
-  return KB == 1 && ST == 6 && WM == 2 && WN == 2 && NI == 2 &&
-         ((MI == 2 && EPI == EPI_QKV_PLANES) || (MI == 3 && (EPI == EPI_SWIGLU_T_H2 || EPI == EPI_SWIGLU_H2)));
-}
 constexpr int LN_LEAD_MAX_TILES = 200;        // GEMM workgroups of a lead launch: fewer than CUs, so the lead workgroups always find one
 
-template <int EPI, int MI, int NI, int WM, int WN, int KB, int ST = 3>
-int launch_small(const H3Problem& p, hipStream_t stream) {
-  using Cfg = H3Cfg<MI, NI, WM, WN, ST, KB>;
-  const int tiles_m = (int)((p.M + Cfg::BM - 1) / Cfg::BM), tiles_n = (int)((p.N + Cfg::BN - 1) / Cfg::BN);
-  if constexpr (ln_lead_compiled<EPI, MI, NI, WM, WN, KB, ST>()) {
-    if (p.ln_x) {
-      ANYLOC_CHECK_ARG(p.ksplit <= 1 && tiles_m * tiles_n <= LN_LEAD_MAX_TILES && p.ln_tickets && p.ln_w && p.ln_b &&
-                           (!p.ln_has_bound || p.c_inv) && p.ln_dim == 16 * p.K16 && Cfg::BM % Cfg::NW == 0,
-                       "gemm_h3_small: LayerNorm lead role asked for a launch it does not fit (h3s_ln_lead_feasible)");
-      H3Problem q = p;
-      q.ln_wgs = (int)(((p.M + Cfg::NW - 1) / Cfg::NW + 7) / 8 * 8);        // one row per wave; a multiple of 8 (XCD mapping of the GEMM ids)
-      static DynLds dyn_lds_once;
-      ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(&gemm_h3_kernel<MI, NI, WM, WN, ST, 2, EPI, KB, 1>), (int)(Cfg::LDS)));
-      hipLaunchKernelGGL((gemm_h3_kernel<MI, NI, WM, WN, ST, 2, EPI, KB, 1>), dim3((unsigned)(q.ln_wgs + tiles_m * tiles_n)),
-                         dim3(64 * WM * WN), Cfg::LDS, stream, q, tiles_m, tiles_n);
-      return launch_status("gemm_h3_kernel (small-M plan, LayerNorm lead role)");
-    }
-  } else {
-    ANYLOC_CHECK_ARG(!p.ln_x, "gemm_h3_small: LayerNorm lead role asked for a plan it is not compiled for (h3s_ln_lead_feasible)");
-  }
-  static DynLds dyn_lds_once;
-  ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(&gemm_h3_kernel<MI, NI, WM, WN, ST, 2, EPI, KB>), (int)(Cfg::LDS)));
-  hipLaunchKernelGGL((gemm_h3_kernel<MI, NI, WM, WN, ST, 2, EPI, KB>), dim3((unsigned)(tiles_m * tiles_n * std::max(1, p.ksplit))),
-                     dim3(64 * WM * WN), Cfg::LDS, stream, p, tiles_m, tiles_n);
-  return launch_status("gemm_h3_kernel (small-M plan)");
-}
-
-// a 6-deep ring where it fits the CU's 160 KiB and the counted wait's 6 bits
-template <int MI, int NI, int WM, int WN, int KB>
-constexpr bool deep_ok() {
-  using C6 = H3Cfg<MI, NI, WM, WN, 3, KB>;      // (LDS / NDMA scale linearly with the stage count)
-  return 2 * C6::LDS <= 160 * 1024 && 4 * C6::NDMA <= 63;
-}
-
-template <int EPI, int MI, int NI, int WM, int WN, int KB>
-int launch_st(const H3Problem& p, int stages, hipStream_t stream) {
-  if constexpr (deep_ok<MI, NI, WM, WN, KB>()) {
-    if (stages >= 6) return launch_small<EPI, MI, NI, WM, WN, KB, 6>(p, stream);
-  }
-  return launch_small<EPI, MI, NI, WM, WN, KB, 3>(p, stream);
-}
-
-template <int EPI, int MI, int NI, int WM, int WN>
-int launch_kb(const H3Problem& p, int kb, int stages, hipStream_t stream) {
-  if (kb >= 4) {
-    if constexpr (H3Cfg<MI, NI, WM, WN, 3, 4>::LDS <= 160 * 1024) return launch_st<EPI, MI, NI, WM, WN, 4>(p, stages, stream);
-    kb = 2;
-  }
-  if (kb == 2) return launch_st<EPI, MI, NI, WM, WN, 2>(p, stages, stream);
-  return launch_st<EPI, MI, NI, WM, WN, 1>(p, stages, stream);
-}
-
-template <int EPI>
-int launch_cfg(const H3Problem& p, const Plan& pl, hipStream_t stream) {
-  switch (pl.cfg) {
-    case 0: return launch_kb<EPI, 1, 2, 2, 1>(p, pl.kb, pl.stages, stream);    // 64 x 64, two waves of 32 x 64
-    case 1: return launch_kb<EPI, 2, 2, 1, 2>(p, pl.kb, pl.stages, stream);    // 64 x 128, two waves of 64 x 64
-    case 2: return launch_kb<EPI, 1, 2, 2, 2>(p, pl.kb, pl.stages, stream);    // 64 x 128, four waves of 32 x 64
-    case 3: return launch_kb<EPI, 1, 4, 2, 1>(p, pl.kb, pl.stages, stream);    // 64 x 128, two waves of 32 x 128
-    case 4: return launch_kb<EPI, 2, 2, 2, 2>(p, pl.kb, pl.stages, stream);    // 128 x 128, four waves of 64 x 64
-    case 5: return launch_kb<EPI, 2, 2, 1, 4>(p, pl.kb, pl.stages, stream);    // 64 x 256, four waves of 64 x 64
-    case 7: return launch_kb<EPI, 3, 2, 2, 2>(p, pl.kb, pl.stages, stream);    // 192 x 128, four waves of 96 x 64 (530 rows = 3 row tiles)
-    default: return launch_kb<EPI, 1, 4, 2, 2>(p, pl.kb, pl.stages, stream);   // 64 x 256, four waves of 32 x 128
-  }
-}
-
-int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// the round-3 rule: below option h3_tiny_max tiles of 128 x 128, 64 x 64 two-wave tiles
+bool tiny(const H3Problem& p) { return cdiv(p.M, 128) * cdiv(p.N, 128) < option(OPT_H3_TINY_MAX); }
 
 // The plan table.  Starting point: the round-3 small-batch rules (64 x 64 two-wave tiles with four / two k-blocks per ring
 // stage while a workgroup is alone on its CU, 128 x 128 four-wave tiles from 256 such tiles up).  Up to two images (M <= 1100
@@ -124,27 +42,18 @@ int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // the last arrival's slab reads cost what the shorter k-loop saves at K = 1536); a deeper ring (bytes in flight) helps the
 // GEMMs with the fewest workgroups; and with the weights resident on-die (a 2-block model) the same launches are no faster
 // (profiles/r04_b1_weight_residency_probe.log) -- a one-image GEMM waits for its own fill / barrier / MFMA chain, not for HBM.
-Plan choose(const H3Problem& p, int epilogue) {
-  Plan pl{0, 1, 1};
+void choose(const H3Problem& p, H3Plan& pl) {
+  auto set = [&](int tile, int kb, int ksplit, int stages = 3) { pl.tile = tile; pl.kb = kb; pl.ksplit = ksplit; pl.stages = stages; };
   const int64_t t64 = cdiv(p.M, 64) * cdiv(p.N, 64);
-  if (cdiv(p.M, 128) * cdiv(p.N, 128) >= option(OPT_H3_TINY_MAX)) pl = Plan{4, 1, 1};
-  else pl = Plan{0, t64 < option(OPT_H3_DEEP_MAX) ? 4 : t64 < option(OPT_H3_DEEP2_MAX) ? 2 : 1, 1};
-  if (option(OPT_H3S_ENABLE) == 0) return pl;              // the round-3 small-batch kernels, exactly
+  if (!tiny(p)) set(4, 1, 1);
+  else set(0, t64 < option(OPT_H3_DEEP_MAX) ? 4 : t64 < option(OPT_H3_DEEP2_MAX) ? 2 : 1, 1);
+  if (option(OPT_H3S_ENABLE) == 0) return;                 // the round-3 small-batch kernels, exactly
   if (p.M <= 1100) {
     const bool one = p.M <= 600;                           // one 322 x 322 image (530 rows) / two
-    if (p.N <= 2048 && p.K16 >= 192) {                     // fc2-like: long contraction, narrow output
-      pl = Plan{2, 1, one ? 2 : 1};
-      pl.stages = 6;
-    } else if (p.N <= 2048) {                              // proj-like
-      pl = one ? Plan{0, 1, 1} : Plan{2, 1, 1};
-      pl.stages = 6;
-    } else if (p.N < 8192) {                               // qkv-like
-      pl = one ? Plan{4, 1, 1} : Plan{2, 1, 1};
-      pl.stages = one ? 6 : 3;
-    } else if (one && p.M > 384 && option(OPT_H3S_W12_TALL)) {   // w12-like, 385 ... 576 rows: three 192-row tiles, one workgroup per CU
-      pl = Plan{7, 1, 1};
-      pl.stages = 6;
-    }
+    if (p.N <= 2048 && p.K16 >= 192) set(2, 1, one ? 2 : 1, 6);              // fc2-like: long contraction, narrow output
+    else if (p.N <= 2048) set(one ? 0 : 2, 1, 1, 6);                         // proj-like
+    else if (p.N < 8192) set(one ? 4 : 2, 1, 1, one ? 6 : 3);                // qkv-like
+    else if (one && p.M > 384 && option(OPT_H3S_W12_TALL)) set(7, 1, 1, 6);  // w12-like, 385 ... 576 rows: three 192-row tiles, one workgroup per CU
   } else if (p.M <= 1700) {
     // One 476 x 630 image = 1531 token rows: the reference scripts' DEFAULT shape (configs.py:141 resize [480, 640], centre crop
     // scripts/dino_v2_vlad.py:173-176) -- and three 322 x 322 images.  Round 5 sweep at that shape (tools/sweep_b1.py 1 ... 476x630,
@@ -152,82 +61,116 @@ Plan choose(const H3Problem& p, int epilogue) {
     // the best plan for qkv (70.6 us) and w12 (103.7 us); the two narrow GEMMs are not --
     //   fc2  (K = 4096, N = 1536): 144 tiles of 128 x 128 on 256 CUs; 64 x 128 four-wave tiles with split-K 2: 88.6 -> 76.3 us
     //   proj (K = 1536, N = 1536): 64 x 128 four-wave tiles, 6-deep ring:                                   40.1 -> 37.4 us
-    if (p.N <= 2048 && p.K16 >= 192) {
-      pl = Plan{2, 1, 2};
-    } else if (p.N <= 2048) {
-      pl = Plan{2, 1, 1};
-      pl.stages = 6;
-    }
+    if (p.N <= 2048 && p.K16 >= 192) set(2, 1, 2);
+    else if (p.N <= 2048) set(2, 1, 1, 6);
   }
   const int64_t mask = option(OPT_H3S_MASK);
   const int bit = p.kind == H3_KIND_QKV ? 1 : p.kind == H3_KIND_PROJ ? 2 : p.kind == H3_KIND_FC1 ? 4 : p.kind == H3_KIND_FC2 ? 8 : 16;
   if (mask & bit) {
     const int64_t c = option(OPT_H3S_CFG), s = option(OPT_H3S_KSPLIT), k = option(OPT_H3S_KB);
-    if (c >= 0 && c < NCFG) pl.cfg = (int)c;
+    if (c >= 0 && c < NSMALL) pl.tile = (int)c;
     if (s > 0) pl.ksplit = (int)s;
     if (k == 1 || k == 2 || k == 4) pl.kb = (int)k;
     const int64_t st = option(OPT_H3S_STAGES);
     if (st == 3 || st == 6) pl.stages = (int)st;
   }
-  return pl;
+}
+
+// the epilogues that write q|k|v tiles need whole heads per wave column block: NI even (all of kSmallTile have it)
+template <int EPI, int ID, int KB, int ST>
+int launch_small(const H3Problem& p, const H3Plan& pl, hipStream_t stream) {
+  constexpr H3Tile T = kSmallTile[ID];
+  if constexpr (small_kb(T, KB) == KB && small_stages(T, KB, ST) == ST) {
+    if constexpr (small_lead_compiled(EPI, ID, KB, ST)) {
+      if (pl.lead) return launch_h3<T.mi, T.ni, T.wm, T.wn, ST, 2, EPI, KB, 1>(p, pl, stream);
+    }
+    return launch_h3<T.mi, T.ni, T.wm, T.wn, ST, 2, EPI, KB>(p, pl, stream);
+  } else {
+    ANYLOC_CHECK_ARG(false, "gemm_h3: tile %d has no small-M kernel with %d k-blocks per stage and a %d-deep ring", ID, KB, ST);
+  }
 }
 
 }  // namespace
 
-// the plan gemm_h3_small will run (shared by it and by h3s_ln_lead_feasible)
-static Plan final_plan(H3Problem& p, int epilogue) {
-  Plan pl = choose(p, epilogue);
-  const int64_t tiles = cdiv(p.M, kCfgBM[pl.cfg]) * cdiv(p.N, kCfgBN[pl.cfg]);
-  if (!p.sk_part || !p.sk_tickets || p.accumulate) pl.ksplit = 1;
-  pl.ksplit = (int)std::min<int64_t>(pl.ksplit, p.K16);
-  while (pl.ksplit > 1 && ((size_t)pl.ksplit * tiles * kCfgBM[pl.cfg] * kCfgBN[pl.cfg] * sizeof(float) > H3_SPLIT_PART_BYTES ||
-                           tiles > (int64_t)H3_SPLIT_TICKETS))
-    --pl.ksplit;
+H3Plan h3_plan(const H3Problem& p, int epilogue, bool ln_in_front) {
+  H3Plan pl{};
+  pl.kb = 1; pl.ksplit = 1; pl.kper = p.K16;
+  // option h3_cfg (micro-benchmarks): 0 = 128x256 tile, 3-deep ring (default; the small-M plans when there are few tiles);
+  // 1 - 5: kH3Tile, at every size
+  const int cfg = (int)option(OPT_H3_CFG);
+  // plain-store GEMMs of >= 256 tiles of 256 x 256 run on the 16 x 16 x 32 MFMA kernel (gemm_h3m.hip; option h3_mfma16: -1 =
+  // when the contraction is >= 4096 long -- the retrieval panels, +3.6 % -- 0 never, 1 whatever the length)
+  const int64_t m16 = option(OPT_H3_MFMA16);
+  pl.mfma16 = epilogue == EPI_STORE && m16 != 0 && (m16 > 0 || p.K16 >= 256) && cdiv(p.M, 256) * cdiv(p.N, 256) >= 256;
+  // few tiles -- one or a few images (the reference's scripts call the extractor per image): tile shape, ring depth and split-K
+  // factor come from the small-M plan table; the epilogues without plans (unfused A/B data flows) keep two fixed shapes
+  const bool few = cfg == 0 && cdiv(p.M, 128) * cdiv(p.N, 256) < 512;
+  H3Tile t;
+  if (few && small_epilogue(epilogue)) {
+    pl.route = H3_ROUTE_SMALL;
+    choose(p, pl);
+    t = kSmallTile[pl.tile];
+    // split-K needs the workspace, a plain (non-accumulating) epilogue input and enough k-blocks
+    const int64_t tiles = cdiv(p.M, t.bm()) * cdiv(p.N, t.bn());
+    if (!p.sk_part || !p.sk_tickets || p.accumulate) pl.ksplit = 1;
+    pl.ksplit = (int)std::min<int64_t>(pl.ksplit, p.K16);
+    while (pl.ksplit > 1 && ((size_t)pl.ksplit * tiles * t.bm() * t.bn() * sizeof(float) > H3_SPLIT_PART_BYTES || tiles > (int64_t)H3_SPLIT_TICKETS))
+      --pl.ksplit;
+    // k-blocks per split: a multiple of the ring stage's k-blocks (as the table asks for them), so that only the LAST split
+    // can end inside a stage (its missing k-blocks lie beyond the buffer descriptors and read as zeros)
+    if (pl.ksplit > 1) {
+      pl.kper = (int)(cdiv(cdiv(p.K16, pl.ksplit), pl.kb) * pl.kb);
+      pl.ksplit = (int)cdiv(p.K16, pl.kper);                 // no empty split
+      if (pl.ksplit <= 1) { pl.ksplit = 1; pl.kper = p.K16; }
+    }
+    pl.kb = small_kb(t, pl.kb);
+    pl.stages = small_stages(t, pl.kb, pl.stages);
+  } else {
+    pl.route = few ? H3_ROUTE_FIXED : H3_ROUTE_BATCHED;
+    pl.tile = few ? (tiny(p) ? H3_TILE_TINY : H3_TILE_128) : (cfg >= 1 && cfg <= 5 ? cfg : 0);
+    t = kH3Tile[pl.tile];
+    pl.stages = t.stages;
+  }
+  pl.tiles_m = (int)cdiv(p.M, t.bm());
+  pl.tiles_n = (int)cdiv(p.N, t.bn());
+  pl.grid = (unsigned)(pl.tiles_m * pl.tiles_n * pl.ksplit);
+  if (!ln_in_front) return pl;
+  // The LayerNorm in front of this GEMM as the lead role of its launch.  One image per call (option h3s_ln_lead): an unsplit plan
+  // the role is compiled for, with a CU left for every lead workgroup -- one row per wave, a multiple of 8 of them (XCD mapping
+  // of the GEMM ids).  Batched (option h3_ln_lead): the default tile, an epilogue the role is compiled for, rows of at most
+  // 1536 columns, and a workgroup order that passes the host check (tile_order.hpp: LeadPlan), which also gives the grid.
+  static_assert(kH3Tile[0].bm() == 128, "h3_lead_plan_check simulates 128-row tiles");
+  unsigned lead_grid = 0;
+  if (pl.route == H3_ROUTE_SMALL && option(OPT_H3S_LN_LEAD) != 0 && small_lead_compiled(epilogue, pl.tile, pl.kb, pl.stages) &&
+      pl.ksplit == 1 && pl.tiles_m * pl.tiles_n <= LN_LEAD_MAX_TILES) {
+    pl.lead = 1;
+    pl.grid += (unsigned)((cdiv(p.M, t.nw()) + 7) / 8 * 8);
+  } else if (pl.route == H3_ROUTE_BATCHED && cfg == 0 && option(OPT_H3_LN_LEAD) != 0 && batched_lead_compiled(epilogue) &&
+             16 * (int64_t)p.K16 <= 1536 && p.ksplit <= 1 &&
+             h3_lead_plan_check(pl.tiles_m, pl.tiles_n, (int)std::max<int64_t>(1, option(OPT_H3_GROUP_M)), p.M, &lead_grid)) {
+    pl.lead = 2;
+    pl.grid = lead_grid;
+  }
   return pl;
 }
 
-bool h3s_ln_lead_feasible(const H3Problem& p_in, int epilogue) {
-  if (option(OPT_H3S_LN_LEAD) == 0 || option(OPT_H3_CFG) != 0) return false;
-  if (epilogue != EPI_QKV_PLANES && epilogue != EPI_SWIGLU_T_H2 && epilogue != EPI_SWIGLU_H2) return false;
-  if (((p_in.M + 127) / 128) * ((p_in.N + 255) / 256) >= 512) return false;        // (dispatch_h3's small-M rule)
-  H3Problem p = p_in;
-  const Plan pl = final_plan(p, epilogue);
-  if (pl.ksplit != 1 || pl.kb != 1 || pl.stages != 6) return false;
-  if (!((pl.cfg == 4 && epilogue == EPI_QKV_PLANES) || (pl.cfg == 7 && epilogue != EPI_QKV_PLANES))) return false;
-  return cdiv(p.M, kCfgBM[pl.cfg]) * cdiv(p.N, kCfgBN[pl.cfg]) <= LN_LEAD_MAX_TILES;
-}
-
-bool h3_small_supported(int epilogue) {
-  switch (epilogue) {
-    case EPI_STORE: case EPI_LS_RESID: case EPI_QKV_PLANES: case EPI_GELU_H2: case EPI_SWIGLU_H2: case EPI_SWIGLU_T_H2: return true;
-    default: return false;
-  }
-}
-
-int gemm_h3_small(const H3Problem& p_in, int epilogue, hipStream_t stream) {
-  H3Problem p = p_in;
-  // the epilogues that write q|k|v tiles need whole heads per wave column block: NI even (all configurations have it)
-  // split-K needs the workspace, a plain (non-accumulating) epilogue input and enough k-blocks
-  Plan pl = final_plan(p, epilogue);
-  p.ksplit = pl.ksplit;
-  // k-blocks per split: a multiple of the ring stage's k-blocks, so that only the LAST split can end inside a stage
-  // (its missing k-blocks lie beyond the buffer descriptors and read as zeros)
-  if (pl.ksplit > 1) {
-    p.kper = (int)(cdiv(cdiv(p.K16, pl.ksplit), pl.kb) * pl.kb);
-    p.ksplit = (int)cdiv(p.K16, p.kper);                   // no empty split
-    if (p.ksplit <= 1) { p.ksplit = 1; p.kper = p.K16; }
-  } else {
-    p.kper = p.K16;
-  }
-  switch (epilogue) {
-    case EPI_STORE: return launch_cfg<EPI_STORE>(p, pl, stream);
-    case EPI_LS_RESID: return launch_cfg<EPI_LS_RESID>(p, pl, stream);
-    case EPI_QKV_PLANES: return launch_cfg<EPI_QKV_PLANES>(p, pl, stream);
-    case EPI_GELU_H2: return launch_cfg<EPI_GELU_H2>(p, pl, stream);
-    case EPI_SWIGLU_H2: return launch_cfg<EPI_SWIGLU_H2>(p, pl, stream);
-    case EPI_SWIGLU_T_H2: return launch_cfg<EPI_SWIGLU_T_H2>(p, pl, stream);
-    default: set_error("gemm_h3_small: epilogue %d has no small-M plan", epilogue); return ANYLOC_ERR_UNSUPPORTED;
-  }
+int gemm_h3_small(const H3Problem& p, int epilogue, const H3Plan& pl, hipStream_t stream) {
+  return with_constant<0, 1, 2, 3, 4, 5, 6, 7, 8, 9>(epilogue, [&](auto e) -> int {
+    constexpr int EPI = decltype(e)::value;
+    if constexpr (small_epilogue(EPI)) {
+      static_assert(NSMALL == 8);
+      return with_constant<0, 1, 2, 3, 4, 5, 6, 7>(pl.tile, [&](auto id) {
+        return with_constant<1, 2, 4>(pl.kb, [&](auto kb) {
+          return with_constant<3, 6>(pl.stages, [&](auto st) {
+            return launch_small<EPI, decltype(id)::value, decltype(kb)::value, decltype(st)::value>(p, pl, stream);
+          });
+        });
+      });
+    } else {
+      set_error("gemm_h3_small: epilogue %d has no small-M plan", EPI);
+      return ANYLOC_ERR_UNSUPPORTED;
+    }
+  });
 }
 
 }  // namespace anyloc

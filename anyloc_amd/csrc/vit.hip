@@ -185,7 +185,8 @@ int run(BlockGemm& g, int epi, hipStream_t stream, const float* gamma = nullptr)
       H3Problem& p = g.h3;
       if (!a.quantised) ANYLOC_TRY(split_h2(a.rows, a.K, a.M, a.K, a.img, a.inv, stream));
       p.gamma = gamma;
-      if (g.ln_x && h3_ln_lead_feasible(p, epi)) {
+      const H3Plan plan = h3_plan(p, epi, g.ln_x != nullptr);
+      if (plan.lead) {
         // the LayerNorm as the lead role of the GEMM's own launch (one image per call: LN1 + qkv, LN2 + w12) ...
         p.ln_x = g.ln_x; p.ln_w = g.ln_w; p.ln_b = g.ln_b; p.ln_eps = 1e-6f; p.ln_dim = (int)a.K;
         p.ln_has_bound = g.ln_bound != nullptr;
@@ -196,7 +197,7 @@ int run(BlockGemm& g, int epi, hipStream_t stream, const float* gamma = nullptr)
         ANYLOC_TRY(layernorm_h2(g.ln_x, g.ln_w, g.ln_b, a.M, (int)a.K, 1e-6f, a.img, a.inv, stream, g.ln_bound,
                                 g.ln_bound ? const_cast<float*>(p.c_inv) : nullptr));
       }
-      return gemm_h3(p, epi, stream);
+      return gemm_h3(p, epi, stream, &plan);
     }
   }
   return ANYLOC_ERR_INVALID_ARG;

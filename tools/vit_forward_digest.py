@@ -3,7 +3,8 @@ packed rows and of the offsets), ``ffn_exact_blocks`` after the call and the ``f
 library's profiler, every launch tag with its ``calls``, ``flops`` and ``bytes`` (computed by the launch wrappers from the
 shapes they were given: equal figures mean equal launch arguments; ``ms`` is left out).  Two builds whose outputs of this tool are
 byte-identical launch the same kernels on the same arguments and compute the same bits; the order of the launches inside
-one tag is not visible here, equal outputs cover it.
+one tag is not visible here, equal outputs cover it.  The last lines are ``ops.gemm_nt_h3`` on its own (``gemm_nt_h3/...``), one
+shape per route of the two-term fp16 GEMM's planner; which kernel and grid a launch got is tools/kernel_trace_launches.py's part.
 
     python tools/vit_forward_digest.py > digest.jsonl          # needs the GPU; ``--list`` prints the case names only
 
@@ -28,13 +29,23 @@ SHAPES = {"b1_224": ("uniform", 1, 224, 224),                             # smal
           "ragged3": ("ragged", [(224, 308), (322, 322), (140, 224)]),
           "b4_322": ("uniform", 4, 322, 322),                             # 2 120 token rows: above x6_min_rows
           "ragged3_big": ("ragged", [(322, 322), (448, 448), (224, 308)]),    # 1 908 token rows: the same
-          "b17_322": ("uniform", 17, 322, 322)}                           # 71 tile rows of 128: h3_ln_lead_feasible accepts
+          "b17_322": ("uniform", 17, 322, 322),                           # 71 tile rows of 128: the batched lead plan passes
+          "b1_322": ("uniform", 1, 322, 322),                             # 530 rows: the 192 x 128 w12 plan, split-K 2 on fc2
+          "b2_322": ("uniform", 2, 322, 322),                             # 1 060 rows: the two-image column of the plan table
+          "b1_476x630": ("uniform", 1, 476, 630)}                         # 1 531 rows: the plans of up to 1 700 rows
 TAPS = {"token_last": [(2, "token")],
         "value_last": [(2, "value")],                                     # the facet-only exit
         "key_token_last": [(2, "key"), (2, "token")],
         "q0_t1_v2_unordered": [(1, "token"), (2, "value"), (0, "query")]}
 # option sets of the h3 forward beyond the defaults (h3_swiglu_t is read when the model is built); x6_fuse rides on x6
 H3_OPTIONS = ({"h3_fuse": 0}, {"h3_patch": 0}, {"h3_swiglu_t": 0}, {"h3_min_rows": 1 << 20}, {"h3s_ln_lead": 1})
+# what decides how a two-term fp16 GEMM is launched, at the shapes of the small-M plan table
+H3_PLAN_OPTIONS = ({}, {"h3s_enable": 0}, {"h3s_w12_tall": 0}, {"h3_epi_lds": 0}, {"h3s_ln_lead": 1})
+# ops.gemm_nt_h3 on its own, hashed the same way: (M, N, K, options)
+GEMM_NT_H3 = ((4096, 4096, 4096, {}),                                     # 256 tiles of 256 x 256, K16 = 256: the 16 x 16 x 32 MFMA kernel
+              (4096, 4096, 4096, {"h3_mfma16": 0}),
+              (300, 700, 64, {}),                                         # small-M plan, no split-K buffers
+              (3000, 40000, 128, {}))                                     # batched default tile
 # weights: "synth" | "outlier" (synth.outlier_state_dict) | "loose" (one fc1 row of huge norm in block 1: the FFN bound of
 # every image trips).  threshold: None = the stock FFN_LOOSENESS_MAX; "between" = the middle of the images' own figures,
 # so that only some images are run again; "median" = the median of all (block, image) figures: several groups of blocks
@@ -70,6 +81,10 @@ def _cases():
         add("dinov2_vitg14", "h3", shape, "token_last", threshold="median")
         for gemm in GEMMS:
             add("dinov2_vits14", gemm, shape, "token_last", weights="outlier")
+    for model, opts, shape in itertools.product(MODELS, H3_PLAN_OPTIONS, ("b1_322", "b2_322", "b1_476x630")):
+        add(model, "h3", shape, "token_last", options=opts)
+    for opts in [{"h3_epi_lds": 0}] + [{"h3_cfg": c} for c in range(1, 6)]:
+        add("dinov2_vits14", "h3", "b4_322", "token_last", options=opts)
     for c in out:
         c["name"] = "/".join([c["model"], c["gemm"], c["shape"], c["taps"]] + (["cls"] if c["use_cls"] else []) +
                              (["norm_concat"] if c["norm_concat"] else []) + [f"{k}={v}" for k, v in c["options"].items()] +
@@ -110,8 +125,10 @@ def main():
     ap.add_argument("--only", default="", help="run the cases whose name contains this")
     args = ap.parse_args()
     cases = [c for c in CASES if args.only in c["name"]]
+    gemms = [(f"gemm_nt_h3/{M}x{N}x{K}" + "".join(f"/{k}={v}" for k, v in o.items()), M, N, K, o) for M, N, K, o in GEMM_NT_H3]
+    gemms = [g for g in gemms if args.only in g[0]]
     if args.list:
-        print("\n".join(c["name"] for c in cases))
+        print("\n".join([c["name"] for c in cases] + [g[0] for g in gemms]))
         return
     from anyloc_amd import extractor as ex, ops
     from anyloc_amd.extractor import HipDinoV2
@@ -159,6 +176,15 @@ def main():
         rec.update(ffn_exact_blocks=sorted(int(b) for b in m.ffn_exact_blocks), ffn_reruns=m.ffn_reruns - runs0, launches=launches)
         print(json.dumps(rec), flush=True)
         m.ffn_check = True
+    for name, M, N, K, opts in gemms:
+        a, w = (torch.randn(r, K, generator=torch.Generator().manual_seed(s)).to(dev) for r, s in ((M, 23), (N, 29)))
+        with ops.options(**opts):
+            a2, w2 = ops.split_h2(a), ops.split_h2(w)
+            ops.profile_reset()
+            out = ops.gemm_nt_h3(a2, w2, M, N, K)
+            torch.cuda.synchronize()
+            launches = {tag: {k: v[k] for k in ("calls", "flops", "bytes")} for tag, v in sorted(ops.profile_dump().items())}
+        print(json.dumps({"case": name, "sha256": _sha(out), "launches": launches}), flush=True)
 
 
 if __name__ == "__main__":
