@@ -51,6 +51,15 @@ class VitBlockH2(C.Structure):
                                                        ("fc1_layout", C.c_int32), ("reserved", C.c_int32)]
 
 
+H3_PLAN_FIELDS = ("mfma16", "route", "tile", "tile_rows", "tile_cols", "kb", "stages", "ksplit", "kper", "lead", "tiles_m", "tiles_n")
+H3_PLAN_SPLIT_WS, H3_PLAN_ACCUMULATE, H3_PLAN_LN_IN_FRONT = 1, 2, 4
+
+
+class H3PlanDesc(C.Structure):
+    """anyloc_h3_plan_desc: the answer of the host-only anyloc_h3_plan_describe"""
+    _fields_ = [(n, C.c_int32) for n in H3_PLAN_FIELDS] + [("grid", C.c_int64)]
+
+
 # name -> (restype, argtypes); also the list the symbol-export test checks
 SIGNATURES = {
     "anyloc_version": (C.c_int, []),
@@ -74,6 +83,7 @@ SIGNATURES = {
     "anyloc_gemm_nt_h3": (C.c_int, [C.c_void_p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_i64, c_i64, c_i64, c_i64,
                                     C.c_void_p]),
     "anyloc_h3_lead_plan_check": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, c_i64, C.POINTER(C.c_uint32)]),
+    "anyloc_h3_plan_describe": (C.c_int, [c_i64, c_i64, c_i64, C.c_char_p, C.c_int32, C.c_uint32, C.POINTER(H3PlanDesc)]),
     "anyloc_gemm_nt": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_f32p, c_i64,
                                  c_i64, c_i64, c_i64, C.c_void_p]),
     "anyloc_layernorm": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i64, C.c_float, C.c_void_p]),

@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <array>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -625,6 +626,37 @@ extern "C" int anyloc_h3_lead_plan_check(int32_t tiles_m, int32_t tiles_n, int32
   const int ok = anyloc::h3_lead_plan_check(tiles_m, tiles_n, group_m, M, &g);
   if (grid) *grid = g;
   return ok;
+}
+
+// host-only: the fields of an H3Problem that h3_plan reads, h3_plan, and the plan with its tile's shape -- nothing else
+extern "C" int anyloc_h3_plan_describe(int64_t M, int64_t N, int64_t K, const char* epilogue, int32_t kind, uint32_t flags,
+                                       anyloc_h3_plan_desc* out) {
+  static const char* const names[] = {"store", "gelu", "ls_resid", "swiglu", "patch", "qkv_planes", "gelu_h2", "swiglu_h2", "swiglu_t",
+                                      "swiglu_t_h2"};
+  static_assert(EPI_STORE == 0 && EPI_GELU == 1 && EPI_LS_RESID == 2 && EPI_SWIGLU == 3 && EPI_PATCH == 4 && EPI_QKV_PLANES == 5 &&
+                    EPI_GELU_H2 == 6 && EPI_SWIGLU_H2 == 7 && EPI_SWIGLU_T == 8 && EPI_SWIGLU_T_H2 == 9,
+                "names[] is indexed by the epilogue");
+  ANYLOC_CHECK_ARG(out && epilogue, "h3_plan_describe: null pointer");
+  ANYLOC_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 16 == 0 && K / 16 <= INT32_MAX, "h3_plan_describe: bad shape %lld x %lld x %lld",
+                   (long long)M, (long long)N, (long long)K);
+  ANYLOC_CHECK_ARG(kind >= H3_KIND_OTHER && kind <= H3_KIND_FC2, "h3_plan_describe: kind %d", kind);
+  ANYLOC_CHECK_ARG((flags & ~7u) == 0, "h3_plan_describe: unknown flags %u", flags);
+  int epi = -1;
+  for (int i = 0; i < 10; ++i)
+    if (std::strcmp(epilogue, names[i]) == 0) epi = i;
+  ANYLOC_CHECK_ARG(epi >= 0, "h3_plan_describe: unknown epilogue \"%s\"", epilogue);
+  static float part_at_hand;                 // h3_plan asks whether the split-K buffers are there, never what they hold
+  static unsigned tickets_at_hand;
+  H3Problem p{};
+  p.M = M; p.N = N; p.K16 = (int)(K / 16); p.kind = kind;
+  if (flags & ANYLOC_H3_PLAN_SPLIT_WS) { p.sk_part = &part_at_hand; p.sk_tickets = &tickets_at_hand; }
+  p.accumulate = (flags & ANYLOC_H3_PLAN_ACCUMULATE) ? 1 : 0;
+  const H3Plan pl = h3_plan(p, epi, (flags & ANYLOC_H3_PLAN_LN_IN_FRONT) != 0);
+  const H3Tile t = pl.route == H3_ROUTE_SMALL ? kSmallTile[pl.tile] : kH3Tile[pl.tile];
+  out->mfma16 = pl.mfma16; out->route = pl.route; out->tile = pl.tile; out->tile_rows = t.bm(); out->tile_cols = t.bn();
+  out->kb = pl.kb; out->stages = pl.stages; out->ksplit = pl.ksplit; out->kper = pl.kper; out->lead = pl.lead;
+  out->tiles_m = pl.tiles_m; out->tiles_n = pl.tiles_n; out->grid = (int64_t)pl.grid;
+  return ANYLOC_OK;
 }
 
 extern "C" int anyloc_split_h2(const float* x, int64_t ldx, int64_t rows, int64_t K, void* h2, float* inv_scale, void* stream) {

@@ -178,6 +178,29 @@ int anyloc_gemm_nt_h3(const void* a2, const float* a_inv, const void* w2,
  * once, every row normalised exactly once, every producer ahead of its consumers in workgroup-id order.  Returns 1 when the plan
  * passes (and *grid = workgroups of the launch), 0 when the forward keeps LayerNorm as a launch of its own for this shape. */
 int anyloc_h3_lead_plan_check(int32_t tiles_m, int32_t tiles_n, int32_t group_m, int64_t M, uint32_t* grid);
+/* Additive to ABI 10 (diagnostic, host only -- no device is touched): how ONE launch of the two-term fp16 GEMM would run.  The
+ * library's plan function (csrc/gemm_h3s.hip: h3_plan) decides tile shape, k-blocks per ring stage, ring depth, split-K factor,
+ * route and the LayerNorm lead role from the shape, the epilogue and the options; this call builds the problem fields that function
+ * reads, calls it, and returns its answer with the tile's rows / columns.
+ *   M, N, K    C [M, N] = A [M, K] W [N, K]^T, K a multiple of 16
+ *   epilogue   "store" "ls_resid" "qkv_planes" "gelu_h2" "swiglu_h2" "swiglu_t_h2" "gelu" "swiglu" "swiglu_t" "patch"
+ *   kind       which block GEMM of the ViT forward (option h3s_mask): 0 other, 1 qkv, 2 proj (and the facet GEMM), 3 fc1 / w12, 4 fc2
+ *   flags      ANYLOC_H3_PLAN_SPLIT_WS: the split-K workspace is at hand (the fused forward's block GEMMs have it);
+ *              ANYLOC_H3_PLAN_ACCUMULATE: the launch adds into C (one K chunk of a longer contraction);
+ *              ANYLOC_H3_PLAN_LN_IN_FRONT: a LayerNorm writes this GEMM's operand image and may travel as the launch's lead role
+ *   out (host) route 0 = the small-M plan table (tile = id of its shapes), 1 = the two fixed shapes of the epilogues without
+ *              small-M plans, 2 = the batched shapes (option h3_cfg); lead 0 = none, 1 = small-M, 2 = batched; kper = k-blocks of
+ *              16 per split-K range; grid = workgroups of the launch, lead workgroups included
+ * Returns ANYLOC_ERR_INVALID_ARG for an unknown epilogue name, kind or flag and for sizes that are not positive. */
+#define ANYLOC_H3_PLAN_SPLIT_WS 1u
+#define ANYLOC_H3_PLAN_ACCUMULATE 2u
+#define ANYLOC_H3_PLAN_LN_IN_FRONT 4u
+typedef struct anyloc_h3_plan_desc {
+  int32_t mfma16, route, tile, tile_rows, tile_cols, kb, stages, ksplit, kper, lead, tiles_m, tiles_n;
+  int64_t grid;
+} anyloc_h3_plan_desc;
+int anyloc_h3_plan_describe(int64_t M, int64_t N, int64_t K, const char* epilogue, int32_t kind, uint32_t flags,
+                            anyloc_h3_plan_desc* out /*host*/);
 
 /* ------------------------------------------------------------ pooling ----
  * One global descriptor per image from its patch tokens, without VLAD:
