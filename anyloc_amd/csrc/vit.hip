@@ -322,6 +322,9 @@ int anyloc_vit_attach_h2(anyloc_vit_t* h, const anyloc_vit_block_h2* blocks) {
   // device is current), every temporary freed on every path; the handle changes only when all of it succeeded -- a failed
   // attach leaves the handle as it was before the call, minus the previous patch image (already dropped above, with the
   // previous h2 blocks detached by the clear() below).
+  // The call has no stream argument and the caller's patch_w may still be in flight on ANY stream (a non-blocking stream is
+  // not ordered against the null stream): the device is drained first, the null stream once more before the temporaries
+  // go -- construction time, the one place of this file that synchronises (include/anyloc_hip.h, "Streams").
   h->h2.clear();
   h->ffn_exact.assign(h->cfg.depth, 0);      // the exact-quantiser switches belong to the weights that are being replaced
   const int64_t D = h->cfg.dim, K0 = h->cfg.patch_k_pad, Kp = (K0 + 15) / 16 * 16;
@@ -344,7 +347,8 @@ int anyloc_vit_attach_h2(anyloc_vit_t* h, const anyloc_vit_block_h2* blocks) {
     }
     return e == hipSuccess;
   };
-  if (hip_ok(hipMalloc(reinterpret_cast<void**>(&padded), sizeof(float) * D * Kp), "hipMalloc (padded patch weights)") &&
+  if (hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize") &&
+      hip_ok(hipMalloc(reinterpret_cast<void**>(&padded), sizeof(float) * D * Kp), "hipMalloc (padded patch weights)") &&
       hip_ok(hipMalloc(reinterpret_cast<void**>(&w2), h2_bytes(D, Kp)), "hipMalloc (patch-embedding image)") &&
       hip_ok(hipMalloc(reinterpret_cast<void**>(&winv), sizeof(float) * D), "hipMalloc (patch-embedding row scales)") &&
       hip_ok(hipMemset(padded, 0, sizeof(float) * D * Kp), "hipMemset") &&

@@ -323,7 +323,7 @@ class HipDinoV2:
             if flat.numel() != pix[-1]:
                 raise ValueError(f"packed buffer holds {flat.numel()} floats, the sizes need {int(pix[-1])}")
             taps, inv = self._ascending(taps)
-            offsets = torch.from_numpy(out_off).to(self.device)
+            offsets = ops.table_to_device(torch.from_numpy(out_off), self.device)
             chunks = ragged_chunks(sizes, self.max_rows, registers=self.n_reg)
             # one chunk (the common case): the forward writes the caller's result directly; several: into slices of it
             out = None if len(chunks) == 1 and inv is None else \

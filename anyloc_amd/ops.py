@@ -41,6 +41,15 @@ def to_host(t):
     return t.cpu()
 
 
+def table_to_device(t, device):
+    """A small HOST table (offsets, index lists) -> device without waiting for the stream: staged in pinned memory and copied
+    non-blocking.  A plain ``.to(device)`` of pageable memory synchronises the current stream, i.e. the caller would wait for
+    everything enqueued before the call."""
+    if torch.device(device).type == "cpu":
+        return t
+    return t.pin_memory().to(device, non_blocking=True)
+
+
 def _f32c(t, device=None):
     """-> contiguous fp32 tensor (on ``device`` when given: ``to_device``, at the PCIe rate here); a dtype conversion
     happens on the device, after the copy."""
@@ -223,7 +232,7 @@ def _offsets_for(tokens_list_or_tensor, device):
         offsets = torch.zeros(n_img + 1, dtype=torch.int64)
         if n_img:
             offsets[1:] = torch.cumsum(torch.tensor(counts, dtype=torch.int64), 0)
-    return packed, offsets.to(device), n_img, D
+    return packed, table_to_device(offsets, device), n_img, D
 
 
 def vlad_auto_parts(n_img, n_tok_total, D, K):
@@ -353,7 +362,10 @@ def pool(tokens, method="average", gem_p=3.0):
     else:
         packed, offsets, n_img, D = _offsets_for(tokens, device)
         n_tok = -1
-        empty = bool(n_img) and bool((offsets[1:] == offsets[:-1]).any())
+        if is_packed_pair(tokens):               # offsets that live on the device: the one host read of this function
+            empty = bool(n_img) and bool((offsets[1:] == offsets[:-1]).any())
+        else:
+            empty = any(len(p) == 0 for p in tokens)
     if n_img == 0:
         return torch.empty(0, D, dtype=torch.float32, device=device)
     if empty and POOL_MODES[method] == 1:

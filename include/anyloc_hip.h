@@ -13,8 +13,27 @@
  *     parameter is documented "host"; the library never returns memory it
  *     allocated; sizes are explicit; tensors are dense row-major fp32 unless
  *     stated; indices / labels are int64 (the reference's torch.long).
- *   - `stream` is a hipStream_t passed as void* (NULL = the null stream).  All
- *     work is enqueued on it; no call synchronises the device.
+ *   - Streams.  `stream` is a hipStream_t passed as void* (NULL = the null
+ *     stream).  ALL device work of a call -- kernels, memsets, copies -- is
+ *     enqueued on it, in order: inputs must be ready in stream order, results
+ *     are ready in stream order, and the workspace may be reused by the next
+ *     call on the same stream (two streams need two workspaces).  A call
+ *     returns without waiting for the device, with these exceptions:
+ *       anyloc_topk, anyloc_topk_search_index, anyloc_topk_search_index_rows
+ *         when the SCREENED search serves the shape (option topk_screen):
+ *         one 4-byte flag is read back, the call waits for `stream` (never
+ *         for the device) before it finishes or re-runs unscreened;
+ *       anyloc_vit_attach_h2 (no stream argument, construction time) waits
+ *         for the whole DEVICE, quantises the patch weights on the null
+ *         stream and waits for that.
+ *     The other construction calls (anyloc_vit_create, anyloc_vit_attach_x3,
+ *     anyloc_vit_set_registers, like anyloc_vit_set_telemetry and
+ *     anyloc_vit_block_ffn_exact) do no device work at all: they store
+ *     pointers that later forwards read in THEIR stream order.  A handle
+ *     holds per-handle state (the attached images, the telemetry target, the
+ *     exact-quantiser switches): one forward at a time per handle.
+ *     tests/test_gpu_streams.py holds every entry point to this, op by op;
+ *     tests/test_stream_contract_cpu.py keeps blocking calls out of the sources.
  *   - scratch space is caller-provided: query the size with the matching
  *     *_workspace_bytes() and pass a buffer at least that large.
  *   - return value: 0 on success, a negative anyloc_status otherwise;
@@ -366,7 +385,10 @@ int anyloc_kmeans_update(const float* sums, const float* counts, const float* ce
  *   row / max(||row||_2, 1e-12), i.e. the F.normalize(db) of utilities.py:436 is applied to the
  *   scores instead of materialising a normalised copy of the database (queries are taken as given).
  *   With <= 64 queries of >= 4096 dimensions the database is streamed once by a split-K launch
- *   (HBM-bound); otherwise scores are fp32-MFMA GEMM panels (MFMA-bound). */
+ *   (HBM-bound); otherwise scores are fp32-MFMA GEMM panels (MFMA-bound).
+ *   Streams: where the screened search runs (option topk_screen: by default >= 256 queries x >= 16 384 rows x >= 4096
+ *   columns on the fp16 panels) the call synchronises with `stream` once -- it waits for its 4-byte overflow flag
+ *   (see anyloc_topk_search_index_rows); every other shape returns without waiting. */
 #define ANYLOC_TOPK_NORMALIZE_DB 1u
 size_t anyloc_topk_workspace_bytes(int64_t nq, int64_t ndb, int64_t dim, int64_t k);
 int anyloc_topk(const float* queries, int64_t nq, const float* db, int64_t ndb,
@@ -387,6 +409,8 @@ int anyloc_topk_path(int64_t nq, int64_t ndb, int64_t dim);   /* which scoring p
 size_t anyloc_topk_index_bytes(int64_t ndb, int64_t dim);
 int anyloc_topk_index_build(const float* db, int64_t ndb, int64_t dim, void* index, size_t index_bytes, void* stream);
 size_t anyloc_topk_index_workspace_bytes(int64_t nq, int64_t ndb, int64_t dim, int64_t k);
+/* Streams: with ANYLOC_TOPK_RESCORE_PLANES on a screened shape the call waits for `stream` once (the overflow flag of the
+ * screened search, below); otherwise it returns without waiting. */
 int anyloc_topk_search_index(const float* queries, int64_t nq, const void* index, int64_t ndb, int64_t dim, int64_t k,
                              int metric, unsigned flags, int64_t index_base, float* dist, int64_t* idx, void* workspace,
                              size_t workspace_bytes, void* stream);
@@ -399,7 +423,9 @@ int anyloc_topk_search_index(const float* queries, int64_t nq, const void* index
  * ANYLOC_TOPK_NORMALIZE_DB, the largest raw row norm without it: rows of very different raw norms make it loose).  k <= 128, dim <= 49 152; a query
  * with more than 512 rows inside its bound makes the call run the unscreened search instead (one 4-byte read-back per call decides).
  * Lists: the rows of the exact search; distances within 1e-6 of it (more accurate, not bit-identical).  db == NULL: as
- * anyloc_topk_search_index. */
+ * anyloc_topk_search_index.
+ * Streams: that read-back makes a screened call synchronise with `stream` (hipStreamSynchronize, on every screened call):
+ * the host waits for everything enqueued on `stream` before the call, other streams are not waited for. */
 int anyloc_topk_search_index_rows(const float* queries, int64_t nq, const float* db, const void* index, int64_t ndb, int64_t dim,
                                   int64_t k, int metric, unsigned flags, int64_t index_base, float* dist, int64_t* idx,
                                   void* workspace, size_t workspace_bytes, void* stream);
@@ -432,7 +458,9 @@ int anyloc_topk_index_build_range(const float* rows, int64_t row0, int64_t nrows
  *   model forward at :269, the hooked facet at :270-281, F.normalize at :283).
  * Weights are caller-owned device tensors in torch Linear layout
  * ([out,in] row-major), handed over once at creation; the handle stores the
- * pointers, it does not copy.  */
+ * pointers, it does not copy.  anyloc_vit_create launches nothing and reads no
+ * device memory: the weights need only be ready, in stream order, for the
+ * first forward (likewise anyloc_vit_attach_x3 and anyloc_vit_set_registers).  */
 typedef struct anyloc_vit anyloc_vit_t;
 
 typedef struct anyloc_vit_block_weights {
@@ -508,6 +536,11 @@ typedef struct anyloc_vit_block_h2 {
   int32_t fc1_layout;
   int32_t reserved;
 } anyloc_vit_block_h2;
+/* Streams: this call synchronises the DEVICE.  It also builds the operand image of the patch-embedding weights (patch_w of
+ * anyloc_vit_create) into memory of its own: it has no stream argument, so it waits for all work on the device first -- the
+ * caller's patch_w may still be in flight on any stream --, quantises on the null stream and waits for that; every later
+ * forward, on any stream, finds the image finished.  Construction time, not the hot path.  blocks == NULL (detach) frees
+ * that image (hipFree). */
 int anyloc_vit_attach_h2(anyloc_vit_t* h, const anyloc_vit_block_h2* blocks /*host array [depth]*/);
 
 /* FFN-bound telemetry of the two-term fp16 forward (ABI 5; per image and without an extra pass over the image since ABI 8).
