@@ -125,6 +125,9 @@ SIGNATURES = {
     "anyloc_vit_attach_x3": (C.c_int, [C.c_void_p, C.POINTER(VitBlockX3)]),
     "anyloc_vit_attach_h2": (C.c_int, [C.c_void_p, C.POINTER(VitBlockH2)]),
     "anyloc_vit_set_registers": (C.c_int, [C.c_void_p, c_f32p, C.c_int32]),
+    "anyloc_vit_set_rope": (C.c_int, [C.c_void_p, C.c_int32]),
+    "anyloc_vit_set_ln_eps": (C.c_int, [C.c_void_p, C.c_float]),
+    "anyloc_rope_rows": (C.c_int, [c_f32p, c_i64, c_i64, c_f32p, c_i64, c_i64, C.c_void_p, C.c_int32, C.c_void_p]),
     "anyloc_vit_set_telemetry": (C.c_int, [C.c_void_p, c_f32p, C.c_int32]),
     "anyloc_vit_block_ffn_exact": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "anyloc_vit_workspace_bytes": (c_sz, [C.c_void_p, c_i64, c_i64, c_i64]),

@@ -196,8 +196,14 @@ enum GemmEpilogue {
   // gemm_h3 only, weights in the 16-channel block layout (anyloc_vit_block_h2.fc1_layout = 1): the product is formed
   // transposed (weights as the MFMA A operand), a lane holds one token and 8 consecutive gate / value channels
   EPI_SWIGLU_T = 8,   // C[:, n/2] = silu(gate) * value as fp32
-  EPI_SWIGLU_T_H2 = 9 // ... as the h2 image of the next GEMM, 16-byte chunks straight from the accumulators
+  EPI_SWIGLU_T_H2 = 9,// ... as the h2 image of the next GEMM, 16-byte chunks straight from the accumulators
+  // gemm_h3 only, rotary models (DINOv3): EPI_QKV_PLANES with the q and k columns of the patch rows rotated (H3Problem::rope)
+  // between descale + bias and the tile's maximum.  An epilogue of its own so that the kernels of EPI_QKV_PLANES stay the
+  // code they were; it has the plans of EPI_QKV_PLANES (plan_epilogue)
+  EPI_QKV_PLANES_ROPE = 10
 };
+// the epilogue whose plans (tile shape, ring, split-K, lead role) an epilogue runs on
+constexpr int plan_epilogue(int epi) { return epi == EPI_QKV_PLANES_ROPE ? EPI_QKV_PLANES : epi; }
 
 struct GemmProblem {
   const float* A; int64_t lda;
@@ -251,6 +257,39 @@ int gemm_x6(const X6Problem& p, int epilogue, hipStream_t stream);
 int layernorm_x3(const float* x, const float* w, const float* b, int64_t rows, int dim, float eps, void* x3,
                  hipStream_t stream);
 
+// Rotary positions (DINOv3): which rotation a token row of a forward gets.  table = fp32 rows of 64, cos[0..31] | sin[0..31]
+// of one patch each (the angles of columns d and d + 32 of a head are equal), the same for every head and block.  Token row
+// `row` is row t of image i; t < prefix (CLS and the registers) is not rotated, otherwise patch t - prefix of image i's table.
+// meta == nullptr: a uniform batch, i = row / T, one table; otherwise the ragged table of the call (RAGGED_TOK gives i, and
+// RAGGED_POS the first ROW of image i's table in the packed tables)
+struct RopeRows {
+  const float* table;
+  const int64_t* meta; int n_img;
+  int T, prefix;
+};
+// the image whose rows [off(i), off(i+1)) hold row r, off(i) = tok[i] - sub * i (strictly ascending for sub <= 1 + R)
+__device__ __forceinline__ int ragged_image(const int64_t* __restrict__ tok, int n_img, int64_t r, int sub) {
+  int lo = 0, hi = n_img - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tok[mid] - (int64_t)sub * mid <= r) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+// -> the 64 floats of `row`'s rotation, or nullptr for a prefix row.  hint: an image at or before the row's (ragged: a walk
+// from there instead of a search; 0 is always valid)
+__device__ __forceinline__ const float* rope_row(const RopeRows& rp, int64_t row, int hint = 0) {
+  if (!rp.meta) {
+    const int t = (int)(row % rp.T) - rp.prefix;
+    return t < 0 ? nullptr : rp.table + (int64_t)t * 64;
+  }
+  int i = hint;
+  while (i + 1 < rp.n_img && rp.meta[i + 1] <= row) ++i;
+  const int64_t t = row - rp.meta[i] - rp.prefix;
+  return t < 0 ? nullptr : rp.table + (rp.meta[2 * (int64_t)(rp.n_img + 1) + i] + t) * 64;
+}
+
 // row-scaled two-term fp16 GEMM on two-plane operand images (gemm_h3.hip)
 struct H3Problem {
   const unsigned char* A2; int64_t RA; const float* a_inv;   // image of A [M, 16*K16], rows of the image, 2^-e per row
@@ -275,6 +314,8 @@ struct H3Problem {
   const float* pos; int patches;            // EPI_PATCH: position table [patches + 1, N]; row b * patches + p -> C row b * (patches + 1) + 1 + p
   // EPI_QKV_PLANES: N = 3 * heads * 64; see QkvPlanes below
   unsigned char* qkv_planes; float* qkv_inv; int heads; int64_t groups;
+  // EPI_QKV_PLANES_ROPE: the rotation table(s) of the call (RopeRows below)
+  RopeRows rope;
   // EPI_GELU_H2 / EPI_SWIGLU_H2: output image (RC rows) quantised with the given per-row 2^-e (c_inv[row])
   unsigned char* C2; int64_t RC; const float* c_inv;
   // FFN-bound telemetry (optional): c_max[row] = bits of the largest scaled magnitude the row holds in the output image, merged by
@@ -395,13 +436,18 @@ int attention(const float* qkv, float* out, int64_t batch, int T, int D, int hea
 //   RAGGED_TOK: token-row offsets (T_i = 1 + R + N_i rows per image: CLS, R registers, patches), entry n_img = total rows
 //   RAGGED_PIX: float offset of image i in the packed CHW input, RAGGED_POS: first row of image i's positional table in the
 //   packed tables, RAGGED_H / RAGGED_W: the image size (last entry of these three unused)
+//   (a rotary model has rotation tables instead: RAGGED_POS = first row of image i's [N_i, 64] table in the packed tables)
 enum { RAGGED_TOK = 0, RAGGED_PIX = 1, RAGGED_POS = 2, RAGGED_H = 3, RAGGED_W = 4, RAGGED_ROWS = 5 };
+static_assert(RAGGED_TOK == 0 && RAGGED_POS == 2, "rope_row reads rows 0 and 2 of the table");
 int im2col_ragged(const float* img, float* col, const int64_t* meta, int n_img, int R, int64_t patch_rows, int P, int kpad,
                   hipStream_t stream);
 // the token rows from the patch GEMM's output [P, D]: CLS + pos[0], R register rows, patch + pos rows.  meta == nullptr: a
 // uniform batch of T-row images sharing the table pos; otherwise the ragged table (T unused)
+// pos == nullptr (rotary models): no positional term anywhere
 int embed_rows(float* x, const float* patch, const float* cls, const float* reg, int R, const float* pos, const int64_t* meta,
                int n_img, int T, int64_t rows, int dim, hipStream_t stream);
+// the rotation of RopeRows in place on the q and k thirds of fp32 qkv [rows, 3 * heads * 64] (v and the prefix rows untouched)
+int rope_rows(float* qkv, int64_t rows, int heads, const RopeRows& rp, hipStream_t stream);
 int facet_rows_ragged(const float* src, int64_t lds_, int coff, float* out, int64_t ldo, int ooff, const int64_t* meta,
                       int n_img, int64_t out_rows, int skip, int gap, int dim, int normalize, float eps, hipStream_t stream);
 // attention over images of different lengths: tok_off = device [n_img + 1] row offsets, max_T the longest image

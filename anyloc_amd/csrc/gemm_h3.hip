@@ -592,6 +592,13 @@ int gemm_h3(const H3Problem& p_in, int epilogue, hipStream_t stream, const H3Pla
                            p.groups == (p.M + 31) / 32,
                        "gemm_h3: QKV_PLANES needs N = 3 * heads * 64, D %% 128 == 0 and groups = ceil(M / 32)");
       return launch_planned<EPI_QKV_PLANES>(p, pl, stream);
+    case EPI_QKV_PLANES_ROPE:
+      ANYLOC_CHECK_ARG(p.qkv_planes && p.qkv_inv && p.heads > 0 && p.N == 3ll * p.heads * 64 && (p.heads * 64) % 128 == 0 &&
+                           p.groups == (p.M + 31) / 32,
+                       "gemm_h3: QKV_PLANES_ROPE needs N = 3 * heads * 64, D %% 128 == 0 and groups = ceil(M / 32)");
+      ANYLOC_CHECK_ARG(p.rope.table && p.rope.prefix >= 0 && (p.rope.meta ? p.rope.n_img > 0 : p.rope.T > p.rope.prefix),
+                       "gemm_h3: QKV_PLANES_ROPE needs the rotation table and the row layout of the call");
+      return launch_planned<EPI_QKV_PLANES_ROPE>(p, pl, stream);
     case EPI_GELU_H2:
       ANYLOC_CHECK_ARG(p.C2 && p.c_inv && p.RC >= p.M && p.N % 64 == 0, "gemm_h3: GELU_H2 needs an output image, c_inv and N %% 64 == 0");
       return launch_planned<EPI_GELU_H2>(p, pl, stream);

@@ -676,7 +676,8 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void gemm_h3_kernel(H3Problem p,
       return;
     }
   }
-  if constexpr (EPI == EPI_QKV_PLANES) {
+  if constexpr (EPI == EPI_QKV_PLANES || EPI == EPI_QKV_PLANES_ROPE) {
+    constexpr bool ROPE = EPI == EPI_QKV_PLANES_ROPE;
     // q | k | v leave the kernel as the per-(head, 32-row group) two-plane fp16 tiles of attention_h3 (layout: common.hpp).
     // A wave owns 32 MI rows x 32 NI columns = MI row groups x NI/2 heads of ONE part (D % (32 NI) == 0).  v tiles are
     // written straight from the C/D layout (a lane holds one d and the 16 rows of its half in exactly the order the
@@ -698,6 +699,22 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void gemm_h3_kernel(H3Problem p,
         const int64_t row = wrow0 + mi * 32 + (r & 3) + 8 * (r >> 2);
         ai[r] = row < p.M ? p.a_inv[row] : 0.0f;
       }
+      // ROPE, q and k: a lane holds columns d = lane & 31 (v[0]) and d + 32 (v[1]) of a head for its 16 rows -- the pair
+      // rotate_half joins -- so the rotation is lane-local; the angles depend on the row alone (one table for every head):
+      // cos / sin of the lane's 16 rows, 1 / 0 for the prefix rows (CLS, registers) and the rows beyond M
+      float rc[ROPE ? 16 : 1], rs[ROPE ? 16 : 1];
+      if constexpr (ROPE) {
+        if (part < 2) {
+          const int img0 = p.rope.meta ? ragged_image(p.rope.meta, p.rope.n_img, rb, 0) : 0;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int64_t row = wrow0 + mi * 32 + (r & 3) + 8 * (r >> 2);
+            const float* tab = row < p.M ? rope_row(p.rope, row, img0) : nullptr;
+            rc[r] = tab ? tab[lane & 31] : 1.0f;
+            rs[r] = tab ? tab[32 + (lane & 31)] : 0.0f;
+          }
+        }
+      }
 #pragma unroll
       for (int hh = 0; hh < NI / 2; ++hh) {
         float v[2][16];
@@ -709,8 +726,20 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void gemm_h3_kernel(H3Problem p,
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             v[nb][r] = ai[r] != 0.0f ? acc[mi][2 * hh + nb][r] * (ai[r] * sw_) + bv : 0.0f;
-            amax = fmaxf(amax, fabsf(v[nb][r]));
+            if constexpr (!ROPE) amax = fmaxf(amax, fabsf(v[nb][r]));
           }
+        }
+        if constexpr (ROPE) {
+          if (part < 2) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const float a = v[0][r], b = v[1][r];
+              v[0][r] = a * rc[r] - b * rs[r];
+              v[1][r] = b * rc[r] + a * rs[r];
+            }
+          }
+#pragma unroll
+          for (int r = 0; r < 16; ++r) amax = fmaxf(amax, fmaxf(fabsf(v[0][r]), fabsf(v[1][r])));
         }
         amax = wave_max(amax);
         float inv;
@@ -963,16 +992,19 @@ constexpr int small_stages(H3Tile t, int kb, int stages) {
 }
 // the epilogues that have small-M plans (the others: kH3Tile 6 / 7)
 constexpr bool small_epilogue(int epi) {
+  epi = plan_epilogue(epi);
   return epi == EPI_STORE || epi == EPI_LS_RESID || epi == EPI_QKV_PLANES || epi == EPI_GELU_H2 || epi == EPI_SWIGLU_H2 ||
          epi == EPI_SWIGLU_T_H2;
 }
 // the plans the small-M LayerNorm lead role (LNL = 1) is compiled for: the one-image qkv plan (128 x 128, 6-deep ring) and the
 // one-image w12 plan (192 x 128, 6-deep ring), with the epilogues those two GEMMs have in the fused forward
 constexpr bool small_lead_compiled(int epi, int tile, int kb, int stages) {
+  epi = plan_epilogue(epi);
   return kb == 1 && stages == 6 && ((tile == 4 && epi == EPI_QKV_PLANES) || (tile == 7 && (epi == EPI_SWIGLU_T_H2 || epi == EPI_SWIGLU_H2)));
 }
 // the epilogues the batched lead role (LNL = 2, kH3Tile[0]) is compiled for
 constexpr bool batched_lead_compiled(int epi) {
+  epi = plan_epilogue(epi);
   return epi == EPI_QKV_PLANES || epi == EPI_SWIGLU_T_H2 || epi == EPI_SWIGLU_H2 || epi == EPI_GELU_H2;
 }
 

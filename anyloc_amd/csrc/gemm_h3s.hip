@@ -93,6 +93,7 @@ int launch_small(const H3Problem& p, const H3Plan& pl, hipStream_t stream) {
 }  // namespace
 
 H3Plan h3_plan(const H3Problem& p, int epilogue, bool ln_in_front) {
+  epilogue = plan_epilogue(epilogue);
   H3Plan pl{};
   pl.kb = 1; pl.ksplit = 1; pl.kper = p.K16;
   // option h3_cfg (micro-benchmarks): 0 = 128x256 tile, 3-deep ring (default; the small-M plans when there are few tiles);
@@ -155,7 +156,7 @@ H3Plan h3_plan(const H3Problem& p, int epilogue, bool ln_in_front) {
 }
 
 int gemm_h3_small(const H3Problem& p, int epilogue, const H3Plan& pl, hipStream_t stream) {
-  return with_constant<0, 1, 2, 3, 4, 5, 6, 7, 8, 9>(epilogue, [&](auto e) -> int {
+  return with_constant<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10>(epilogue, [&](auto e) -> int {
     constexpr int EPI = decltype(e)::value;
     if constexpr (small_epilogue(EPI)) {
       static_assert(NSMALL == 8);

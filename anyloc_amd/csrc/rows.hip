@@ -138,17 +138,6 @@ __global__ __launch_bounds__(256) void facet_rows_kernel(const float* __restrict
 // owns token rows tok[i] .. tok[i+1], patch rows tok[i] - i(1+R) .. tok[i+1] - (i+1)(1+R) - 1 and output rows from
 // tok[i] - i(1+R) (tok[i] - iR with the CLS row)
 
-// the image whose rows [off(i), off(i+1)) hold row r, off(i) = tok[i] - sub * i (strictly ascending for sub <= 1 + R)
-__device__ __forceinline__ int ragged_image(const int64_t* __restrict__ tok, int n_img, int64_t r, int sub) {
-  int lo = 0, hi = n_img - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tok[mid] - (int64_t)sub * mid <= r) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 // col[patch row, c*P*P + i*P + j] = img_i[c, py*P + i, px*P + j] for the image i that owns the patch row (R register rows
 // per image: patch rows of image i from tok[i] - i(1+R))
 __global__ __launch_bounds__(256) void im2col_ragged_kernel(const float* __restrict__ img, float* __restrict__ col,
@@ -195,9 +184,33 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(float* __restrict__ x, 
     for (int k = threadIdx.x; k < dim; k += 256) dst[k] = rr[k];
     return;
   }
-  const float* pr = pb + (t == 0 ? 0 : t - R) * dim;
   const float* sr = t == 0 ? cls : patch + (row - (i + 1) * (1 + R)) * dim;
+  if (!pos) {                                   // a rotary model: no positional term
+    for (int k = threadIdx.x; k < dim; k += 256) dst[k] = sr[k];
+    return;
+  }
+  const float* pr = pb + (t == 0 ? 0 : t - R) * dim;
   for (int k = threadIdx.x; k < dim; k += 256) dst[k] = sr[k] + pr[k];
+}
+
+// Rotary positions in place on fp32 qkv [rows, 3 D], D = heads * 64: for q and k of every head of a patch row
+//   x'[d] = x[d] cos[d] - x[d + 32] sin[d],   x'[d + 32] = x[d + 32] cos[d] + x[d] sin[d]      (d < 32)
+// (transformers modeling_dinov3_vit.py apply_rotary_pos_emb: q * cos + rotate_half(q) * sin with cos[d + 32] = cos[d]; the two
+// products and the sum round as torch's do).  One block per row; a thread owns pairs (d, d + 32) of the 2 * heads (part, head)
+// slots.  Prefix rows (CLS, registers) and the v third are not touched.
+__global__ __launch_bounds__(256) void rope_rows_kernel(float* __restrict__ qkv, int heads, RopeRows rp) {
+  const int64_t row = blockIdx.x;
+  const float* tab = rope_row(rp, row, rp.meta ? ragged_image(rp.meta, rp.n_img, row, 0) : 0);
+  if (!tab) return;
+  const int D = heads * 64;
+  float* xr = qkv + row * 3 * D;
+  for (int u = threadIdx.x; u < 2 * heads * 32; u += 256) {
+    const int d = u & 31, slot = u >> 5;        // slot = part * heads + head: q | k are the first 2 D columns
+    float* x = xr + slot * 64 + d;
+    const float c = tab[d], s = tab[32 + d], a = x[0], b = x[32];
+    x[0] = a * c - b * s;
+    x[32] = b * c + a * s;
+  }
 }
 
 // out[orow, ooff + d] = src[tok[i] + skip + n + (n > 0 ? gap : 0), coff + d], orow = tok[i] - (skip + gap) * i + n
@@ -315,6 +328,15 @@ int embed_rows(float* x, const float* patch, const float* cls, const float* reg,
   hipLaunchKernelGGL(embed_rows_kernel, dim3((unsigned)rows), dim3(256), 0, stream, x, patch, cls, reg, R, pos, meta, n_img, T,
                      dim);
   return launch_status("embed_rows_kernel");
+}
+
+int rope_rows(float* qkv, int64_t rows, int heads, const RopeRows& rp, hipStream_t stream) {
+  ANYLOC_CHECK_ARG(qkv && rp.table && rows > 0 && rows < (1ll << 31) && heads > 0, "rope_rows: bad arguments");
+  ANYLOC_CHECK_ARG(rp.meta ? rp.n_img > 0 : rp.T > rp.prefix, "rope_rows: bad row layout");
+  ANYLOC_CHECK_ARG(rp.prefix >= 0, "rope_rows: prefix %d", rp.prefix);
+  ProfScope prof("rope_rows", stream, 6.0 * rows * heads * 64 * 2, 16.0 * rows * heads * 64 * 2);
+  hipLaunchKernelGGL(rope_rows_kernel, dim3((unsigned)rows), dim3(256), 0, stream, qkv, heads, rp);
+  return launch_status("rope_rows_kernel");
 }
 
 int facet_rows_ragged(const float* src, int64_t lds_, int coff, float* out, int64_t ldo, int ooff, const int64_t* meta,

@@ -31,6 +31,8 @@ struct anyloc_vit {
   const float* cls;
   const float* regs = nullptr;              // register tokens (device [n_reg, dim], caller-owned) or null
   int n_reg = 0;                            // R: token rows per image are CLS, R registers, patches
+  int rope = 0;                             // 1: rotary positions (DINOv3) -- no positional table, q / k of the patch rows rotated
+  float ln_eps = 1e-6f;                     // eps of every LayerNorm of the forward
   std::vector<anyloc_vit_block_weights> blocks;
   std::vector<anyloc_vit_block_x3> x3;      // optional: three-plane bf16 images of the four weight matrices
   std::vector<anyloc_vit_block_h2> h2;      // optional: two-plane fp16 images + row scales of the same matrices
@@ -125,6 +127,7 @@ struct BlockGemm {
   // h3, optional: the LayerNorm whose output IS the operand image (a.img / a.inv; with ln_bound, HOST [4], also the FFN bound
   // into h3.c_inv).  ln_tickets: zeroed words of this launch, one per 128-row tile (VitWs::ln_tk)
   const float *ln_x, *ln_w, *ln_b, *ln_bound;
+  float ln_eps;
   unsigned* ln_tickets;
 };
 
@@ -188,13 +191,13 @@ int run(BlockGemm& g, int epi, hipStream_t stream, const float* gamma = nullptr)
       const H3Plan plan = h3_plan(p, epi, g.ln_x != nullptr);
       if (plan.lead) {
         // the LayerNorm as the lead role of the GEMM's own launch (one image per call: LN1 + qkv, LN2 + w12) ...
-        p.ln_x = g.ln_x; p.ln_w = g.ln_w; p.ln_b = g.ln_b; p.ln_eps = 1e-6f; p.ln_dim = (int)a.K;
+        p.ln_x = g.ln_x; p.ln_w = g.ln_w; p.ln_b = g.ln_b; p.ln_eps = g.ln_eps; p.ln_dim = (int)a.K;
         p.ln_has_bound = g.ln_bound != nullptr;
         for (int i = 0; i < 4; ++i) p.ln_bound[i] = g.ln_bound ? g.ln_bound[i] : 0.0f;
         p.ln_tickets = g.ln_tickets;
       } else if (g.ln_x) {
         // ... or as a launch of its own in front of it: the same arithmetic, the same bits
-        ANYLOC_TRY(layernorm_h2(g.ln_x, g.ln_w, g.ln_b, a.M, (int)a.K, 1e-6f, a.img, a.inv, stream, g.ln_bound,
+        ANYLOC_TRY(layernorm_h2(g.ln_x, g.ln_w, g.ln_b, a.M, (int)a.K, g.ln_eps, a.img, a.inv, stream, g.ln_bound,
                                 g.ln_bound ? const_cast<float*>(p.c_inv) : nullptr));
       }
       return gemm_h3(p, epi, stream, &plan);
@@ -307,7 +310,8 @@ int anyloc_vit_attach_h2(anyloc_vit_t* h, const anyloc_vit_block_h2* blocks) {
     h->ffn_exact.assign(h->cfg.depth, 0);
     return ANYLOC_OK;
   }
-  ANYLOC_CHECK_ARG(h->cfg.dim % 16 == 0 && h->cfg.ffn_hidden % 16 == 0 && h->cfg.ffn_hidden <= 4096 && h->cfg.dim <= 2048,
+  // (ffn_hidden 5120 = ViT-H+/16, the widest model the path has been run with: tests/test_gpu_dinov3.py)
+  ANYLOC_CHECK_ARG(h->cfg.dim % 16 == 0 && h->cfg.ffn_hidden % 16 == 0 && h->cfg.ffn_hidden <= 5120 && h->cfg.dim <= 2048,
                    "vit_attach_h2: dim %d / ffn_hidden %d outside the fp16 path's limits", h->cfg.dim, h->cfg.ffn_hidden);
   for (int i = 0; i < h->cfg.depth; ++i) {
     const anyloc_vit_block_h2& b = blocks[i];
@@ -377,6 +381,29 @@ int anyloc_vit_set_registers(anyloc_vit_t* h, const float* register_tokens, int3
   h->regs = n_registers ? register_tokens : nullptr;
   h->n_reg = n_registers;
   return ANYLOC_OK;
+}
+
+int anyloc_vit_set_rope(anyloc_vit_t* h, int32_t on) {
+  ANYLOC_CHECK_ARG(h, "vit_set_rope: null handle");
+  h->rope = on ? 1 : 0;
+  return ANYLOC_OK;
+}
+
+int anyloc_vit_set_ln_eps(anyloc_vit_t* h, float eps) {
+  ANYLOC_CHECK_ARG(h, "vit_set_ln_eps: null handle");
+  ANYLOC_CHECK_ARG(eps > 0.0f && eps < 1.0f, "vit_set_ln_eps: eps %g outside (0, 1)", (double)eps);
+  h->ln_eps = eps;
+  return ANYLOC_OK;
+}
+
+int anyloc_rope_rows(float* qkv, int64_t rows, int64_t heads, const float* table, int64_t tokens, int64_t prefix,
+                     const int64_t* dev_meta, int32_t n_img, void* stream) {
+  ANYLOC_CHECK_ARG(qkv && table, "rope_rows: null pointer");
+  ANYLOC_CHECK_ARG(rows > 0 && heads > 0 && heads < 65536 && prefix >= 0 && prefix < (1 << 20), "rope_rows: bad shape");
+  ANYLOC_CHECK_ARG(dev_meta ? n_img > 0 : (tokens > prefix && tokens < (1ll << 31) && rows % tokens == 0),
+                   "rope_rows: uniform rows need rows = batch * tokens and tokens > prefix; ragged rows the table and n_img > 0");
+  const RopeRows rp{table, dev_meta, dev_meta ? n_img : 0, dev_meta ? 0 : (int)tokens, (int)prefix};
+  return rope_rows(qkv, rows, (int)heads, rp, static_cast<hipStream_t>(stream));
 }
 
 int anyloc_vit_set_telemetry(anyloc_vit_t* h, float* ffn_looseness, int32_t per_image) {
@@ -470,7 +497,7 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
                                     : (size_t)(reinterpret_cast<char*>(w.hmax) - reinterpret_cast<char*>(w.sk_tickets)),
                               stream));
 
-  // ---- patch embedding: conv 14x14 stride 14 == GEMM over gathered patches, + bias + pos ----
+  // ---- patch embedding: conv PxP stride P == GEMM over gathered patches, + bias + pos ----
   // h3: the gathered patches are quantised like every other operand (row maximum -> power-of-two scale), the contraction
   // padded to whole 16-element k-blocks
   const bool patch_h3 = h3 && h->patch_w2 && option(OPT_H3_PATCH) != 0;
@@ -480,7 +507,11 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
   else ANYLOC_TRY(im2col(img, col, batch, (int)img_h, (int)img_w, c.patch, kp, stream));
   // ragged or with registers: the patch GEMM with its bias epilogue into w.y [P, D]; embed_rows then adds each image's
   // positional rows and writes the CLS and register rows (the same two sums as EPI_PATCH + cls_rows)
-  const bool embed_pass = rg || R > 0;
+  // a rotary model takes the same pass: its rows have no positional term, `pos` is the rotation table(s) of the call
+  const bool rope = h->rope != 0;
+  const bool embed_pass = rg || R > 0 || rope;
+  const RopeRows rp{pos, meta, rg ? (int)batch : 0, T, 1 + R};
+  const float eps = h->ln_eps;
   const Act patches{col, w.a3, w.ainv, P, kp, false};
   const Weights Wpatch{h->patch_w, nullptr, h->patch_w2, h->patch_inv, D};
   BlockGemm pe = describe(patch_h3 ? Arith::H3 : Arith::F32, "vit_patch_embed_gemm", patches, Wpatch, 0, D, h->patch_b,
@@ -488,15 +519,15 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
   pe.f32.pos = pe.h3.pos = embed_pass ? nullptr : pos;
   pe.f32.patches = pe.h3.patches = np;
   ANYLOC_TRY(run(pe, embed_pass ? EPI_STORE : EPI_PATCH, stream));
-  if (embed_pass) ANYLOC_TRY(embed_rows(w.x, w.y, h->cls, h->regs, R, pos, meta, (int)batch, T, M, D, stream));
+  if (embed_pass) ANYLOC_TRY(embed_rows(w.x, w.y, h->cls, h->regs, R, rope ? nullptr : pos, meta, (int)batch, T, M, D, stream));
   else ANYLOC_TRY(cls_rows(w.x, h->cls, pos, batch, T, D, stream));
 
   // y = LN(x): as the operand image of the GEMM that follows (h3 always, x6 when fused) or as fp32 rows in w.y
   const bool ln_quantises = h3 || fuse_x6;
   auto layer_norm = [&](const float* nw, const float* nb) {
-    if (h3) return layernorm_h2(w.x, nw, nb, M, D, 1e-6f, w.a3, w.ainv, stream);
-    if (fuse_x6) return layernorm_x3(w.x, nw, nb, M, D, 1e-6f, w.a3, stream);
-    return layernorm(w.x, w.y, nw, nb, M, D, 1e-6f, stream);
+    if (h3) return layernorm_h2(w.x, nw, nb, M, D, eps, w.a3, w.ainv, stream);
+    if (fuse_x6) return layernorm_x3(w.x, nw, nb, M, D, eps, w.a3, stream);
+    return layernorm(w.x, w.y, nw, nb, M, D, eps, stream);
   };
   const Act y{w.y, w.a3, w.ainv, M, D, ln_quantises};
   static const anyloc_vit_block_x3 no_x3{};
@@ -538,12 +569,16 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
                              h3_attn ? H3_KIND_QKV : H3_KIND_OTHER, w);
     if (h3_attn) {
       qkv.h3.qkv_planes = reinterpret_cast<unsigned char*>(w.qkv); qkv.h3.qkv_inv = w.qinv; qkv.h3.heads = c.heads;
-      qkv.ln_x = w.x; qkv.ln_w = b.norm1_w; qkv.ln_b = b.norm1_b;
+      qkv.h3.rope = rp;
+      qkv.ln_x = w.x; qkv.ln_w = b.norm1_w; qkv.ln_b = b.norm1_b; qkv.ln_eps = eps;
       qkv.ln_tickets = w.ln_tickets + (size_t)l * 2 * w.ln_tk;
     }
-    ANYLOC_TRY(run(qkv, h3_attn ? EPI_QKV_PLANES : EPI_STORE, stream));
+    // rotary model: q and k of the patch rows are rotated in the epilogue that writes their tiles, or -- where q | k | v exist
+    // in fp32 -- in place AFTER the layer's q / k / v taps, which hand out the projections' outputs as they are
+    ANYLOC_TRY(run(qkv, h3_attn ? (rope ? EPI_QKV_PLANES_ROPE : EPI_QKV_PLANES) : EPI_STORE, stream));
     for (int t = 0; t < n_taps; ++t)
       if (tap_layers[t] == l && tap_facets[t] != ANYLOC_FACET_TOKEN) ANYLOC_TRY(facet(w.qkv, 3 * D, tap_facets[t] * D, t * D));
+    if (rope && !h3_attn) ANYLOC_TRY(rope_rows(w.qkv, M, c.heads, rp, stream));
     // ---- a = softmax((q/8) k^T) v ----
     const unsigned char* tiles = reinterpret_cast<const unsigned char*>(w.qkv);
     unsigned char* a_img = fuse_attn ? w.a3 : nullptr;     // x6: the output as the plane image instead of fp32 rows in w.y
@@ -565,7 +600,7 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
       // quantised in the epilogue against the row bound LayerNorm 2 leaves in w.hinv
       fc1.h3.C2 = w.h3; fc1.h3.c_inv = w.hinv;
       fc1.h3.c_max = telem ? w.hmax + (size_t)l * M : nullptr;
-      fc1.ln_x = w.x; fc1.ln_w = b.norm2_w; fc1.ln_b = b.norm2_b; fc1.ln_bound = fb;
+      fc1.ln_x = w.x; fc1.ln_w = b.norm2_w; fc1.ln_b = b.norm2_b; fc1.ln_bound = fb; fc1.ln_eps = eps;
       fc1.ln_tickets = w.ln_tickets + ((size_t)l * 2 + 1) * w.ln_tk;
     }
     if (x6 && fuse_ffn) fc1.x6.C3 = w.h3;

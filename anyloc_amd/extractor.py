@@ -20,7 +20,7 @@ import torch
 from torch.nn import functional as F
 
 from . import _lib, ops, weights
-from .synth import ARCH, PATCH, POS_GRID, n_registers
+from .synth import ARCH, ARCH_V3, PATCH, POS_GRID, ROPE_THETA, UNSERVED, is_rope, ln_eps, n_registers, patch_size
 
 DEFAULT_GEMM = "h3"      # block-GEMM arithmetic when neither the constructor nor ANYLOC_GEMM says otherwise
 # FFN-bound telemetry of the h3 forward (include/anyloc_hip.h, anyloc_vit_set_telemetry): EVERY call measures, per executed
@@ -34,6 +34,9 @@ FFN_LOOSENESS_MAX = 2.0 ** 14
 _DINO_V2_MODELS = ("dinov2_vits14", "dinov2_vitb14", "dinov2_vitl14", "dinov2_vitg14",
                    # with four register tokens: the patch grid comes back, never the register rows
                    "dinov2_vits14_reg", "dinov2_vitb14_reg", "dinov2_vitl14_reg", "dinov2_vitg14_reg")
+# DINOv3: patch 16, four registers, rotary positions; q / k / v facets are the projections BEFORE the rotation
+_DINO_V3_MODELS = tuple(ARCH_V3)
+_DINO_MODELS = _DINO_V2_MODELS + _DINO_V3_MODELS
 _DINO_FACETS = ("query", "key", "value", "token")
 INTERP_OFFSET = 0.1
 
@@ -94,6 +97,22 @@ def interpolate_pos_embed_reg(pos_embed, h_img, w_img):
     return torch.cat([pos_embed[0, :1], grid], dim=0).contiguous()
 
 
+def rope_table(h_img, w_img, patch=16, theta=ROPE_THETA):
+    """Rotation table of an ``h_img x w_img`` input of a DINOv3 model: fp32 [N, 64], row p = cos[0..31] | sin[0..31] of
+    patch p (the angles of columns d and d + 32 of a head are equal).  The same torch calls in fp32 as transformers
+    ``DINOv3ViTRopePositionEmbedding.forward`` / ``get_patches_center_coordinates`` (head_dim 64: 16 frequencies for y, then
+    16 for x), so cos / sin are that module's bits."""
+    gh, gw = h_img // patch, w_img // patch
+    inv_freq = 1 / theta ** torch.arange(0, 1, 4 / 64, dtype=torch.float32)
+    coords_h = torch.arange(0.5, gh, dtype=torch.float32) / gh
+    coords_w = torch.arange(0.5, gw, dtype=torch.float32) / gw
+    coords = torch.stack(torch.meshgrid(coords_h, coords_w, indexing="ij"), dim=-1).flatten(0, 1)
+    coords = 2.0 * coords - 1.0
+    angles = 2 * math.pi * coords[:, :, None] * inv_freq[None, None, :]
+    angles = angles.flatten(1, 2)
+    return torch.cat([torch.cos(angles), torch.sin(angles)], dim=1).contiguous()
+
+
 def ragged_chunks(sizes, max_rows, patch=PATCH, registers=0):
     """Greedy packing of images of sizes [(H, W), ...] in input order under a budget of ``max_rows`` token rows per call
     (1 + ``registers`` + N_i per image): -> [(start, stop), ...] index ranges.  An image whose own rows exceed the budget
@@ -141,7 +160,12 @@ class HipDinoV2:
         self.gemm = gemm or os.environ.get("ANYLOC_GEMM", DEFAULT_GEMM)
         if self.gemm not in ("x6", "h3", "f32"):
             raise ValueError(f"gemm mode must be 'x6', 'h3' or 'f32', got {self.gemm!r}")
+        if name in UNSERVED:
+            raise NotImplementedError(f"{name} is not served: {UNSERVED[name]}")
         dim, depth, heads, ffn, hidden = ARCH[name]
+        # what the name says beyond the shapes: patch size, LayerNorm eps, rotary positions instead of a positional table
+        self.patch, self.ln_eps, self.rope = patch_size(name), ln_eps(name), is_rope(name)
+        P = self.patch
         have = 1 + max(int(k.split(".")[1]) for k in state_dict if k.startswith("blocks."))
         depth = min(depth, have)
         if max_layer is not None:
@@ -156,9 +180,9 @@ class HipDinoV2:
             t = dev(t)
             self._keep.append(t)
             return t
-        self.pos_embed_host = state_dict["pos_embed"].detach().to("cpu", torch.float32)
+        self.pos_embed_host = None if self.rope else state_dict["pos_embed"].detach().to("cpu", torch.float32)
         self._pos_cache = {}
-        patch_w = keep(state_dict["patch_embed.proj.weight"].reshape(dim, 3 * PATCH * PATCH))
+        patch_w = keep(state_dict["patch_embed.proj.weight"].reshape(dim, 3 * P * P))
         patch_b = keep(state_dict["patch_embed.proj.bias"])
         cls = keep(state_dict["cls_token"].reshape(dim))
         if self.n_reg and "register_tokens" not in state_dict:
@@ -228,13 +252,17 @@ class HipDinoV2:
                              float(w12d[hidden:].norm(dim=1).max()), float(b12d[hidden:].abs().max())]
                 for j in range(4):
                     h2[i].fc1_bound[j] = bound[j] * (1.0 + 1e-6)
-        cfg = _lib.VitConfig(dim, depth, heads, self.ffn_kind, hidden, PATCH, 3 * PATCH * PATCH)
+        cfg = _lib.VitConfig(dim, depth, heads, self.ffn_kind, hidden, P, 3 * P * P)
         self._handle = C.c_void_p()
         lib = _lib.load()
         _lib.check(lib.anyloc_vit_create(C.byref(self._handle), C.byref(cfg), _lib.ptr(patch_w),
                                          _lib.ptr(patch_b), _lib.ptr(cls), blocks), "anyloc_vit_create")
         if regs is not None:
             _lib.check(lib.anyloc_vit_set_registers(self._handle, _lib.ptr(regs), self.n_reg), "anyloc_vit_set_registers")
+        if self.ln_eps != 1e-6:
+            _lib.check(lib.anyloc_vit_set_ln_eps(self._handle, self.ln_eps), "anyloc_vit_set_ln_eps")
+        if self.rope:
+            _lib.check(lib.anyloc_vit_set_rope(self._handle, 1), "anyloc_vit_set_rope")
         if self.gemm == "x6":
             _lib.check(lib.anyloc_vit_attach_x3(self._handle, x3), "anyloc_vit_attach_x3")
         if self.gemm == "h3":
@@ -275,11 +303,15 @@ class HipDinoV2:
         with _on_device(self.device):          # every launch of the call on the model's device, whatever the current one is
             self._begin_call()
             tok = self._forward_taps(img, [(self.depth - 1, "token")], True, False, False)
-            res = ops.layernorm(tok[:, 0].contiguous(), self._final_norm[0], self._final_norm[1], 1e-6)
+            res = ops.layernorm(tok[:, 0].contiguous(), self._final_norm[0], self._final_norm[1], self.ln_eps)
         return res if img.is_cuda else ops.to_home(res, img.device)
 
     def pos_table(self, H, W):
+        """What the forward's ``pos`` argument carries for an ``H x W`` input, cached per size: the interpolated positional
+        table [1 + N, D], or a rotary model's rotation table [N, 64]."""
         key = (H, W)
+        if key not in self._pos_cache and self.rope:
+            self._pos_cache[key] = rope_table(H, W, self.patch).to(self.device)
         if key not in self._pos_cache:
             interp = interpolate_pos_embed_reg if self.n_reg else interpolate_pos_embed
             self._pos_cache[key] = interp(self.pos_embed_host, H, W).to(self.device)
@@ -317,14 +349,14 @@ class HipDinoV2:
                     parts.append(ops._f32c(im, self.device).reshape(-1))
                 flat = torch.cat(parts) if parts else torch.empty(0, device=self.device)
             for h, w in sizes:
-                if h % PATCH or w % PATCH or h < PATCH or w < PATCH:
-                    raise ValueError(f"image {h}x{w} is not a positive multiple of the patch size {PATCH}")
-            tok, out_off, pix = ragged_offsets(sizes, use_cls, registers=self.n_reg)
+                if h % self.patch or w % self.patch or h < self.patch or w < self.patch:
+                    raise ValueError(f"image {h}x{w} is not a positive multiple of the patch size {self.patch}")
+            tok, out_off, pix = ragged_offsets(sizes, use_cls, patch=self.patch, registers=self.n_reg)
             if flat.numel() != pix[-1]:
                 raise ValueError(f"packed buffer holds {flat.numel()} floats, the sizes need {int(pix[-1])}")
             taps, inv = self._ascending(taps)
             offsets = ops.table_to_device(torch.from_numpy(out_off), self.device)
-            chunks = ragged_chunks(sizes, self.max_rows, registers=self.n_reg)
+            chunks = ragged_chunks(sizes, self.max_rows, patch=self.patch, registers=self.n_reg)
             # one chunk (the common case): the forward writes the caller's result directly; several: into slices of it
             out = None if len(chunks) == 1 and inv is None else \
                 torch.empty(int(out_off[-1]), len(taps) * self.dim, dtype=torch.float32, device=self.device)
@@ -344,9 +376,10 @@ class HipDinoV2:
     def _forward_ragged(self, flat, sizes, taps, use_cls, norm_taps, norm_concat):
         """One ragged call (taps ascending) over images that fit one launch sequence -> [sum rows_i, len(taps)*D]."""
         n_img, n_taps = len(sizes), len(taps)
-        tok, out_off, pix = ragged_offsets(sizes, use_cls, registers=self.n_reg)
+        tok, out_off, pix = ragged_offsets(sizes, use_cls, patch=self.patch, registers=self.n_reg)
         out = torch.empty(int(out_off[-1]), n_taps * self.dim, dtype=torch.float32, device=self.device)
-        # positional tables: one per distinct size (the pos_table cache), packed, addressed per image by its first row
+        # positional (rotary model: rotation) tables: one per distinct size (the pos_table cache), packed, addressed per image
+        # by its first row
         first, tables, pos_row, at = {}, [], [], 0
         for hw in sizes:
             if hw not in first:
@@ -470,8 +503,8 @@ class HipDinoV2:
         if img.ndim != 4 or img.shape[1] != 3:
             raise ValueError(f"expected an image batch [B,3,H,W], got {tuple(img.shape)}")
         H, W = img.shape[2:]
-        assert H % PATCH == 0, f"Input image height {H} is not a multiple of patch height {PATCH}"
-        assert W % PATCH == 0, f"Input image width {W} is not a multiple of patch width: {PATCH}"
+        assert H % self.patch == 0, f"Input image height {H} is not a multiple of patch height {self.patch}"
+        assert W % self.patch == 0, f"Input image width {W} is not a multiple of patch width: {self.patch}"
         taps, inv = self._ascending(taps)
         res = self._forward_uniform(ops._f32c(img, self.device), taps, use_cls, norm_taps, norm_concat)
         if inv is None:
@@ -484,7 +517,7 @@ class HipDinoV2:
     def _forward_uniform(self, img, taps, use_cls, norm_taps, norm_concat):
         """One batch of equal-sized images (taps ascending) -> [B, N(+1), len(taps)*D]."""
         B, _, H, W = img.shape
-        np_ = (H // PATCH) * (W // PATCH)
+        np_ = (H // self.patch) * (W // self.patch)
         out = torch.empty(B, np_ + 1 if use_cls else np_, len(taps) * self.dim, dtype=torch.float32, device=self.device)
         if B == 0:
             return out
@@ -510,9 +543,12 @@ def hub_load(repo_or_dir, model, *args, **kwargs):
     ``scripts/dino_v2_global_vpr.py:115-116``): there is no network, so the weights come from
     ``anyloc_amd.weights`` and the returned object runs the HIP forward.  ``.eval()`` / ``.to(device)`` are
     accepted and return the same object (it lives on the GPU)."""
-    if "dinov2" not in str(repo_or_dir) or model not in _DINO_V2_MODELS:
-        raise RuntimeError(f"hub stand-in only serves facebookresearch/dinov2 {_DINO_V2_MODELS}; "
-                           f"got {repo_or_dir!r}, {model!r} (no network in this environment)")
+    if model in UNSERVED:
+        raise NotImplementedError(f"{model} is not served: {UNSERVED[model]}")
+    family = "dinov3" if model in _DINO_V3_MODELS else "dinov2"
+    if family not in str(repo_or_dir) or model not in _DINO_MODELS:
+        raise RuntimeError(f"hub stand-in only serves facebookresearch/dinov2 {_DINO_V2_MODELS} and facebookresearch/dinov3 "
+                           f"{_DINO_V3_MODELS}; got {repo_or_dir!r}, {model!r} (no network in this environment)")
     return HipDinoV2(model, weights.resolve_state_dict(model), _lib.require_gpu())
 
 
@@ -529,8 +565,10 @@ class DinoV2ExtractFeatures:
     """
     def __init__(self, dino_model: str, layer: int, facet: str = "token", use_cls=False,
                  norm_descs=True, device: str = "cpu") -> None:
-        if dino_model not in _DINO_V2_MODELS:
-            raise ValueError(f"dino_model must be one of {_DINO_V2_MODELS}")
+        if dino_model in UNSERVED:
+            raise NotImplementedError(f"{dino_model} is not served: {UNSERVED[dino_model]}")
+        if dino_model not in _DINO_MODELS:
+            raise ValueError(f"dino_model must be one of {_DINO_MODELS}")
         if facet not in _DINO_FACETS:
             raise ValueError(f"facet must be one of {_DINO_FACETS}")
         self.vit_type: str = dino_model
@@ -556,7 +594,7 @@ class DinoV2ExtractFeatures:
         """
             Parameters:
             - img:   The input image batch [B, 3, H, W] (ImageNet-normalised,
-                     H and W multiples of 14).  Returns [B, N(+1), D] on the
+                     H and W multiples of the model's patch, 14 or 16).  Returns [B, N(+1), D] on the
                      input's device.
         """
         res = self.dino_model.forward_taps(img, [(self.layer, self.facet)], use_cls=self.use_cls,
@@ -575,7 +613,7 @@ class DinoV2ExtractFeatures:
 
     def extract_ragged(self, imgs, packed=False):
         """Additive API: images of different sizes (a list of [3, H_i, W_i] tensors, ImageNet-normalised, sides multiples of
-        14) in few batched launches -> a list of [1, N_i(+1), D] tensors on the model's device, each what ``self(img[None])``
+        the model's patch) in few batched launches -> a list of [1, N_i(+1), D] tensors on the model's device, each what ``self(img[None])``
         returns for that image; ``packed=True``: the (packed [sum rows_i, D], offsets [n+1]) pair instead, which
         ``ops.vlad`` / ``VLAD.generate_multi`` take without a copy."""
         out, offsets = self.dino_model.forward_taps_ragged(imgs, [(self.layer, self.facet)], use_cls=self.use_cls,

@@ -161,6 +161,23 @@ def layernorm(x, weight, bias, eps=1e-6):
     return y
 
 
+def rope_rows(qkv, heads, table, tokens=None, prefix=5, meta=None):
+    """The rotary rotation of a DINOv3 block alone (include/anyloc_hip.h, anyloc_rope_rows): qkv fp32 [rows, 3 * heads * 64]
+    -> a rotated copy (q and k of the rows that are not prefix rows; v and the prefix rows keep their bits).  ``table``:
+    [N, 64] rotation rows (cos | sin).  Uniform rows: ``tokens`` rows per image (prefix + N); ragged rows: ``meta`` = the
+    int64 [5, n_img + 1] table of a ragged forward (rows 0 and 2 are read), ``table`` the packed tables."""
+    _need_cuda(qkv, table)
+    out = _f32c(qkv).clone()
+    table = _f32c(table)
+    n_img = 0
+    if meta is not None:
+        meta = meta.to(out.device, torch.int64).contiguous()
+        n_img = meta.shape[1] - 1
+    _lib.check(_lib.load().anyloc_rope_rows(_lib.ptr(out), out.shape[0], heads, _lib.ptr(table), int(tokens or 0), prefix,
+                                            _lib.ptr(meta), n_img, _lib.stream_ptr()), "anyloc_rope_rows")
+    return out
+
+
 def attention(qkv, heads):
     """qkv [B, T, 3*D] -> [B, T, D]  (softmax((q/8) k^T) v per 64-wide head)."""
     _need_cuda(qkv)

@@ -24,6 +24,33 @@ REGISTERS = {f"{base}_reg": 4 for base in tuple(ARCH)}
 ARCH.update({name: ARCH[name[:-len("_reg")]] for name in REGISTERS})
 PATCH = 14
 POS_GRID = 37
+# DINOv3 (facebookresearch/dinov3 dinov3_vit*16): patch 16, four register tokens, NO positional table -- q and k of every
+# block are rotated by a per-patch 2-D rotary embedding -- LayerNorm eps 1e-5, no bias on the k projection.
+# Shapes from the published model cards (head_dim 64 throughout); dinov3_vit7b16 (head_dim 128) is not served
+ARCH_V3 = {
+    "dinov3_vits16": (384, 12, 6, "mlp", 1536),
+    "dinov3_vits16plus": (384, 12, 6, "swiglu", 1536),
+    "dinov3_vitb16": (768, 12, 12, "mlp", 3072),
+    "dinov3_vitl16": (1024, 24, 16, "mlp", 4096),
+    "dinov3_vith16plus": (1280, 32, 20, "swiglu", 5120),
+}
+ARCH.update(ARCH_V3)
+REGISTERS.update({name: 4 for name in ARCH_V3})
+ROPE_THETA = 100.0
+UNSERVED = {"dinov3_vit7b16": "head_dim 128 (the attention kernels are written for head_dim 64)"}
+
+
+def is_rope(name):
+    """A model without a positional table whose q / k are rotated (the DINOv3 family)."""
+    return name in ARCH_V3
+
+
+def patch_size(name):
+    return 16 if name in ARCH_V3 else PATCH
+
+
+def ln_eps(name):
+    return 1e-5 if name in ARCH_V3 else 1e-6
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
 
@@ -43,6 +70,8 @@ def synthetic_state_dict(name, seed=0, device="cpu", depth=None):
     A ``_reg`` name gets the base model's dict for the same seed plus ``register_tokens [1, R, D]`` drawn from a generator
     of its own, so the base dicts stay what they were.
     """
+    if name in ARCH_V3:
+        return _synthetic_v3(name, seed, device, depth)
     if name in REGISTERS:
         sd = synthetic_state_dict(base_model(name), seed, device, depth)
         gen = torch.Generator(device=device)
@@ -95,9 +124,53 @@ def synthetic_state_dict(name, seed=0, device="cpu", depth=None):
     return sd
 
 
+def _synthetic_v3(name, seed, device, depth):
+    """A DINOv3 name in the same key layout (``blocks.N.attn.qkv.*``, ``ls1.gamma``, ``mlp.fc1/fc2`` or ``mlp.w12/w3``,
+    ``register_tokens``): no ``pos_embed``, 16 x 16 patches, the k third of ``attn.qkv.bias`` zero (the k projection has no
+    bias)."""
+    dim, full_depth, heads, ffn, hidden = ARCH[name]
+    depth = full_depth if depth is None else depth
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed + 0xD3)
+    r = lambda shape, std: _randn(gen, shape, std, device)
+    sd = {}
+    sd["cls_token"] = r((1, 1, dim), 0.02)
+    sd["mask_token"] = torch.zeros(1, dim, device=device)
+    sd["register_tokens"] = r((1, REGISTERS[name], dim), 0.05)
+    sd["patch_embed.proj.weight"] = r((dim, 3, 16, 16), 0.03)
+    sd["patch_embed.proj.bias"] = r((dim,), 0.02)
+    w_std = 0.7 / math.sqrt(dim)
+    for i in range(depth):
+        p = f"blocks.{i}."
+        sd[p + "norm1.weight"] = 1.0 + r((dim,), 0.1)
+        sd[p + "norm1.bias"] = r((dim,), 0.05)
+        sd[p + "attn.qkv.weight"] = r((3 * dim, dim), 2.0 * w_std)
+        sd[p + "attn.qkv.bias"] = r((3 * dim,), 0.05)
+        sd[p + "attn.qkv.bias"][dim:2 * dim] = 0.0
+        sd[p + "attn.proj.weight"] = r((dim, dim), w_std)
+        sd[p + "attn.proj.bias"] = r((dim,), 0.02)
+        sd[p + "ls1.gamma"] = 0.3 + 0.2 * torch.rand(dim, generator=gen, device=device)
+        sd[p + "norm2.weight"] = 1.0 + r((dim,), 0.1)
+        sd[p + "norm2.bias"] = r((dim,), 0.05)
+        if ffn == "mlp":
+            sd[p + "mlp.fc1.weight"] = r((hidden, dim), w_std)
+            sd[p + "mlp.fc1.bias"] = r((hidden,), 0.05)
+            sd[p + "mlp.fc2.weight"] = r((dim, hidden), 0.7 / math.sqrt(hidden))
+            sd[p + "mlp.fc2.bias"] = r((dim,), 0.02)
+        else:
+            sd[p + "mlp.w12.weight"] = r((2 * hidden, dim), w_std)
+            sd[p + "mlp.w12.bias"] = r((2 * hidden,), 0.05)
+            sd[p + "mlp.w3.weight"] = r((dim, hidden), 0.7 / math.sqrt(hidden))
+            sd[p + "mlp.w3.bias"] = r((dim,), 0.02)
+        sd[p + "ls2.gamma"] = 0.3 + 0.2 * torch.rand(dim, generator=gen, device=device)
+    sd["norm.weight"] = 1.0 + r((dim,), 0.1)
+    sd["norm.bias"] = r((dim,), 0.05)
+    return sd
+
+
 def base_model(name):
-    """The plain DINOv2 a name shares its blocks with (``dinov2_vitg14_reg`` -> ``dinov2_vitg14``)."""
-    return name[:-len("_reg")] if name in REGISTERS else name
+    """The plain DINOv2 a name shares its blocks with (``dinov2_vitg14_reg`` -> ``dinov2_vitg14``); a DINOv3 name is its own."""
+    return name[:-len("_reg")] if name in REGISTERS and name not in ARCH_V3 else name
 
 
 def n_registers(name):

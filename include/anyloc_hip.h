@@ -567,6 +567,33 @@ int anyloc_vit_block_ffn_exact(anyloc_vit_t* h, int32_t layer, int32_t exact);
  * workspace queries size for T = 1 + R + N once registers are set. */
 int anyloc_vit_set_registers(anyloc_vit_t* h, const float* register_tokens /*device [R, D]*/, int32_t n_registers);
 
+/* DINOv3 (dinov3_vit*16; additive to ABI 10): rotary positions and the LayerNorm eps of the handle.  What the two calls
+ * restate is transformers/models/dinov3_vit/modeling_dinov3_vit.py:
+ *   anyloc_vit_set_ln_eps(h, eps)   every LayerNorm of later forwards uses eps (default 1e-6, the DINOv2 value; DINOv3:
+ *     `nn.LayerNorm(config.hidden_size, eps=config.layer_norm_eps)` with layer_norm_eps = 1e-5).  eps outside (0, 1) is
+ *     ANYLOC_ERR_INVALID_ARG.
+ *   anyloc_vit_set_rope(h, on)      on != 0: the model has NO positional table.  Token rows are [CLS, reg_0 .. reg_{R-1},
+ *     patch_p] with nothing added (`torch.cat([cls_token, register_tokens, patch_embeddings], dim=1)`), and in every block
+ *     q and k of the PATCH rows -- not of the 1 + R prefix rows -- are rotated per head (head_dim 64, d < 32):
+ *         q'[d]      = q[d] cos[d]      - q[d + 32] sin[d]
+ *         q'[d + 32] = q[d + 32] cos[d] + q[d] sin[d]
+ *     (`apply_rotary_pos_emb`: `q * cos + rotate_half(q) * sin` on `q.split((num_prefix_tokens, num_patches), dim=-2)[1]`;
+ *     the angles are tiled twice over the head, `angles.tile(2)`, hence cos[d + 32] = cos[d]).  The `pos` argument of
+ *     anyloc_vit_forward then carries the ROTATION TABLE of the call's size instead of a positional table: fp32 [N, 64],
+ *     row p = cos[0..31] | sin[0..31] of patch p (`DINOv3ViTRopePositionEmbedding.forward`: patch centres (i + 0.5) / h,
+ *     (j + 0.5) / w mapped to [-1, 1], angles = 2 pi coord inv_freq with 16 frequencies for y, then 16 for x).  In
+ *     anyloc_vit_forward_ragged `pos` holds the images' tables packed and dev_meta[2][i] is the first ROW (of 64 floats)
+ *     of image i's table.  The q / k / v taps hand out the projections' outputs BEFORE the rotation (what a forward
+ *     hook on the linear layers sees); the token tap is the block output.  on = 0 restores the positional-table forward.
+ * anyloc_rope_rows (unit tests): the rotation alone, in place on fp32 qkv [rows, 3 * heads * 64] (q | k | v, heads
+ * contiguous): q and k of every row that is not a prefix row; v and the prefix rows keep their bits.  dev_meta = NULL:
+ * uniform images of `tokens` rows (rows % tokens == 0) sharing table [tokens - prefix, 64]; otherwise the ragged table
+ * above (rows [0] and [2] are read, n_img images, `tokens` unused). */
+int anyloc_vit_set_rope(anyloc_vit_t* h, int32_t on);
+int anyloc_vit_set_ln_eps(anyloc_vit_t* h, float eps);
+int anyloc_rope_rows(float* qkv, int64_t rows, int64_t heads, const float* table, int64_t tokens, int64_t prefix,
+                     const int64_t* dev_meta, int32_t n_img, void* stream);
+
 #define ANYLOC_VIT_USE_CLS 1u        /* keep the CLS row (utilities.py:270-273) */
 #define ANYLOC_VIT_NORM_TAPS 2u      /* L2-normalise each tap (utilities.py:282-283) */
 #define ANYLOC_VIT_NORM_CONCAT 4u    /* L2-normalise the concatenated taps again
@@ -574,8 +601,9 @@ int anyloc_vit_set_registers(anyloc_vit_t* h, const float* register_tokens /*dev
 
 size_t anyloc_vit_workspace_bytes(const anyloc_vit_t* h, int64_t batch,
                                   int64_t img_h, int64_t img_w);
-/*   img  [B,3,H,W]  ImageNet-normalised, H and W multiples of 14
+/*   img  [B,3,H,W]  ImageNet-normalised, H and W multiples of the model's patch (anyloc_vit_config.patch)
  *   pos  [1+N, D]   positional table already interpolated for (H,W), row 0 = CLS
+ *                   (anyloc_vit_set_rope: [N, 64], the rotation table of (H,W))
  *   tap_layers / tap_facets: host arrays of n_taps entries, layers ascending
  *   out  [B, N (+1 with USE_CLS), n_taps*D]  taps concatenated on the feature axis */
 int anyloc_vit_forward(anyloc_vit_t* h, const float* img, int64_t batch,
@@ -585,8 +613,8 @@ int anyloc_vit_forward(anyloc_vit_t* h, const float* img, int64_t batch,
                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* Ragged batches (ABI 10): images of DIFFERENT sizes in one forward, packed back to back.  Image i is
- * img_hw[2i] x img_hw[2i+1] pixels (each a positive multiple of 14, else ANYLOC_ERR_INVALID_ARG before any
- * device work), N_i = (H_i/14)(W_i/14) patches, T_i = 1 + R + N_i token rows (CLS first, then the R registers of
+ * img_hw[2i] x img_hw[2i+1] pixels (each a positive multiple of the model's patch P, else ANYLOC_ERR_INVALID_ARG before any
+ * device work), N_i = (H_i/P)(W_i/P) patches, T_i = 1 + R + N_i token rows (CLS first, then the R registers of
  * anyloc_vit_set_registers; R = 0 without them).  No image attends to
  * another; flags, taps, anyloc_vit_block_ffn_exact and the telemetry mean what they mean for
  * anyloc_vit_forward (per_image = 1: ffn_looseness[depth][n_img]).  The call is stream-ordered and never
@@ -599,6 +627,7 @@ int anyloc_vit_forward(anyloc_vit_t* h, const float* img, int64_t batch,
  *     [3][i] H_i,  [4][i] W_i                       ([1..4][n_img] unused)
  *   img   the CHW images, image i at img + dev_meta[1][i]
  *   pos   packed positional tables, [1 + N_i, D] for image i at row dev_meta[2][i]
+ *         (anyloc_vit_set_rope: packed rotation tables, [N_i, 64] for image i at row dev_meta[2][i])
  *   out   [sum rows_i, n_taps*D], rows_i = N_i (+1 with USE_CLS); image i's rows start at dev_meta[0][i] - i(1+R)
  *         (dev_meta[0][i] - iR with USE_CLS) -- offsets anyloc_vlad_hard / anyloc_vlad_soft take as they are */
 size_t anyloc_vit_workspace_bytes_ragged(const anyloc_vit_t* h, int32_t n_img,

@@ -23,7 +23,7 @@ from typing import List, Tuple, Union
 import numpy as np
 import torch
 
-from anyloc_amd.extractor import DinoV2ExtractFeatures, _DINO_FACETS, _DINO_V2_MODELS  # noqa: F401
+from anyloc_amd.extractor import DinoV2ExtractFeatures, _DINO_FACETS, _DINO_MODELS, _DINO_V2_MODELS, _DINO_V3_MODELS  # noqa: F401
 from anyloc_amd.kmeans import KMeans  # noqa: F401
 from anyloc_amd.retrieval import get_top_k_recall  # noqa: F401
 from anyloc_amd.vlad import VLAD  # noqa: F401
