@@ -1,15 +1,26 @@
 // Exact brute-force top-k retrieval (inner product / squared L2).
 //
-// replaces: faiss.IndexFlatIP / IndexFlatL2 .add + .search as called by
-// get_top_k_recall (reference utilities.py:439-450).
+// replaces: faiss.IndexFlatIP / IndexFlatL2 .add + .search as called by get_top_k_recall (reference utilities.py:439-450).
 //
-// The database is processed in column panels: an fp32 MFMA GEMM (gemm_f32.hip)
-// writes the [nq, panel] score block, then one block per query merges the
-// panel into that query's running top-k list (threshold filter against the
-// list's k-th entry + one-wave selection; ties -> lower database index,
-// deterministic).
-// Governing roofline: fp32 MFMA (2*nq flop per database float).
+// The database is processed in row panels: a GEMM writes the [nq, panel] score block, then one block per query merges the panel
+// into that query's running top-k list (threshold filter against the list's k-th entry + one-wave selection; ties -> lower
+// database index, deterministic).  Three scoring paths, one per call (topk_plan chooses, anyloc_topk_path names it):
+//   fp32 panels  32 768 rows per panel on the fp32 MFMA GEMM (gemm_f32.hip); roofline: fp32 MFMA, 2*nq flop per database float
+//   few queries  <= 64 queries against rows of >= 4096 columns: a [nq, panel] GEMM has too few tiles to stream the database, so
+//                the panel is the M operand of a split-K launch (option topk_fewq_x6: scores_h3.hip / scores_x6.hip / gemm_nt_splitk)
+//   fp16 panels  8192 rows per panel on the two-term fp16 GEMM (gemm_h3.hip), 2.5-3x the fp32-MFMA rate and as accurate: queries
+//                quantised once per call, a panel once per panel -- or never: a PREPARED INDEX (anyloc_topk_index_build[_range])
+//                holds every panel's operand image, row scales, sums of squares and residual norms, for every query count
+// On the fp16 panels the SCREENED search (scores_screen.hip) scores whole column ranges on the leading planes alone and re-scores
+// exactly the rows its error bound cannot rule out; when a query has more of those than SCREEN_CMAX the call falls back to the
+// unscreened panel search, on the query operands it already has.
+// Where each decision lives: topk_plan -- path, panel height, query chunk, screened column range, few-query arithmetic; the one
+// reader of the topk_* options, asked by carve, the searches, anyloc_topk_path, the index layout and the size functions of the ABI.
+// topk_impl -- validation, the workspace check, whether THIS call screens, the fallback.  prologue -- norms and the queries' operand
+// images, once per call.  db_panel / score_panel -- a database panel as GEMM operand with its norms / the query-chunk x k-chunk loop
+// on the fp16 planes.  screened_search, panel_search -- the two searches.  launch_* -- the one launch site of each kernel here.
 #include <algorithm>
+#include <optional>
 
 #include "common.hpp"
 
@@ -247,10 +258,7 @@ __global__ void topk_finish_kernel(float* __restrict__ v, const long long* __res
   if (metric) v[i] = idx[i] < 0 ? INFINITY : -v[i];
 }
 
-// few queries (<= 64) against long rows: a [nq, panel] GEMM has too few tiles to stream the database, so the panel is
-// scored by a split-K launch with the database as the M operand (gemm_nt_splitk)
-constexpr int SPLITK_MAX = 16;
-bool few_queries(int64_t nq, int64_t dim) { return nq <= 64 && dim % 32 == 0 && dim >= 4096; }
+constexpr int SPLITK_MAX = 16;            // few-query path: K slices of the split-K launch, at most
 // number of K slices: a divisor of dim/32 that fills the 512 resident workgroups (2 per CU) best, slices >= 1024 long
 int choose_ksplit(int64_t rows, int64_t dim) {
   const int64_t tiles = (rows + 127) / 128, kb = dim / 32;
@@ -265,43 +273,103 @@ int choose_ksplit(int64_t rows, int64_t dim) {
   return best;
 }
 
-// Many queries against long rows: the score panels run on the two-term fp16 GEMM (gemm_h3.hip: three fp16 matrix-core products
-// per k-step of row-scaled 22-bit operands, fp32 accumulate -- the arithmetic of the ViT block GEMMs, 2.5-3x the fp32-MFMA
-// rate, as accurate as an fp32 GEMM).  Queries are quantised once per call, every database panel once per panel
-// (split_h2_wide: two reads + one write of the panel, a few % of its GEMM; the rows' sums of squares for F.normalize / L2
-// come out of the same pass).  An operand image must stay inside 2 GiB of buffer addressing: rows per image <=
-// (2^31 - 1) / (64 * dim / 16).  Option topk_h3: -1 (default) = where it pays (>= 256 queries, dim >= 1024, >= 2048 rows),
-// 0 = never, 1 = wherever the shape allows (tests).
+// fp16 panels (gemm_h3.hip: three fp16 matrix-core products per k-step of row-scaled 22-bit operands, fp32 accumulate).  Quantising
+// a panel (split_h2_wide) is two reads + one write of it, a few % of its GEMM; the rows' sums of squares for F.normalize / L2 come
+// out of the same pass.  An operand image must stay inside 2 GiB of buffer addressing: rows <= (2^31 - 1) / (64 * dim / 16).
 constexpr int64_t H3_PANEL = 8192;
-int64_t h3_rows_limit(int64_t dim) { return ((1ll << 31) - 1) / (4 * dim) / 256 * 256; }
-bool h3_scores(int64_t nq, int64_t ndb, int64_t dim) {
-  const int64_t mode = option(OPT_TOPK_H3);
-  if (mode == 0 || nq <= 64 || dim % 16 != 0 || h3_rows_limit(dim) < 256) return false;
-  return mode > 0 || (nq >= 256 && dim >= 1024 && ndb >= 2048);
-}
+int64_t h3_rows_limit(int64_t dim) { return dim > 0 ? ((1ll << 31) - 1) / (4 * dim) / 256 * 256 : 0; }
+// A 49 152-long contraction in ONE fp32 accumulator takes ~9 000 rounded additions: 4e-6 on a score of 1.  Cut into chunks of 8192 k
+// (one launch each, the later ones adding into the panel) the error is that of ~1 500 additions plus six: 5e-7 -- the chunked summation
+// of the fp32-MFMA path (gemm_f32.hip, ABL bit 5) at the price of re-reading and re-writing the score panel per chunk (3 % of the GEMM time).
+constexpr int64_t SCORE_KC16 = 512;       // k-blocks of 16 per accumulated chunk: exact scores
+constexpr int64_t SCREEN_KC16 = 1536;     // ... leading-plane scores (the accumulation term of the screening bound)
 
-// Screened search (scores_screen.hip): the leading-plane scores of a whole range of database columns [nq, sc_cols], the
-// screened running lists, the per-query margin, the candidates and their re-scored values
+// Screened search (scores_screen.hip)
 constexpr int SCREEN_CMAX = 512;          // candidates per query and column range; more: the call re-runs unscreened
 constexpr int SCREEN_KMAX = 128;
 constexpr int64_t SCREEN_COLS = 131072;   // database columns per range (a multiple of the panel)
 constexpr size_t SCREEN_SBUF_MAX = 12ull << 30;
+
+enum { PATH_F32 = 0, PATH_FEWQ = 1, PATH_H3 = 2 };   // the values anyloc_topk_path answers
+struct TopkPlan {
+  int64_t nq, ndb, dim, k;
+  bool indexed;                    // the database side is a prepared index: fp16 panels at every query count
+  int path;
+  int64_t panel, q_chunk;          // database rows per score panel; fp16 panels: queries per operand image
+  int64_t sc_cols;                 // database columns per screened range; 0: no screened search for this shape
+  int fewq;                        // few-query arithmetic: 2 = two fp16 planes, 1 = three bf16 planes, 0 = fp32 MFMA
+  bool qdma;                       // ... on fp16 planes: the queries are pre-split once per call
+};
+// Option topk_h3: -1 (default) = where it pays (>= 256 queries, dim >= 1024, >= 2048 rows), 0 = never, 1 = wherever the shape
+// allows (tests).  Option topk_screen: 0 = never, 1 = wherever the shape allows, -1 (default) = where it pays (>= 256 queries
+// against >= 16 384 rows of >= 4096 columns); it serves the fp16 panels' shapes with k <= 128, rows the re-scoring kernel holds
+// in registers, and a score buffer of at most 12 GiB (fewer columns per range for more queries).
+TopkPlan topk_plan(int64_t nq, int64_t ndb, int64_t dim, int64_t k, bool indexed) {
+  const int64_t h3_mode = option(OPT_TOPK_H3), screen_mode = option(OPT_TOPK_SCREEN), limit = h3_rows_limit(dim);
+  TopkPlan p{nq, ndb, dim, k, indexed};
+  p.fewq = (int)option(OPT_TOPK_FEWQ_X6);
+  p.qdma = option(OPT_TOPK_FEWQ_QDMA) != 0;
+  const bool h3 = indexed || (h3_mode != 0 && nq > 64 && dim % 16 == 0 && limit >= 256 &&
+                              (h3_mode > 0 || (nq >= 256 && dim >= 1024 && ndb >= 2048)));
+  p.path = h3 ? PATH_H3 : nq <= 64 && dim % 32 == 0 && dim >= 4096 ? PATH_FEWQ : PATH_F32;
+  p.panel = h3 ? std::min(H3_PANEL, limit) : PANEL;
+  p.q_chunk = std::max<int64_t>(1, h3 ? std::min(nq, limit) : nq);
+  if (h3 && screen_mode != 0 && k >= 1 && k <= SCREEN_KMAX && screen_rescore_supported(dim) && nq > 0 && ndb > 0 &&
+      (screen_mode > 0 || (nq >= 256 && ndb >= 16384 && dim >= 4096))) {
+    const int64_t fit = (int64_t)(SCREEN_SBUF_MAX / 4) / nq / p.panel * p.panel;
+    const int64_t cols = std::min(std::min(SCREEN_COLS, cdiv(ndb, p.panel) * p.panel), fit);
+    p.sc_cols = cols >= p.panel ? cols : 0;
+  }
+  return p;
+}
+
 struct TopkWs {
+  // screened search: leading-plane scores [nq, sc_cols], screened running lists, per-query margin, candidates, their re-scored values
   float *sbuf, *scr_v, *margin, *cand_v, *rho_q, *rho_d, *resid;
   long long* scr_i;
   int *cand, *count, *overflow;
-  int64_t sc_cols;                 // 0: no screened search for this shape
   float *scores, *qn, *dn, *dss, *dnorm, *part, *rsq_part;
   unsigned char *qimg, *dimg;      // h3 path: operand images of the queries (per chunk of q_chunk rows) and of one panel
-  float *qinv, *dinv;
-  int64_t panel, q_chunk;
+  float *qinv, *dinv;              // ... and their row scales
   size_t bytes;
 };
+TopkWs carve(void* ws, size_t cap, const TopkPlan& p) {
+  Arena a(ws, cap);
+  TopkWs w;
+  const bool h3 = p.path == PATH_H3, few = p.path == PATH_FEWQ, own_db = h3 && !p.indexed, sc = p.sc_cols > 0;
+  const int64_t nq = p.nq, k = p.k, ndb1 = std::max<int64_t>(p.ndb, 1), panel = std::min(p.panel, ndb1);
+  w.scores = a.take<float>(std::max<int64_t>(nq, 1) * panel);
+  // (few-query fp16 path: the queries' pre-split planes, 10 KiB per 32-k slab)
+  w.qimg = a.take<unsigned char>(h3 ? (size_t)cdiv(nq, p.q_chunk) * h2_bytes(p.q_chunk, p.dim) : few ? fewq_query_image_bytes(p.dim) : 1);
+  w.dimg = a.take<unsigned char>(own_db ? h2_bytes(panel, p.dim) : 1);
+  w.qinv = a.take<float>(h3 ? nq : 64);                  // (few-query fp16 path: the <= 64 queries' row scales)
+  w.dinv = a.take<float>(own_db ? panel : 1);
+  w.qn = a.take<float>(std::max<int64_t>(nq, 1));
+  w.dn = a.take<float>(ndb1);
+  w.dss = a.take<float>(ndb1);
+  w.dnorm = a.take<float>(ndb1);
+  w.part = a.take<float>(few ? (size_t)SPLITK_MAX * panel * 64 : 1);
+  w.rsq_part = a.take<float>(few ? (size_t)SPLITK_MAX * panel : 1);
+  w.sbuf = a.take<float>(sc ? (size_t)nq * p.sc_cols : 1);
+  w.scr_v = a.take<float>(sc ? (size_t)nq * k : 1);
+  w.scr_i = a.take<long long>(sc ? (size_t)nq * k : 1);
+  w.margin = a.take<float>(sc ? (size_t)nq : 1);
+  w.cand = a.take<int>(sc ? (size_t)nq * SCREEN_CMAX : 1);
+  w.cand_v = a.take<float>(sc ? (size_t)nq * SCREEN_CMAX : 1);
+  w.count = a.take<int>(sc ? (size_t)nq : 1);
+  w.rho_q = a.take<float>(sc ? (size_t)nq : 1);
+  w.rho_d = a.take<float>(sc && !p.indexed ? (size_t)ndb1 : 1);
+  w.resid = a.take<float>(sc && !p.indexed ? (size_t)panel : 1);
+  w.overflow = a.take<int>(4);                            // [0] overflow flag, [1] bits of the largest database rho, [2] of the largest raw sum of squares
+  w.bytes = a.off;
+  return w;
+}
+
 // A prepared database (anyloc_topk_index_build: faiss' index.add): per panel of index_panel(dim) rows the two-plane fp16 image
 // the score GEMM reads, then the rows' 2^-e and their raw sums of squares.  Layout inside the caller's buffer:
 //   [n_panels][align256(h2_bytes(panel, dim))] images (a shorter last panel: an image of its own row count at its slot)
 //   [ndb] float 2^-e      [ndb] float sum of squares      [ndb] float relative residual norm (ABI 9)
-int64_t index_panel(int64_t dim) { return std::min(H3_PANEL, h3_rows_limit(dim)); }
+int64_t index_panel(int64_t dim) { return topk_plan(0, 0, dim, 0, true).panel; }
 bool index_supported(int64_t ndb, int64_t dim) { return ndb > 0 && dim % 16 == 0 && dim >= 16 && h3_rows_limit(dim) >= 256; }
 struct IndexView {
   unsigned char* img;
@@ -314,65 +382,251 @@ IndexView index_view(void* p, int64_t ndb, int64_t dim) {
   v.panel = index_panel(dim);
   const int64_t np = (ndb + v.panel - 1) / v.panel;
   v.slot = align_up(h2_bytes(v.panel, dim), 256);
-  unsigned char* b = static_cast<unsigned char*>(p);
-  v.img = b;
-  v.dinv = reinterpret_cast<float*>(b + (size_t)np * v.slot);
+  v.img = static_cast<unsigned char*>(p);
+  v.dinv = reinterpret_cast<float*>(v.img + (size_t)np * v.slot);
   v.dss = v.dinv + align_up((size_t)ndb, 64);
   v.drho = v.dss + align_up((size_t)ndb, 64);
   v.bytes = (size_t)np * v.slot + 3 * align_up((size_t)ndb, 64) * sizeof(float);
   return v;
 }
 
-// Shapes the screened search serves (option topk_screen: 0 = never, 1 = wherever the shape allows, -1 (default) = where it
-// pays: >= 256 queries against >= 16 384 rows of >= 4096 columns): the h3 score panels' shapes with k <= 128, rows the re-scoring kernel holds
-// in registers, and a score buffer of at most 12 GiB (fewer columns per range for more queries)
-int64_t screen_cols(int64_t nq, int64_t ndb, int64_t dim, int64_t k, bool h3) {
-  const int64_t mode = option(OPT_TOPK_SCREEN);
-  if (!h3 || mode == 0 || k > SCREEN_KMAX || k <= 0 || !screen_rescore_supported(dim) || nq <= 0 || ndb <= 0) return 0;
-  if (mode < 0 && !(nq >= 256 && ndb >= 16384 && dim >= 4096)) return 0;
-  const int64_t panel = std::min(H3_PANEL, h3_rows_limit(dim));
-  int64_t cols = std::min<int64_t>(SCREEN_COLS, (ndb + panel - 1) / panel * panel);
-  const int64_t fit = (int64_t)(SCREEN_SBUF_MAX / 4) / nq / panel * panel;
-  cols = std::min(cols, fit);
-  return cols >= panel ? cols : 0;
+// One search: the caller's arguments, the plan, the carved workspace and the index, for the steps below
+struct TopkCall {
+  const float *queries, *db;       // db == nullptr: a prepared index without its fp32 rows
+  int metric;
+  bool norm_db, rescore_planes;
+  int64_t index_base;
+  float* dist;
+  long long* idx;
+  hipStream_t stream;
+  TopkPlan p;
+  TopkWs w;
+  IndexView iv;                    // of the prepared index, if any
+};
+
+int launch_rownorm(const float* x, int64_t rows, int64_t dim, float* out, const char* what, hipStream_t stream) {
+  hipLaunchKernelGGL(rownorm_sq_kernel, dim3((unsigned)rows), dim3(256), 0, stream, x, dim, out);
+  return launch_status(what);
+}
+int launch_dbnorm(const float* ss, int64_t n, float* dnorm, float* dn, hipStream_t stream) {
+  hipLaunchKernelGGL(dbnorm_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream, ss, n, dnorm, dn);
+  return launch_status("dbnorm_kernel");
+}
+// merges score columns [col0, col0 + ncols) into the lists run_v / run_i; no columns: an empty database's padding list, not profiled
+int launch_merge(const TopkCall& c, const float* scores, int64_t ld, int64_t ncols, int64_t col0, const float* dn, const float* dnorm,
+                 float* run_v, long long* run_i, int first) {
+  static_assert(PANEL <= 0x8000 && H3_PANEL <= PANEL && CAP + KMAX + 2 <= 0xffff, "merge keys hold the column in 15 bits and the slot in 16");
+  const size_t k2 = (size_t)((c.p.k + 1) & ~1ll), lds = 16 * (k2 + CAP) + 12 * k2 + 16;   // 37 KiB at k = 20: four blocks per CU
+  std::optional<ProfScope> prof;
+  if (ncols > 0) prof.emplace("topk_merge", c.stream, 0.0, 4.0 * c.p.nq * ncols);
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)c.p.nq), dim3(256), lds, c.stream, scores, ld, ncols, c.index_base + col0,
+                     (int)c.p.k, c.metric, c.w.qn, dn, dnorm, run_v, run_i, first);
+  return launch_status("topk_merge_kernel");
 }
 
-TopkWs carve(void* ws, size_t cap, int64_t nq, int64_t ndb, int64_t dim, bool indexed = false, int64_t k = 0) {
-  Arena a(ws, cap);
-  TopkWs w;
-  const bool h3 = indexed || h3_scores(nq, ndb, dim);
-  w.panel = h3 ? std::min(H3_PANEL, h3_rows_limit(dim)) : PANEL;
-  w.q_chunk = h3 ? std::min<int64_t>(nq, h3_rows_limit(dim)) : nq;
-  const int64_t panel = std::min<int64_t>(w.panel, std::max<int64_t>(ndb, 1));
-  w.scores = a.take<float>(std::max<int64_t>(nq, 1) * panel);
-  const int64_t n_qchunks = h3 ? (nq + w.q_chunk - 1) / w.q_chunk : 0;
-  // (few-query fp16 path: the queries' pre-split planes, 10 KiB per 32-k slab)
-  w.qimg = a.take<unsigned char>(h3 ? (size_t)n_qchunks * h2_bytes(w.q_chunk, dim) : few_queries(nq, dim) ? fewq_query_image_bytes(dim) : 1);
-  w.dimg = a.take<unsigned char>(h3 && !indexed ? h2_bytes(panel, dim) : 1);
-  w.qinv = a.take<float>(h3 ? nq : 64);                  // (few-query fp16 path: the <= 64 queries' row scales)
-  w.dinv = a.take<float>(h3 && !indexed ? panel : 1);
-  w.qn = a.take<float>(std::max<int64_t>(nq, 1));
-  w.dn = a.take<float>(std::max<int64_t>(ndb, 1));
-  w.dss = a.take<float>(std::max<int64_t>(ndb, 1));
-  w.dnorm = a.take<float>(std::max<int64_t>(ndb, 1));
-  const bool few = !indexed && few_queries(nq, dim);
-  w.part = a.take<float>(few ? (size_t)SPLITK_MAX * panel * 64 : 1);
-  w.rsq_part = a.take<float>(few ? (size_t)SPLITK_MAX * panel : 1);
-  w.sc_cols = screen_cols(nq, ndb, dim, k, h3);
-  const bool sc = w.sc_cols > 0;
-  w.sbuf = a.take<float>(sc ? (size_t)nq * w.sc_cols : 1);
-  w.scr_v = a.take<float>(sc ? (size_t)nq * k : 1);
-  w.scr_i = a.take<long long>(sc ? (size_t)nq * k : 1);
-  w.margin = a.take<float>(sc ? (size_t)nq : 1);
-  w.cand = a.take<int>(sc ? (size_t)nq * SCREEN_CMAX : 1);
-  w.cand_v = a.take<float>(sc ? (size_t)nq * SCREEN_CMAX : 1);
-  w.count = a.take<int>(sc ? (size_t)nq : 1);
-  w.rho_q = a.take<float>(sc ? (size_t)nq : 1);
-  w.rho_d = a.take<float>(sc && !indexed ? (size_t)std::max<int64_t>(ndb, 1) : 1);
-  w.resid = a.take<float>(sc && !indexed ? (size_t)panel : 1);
-  w.overflow = a.take<int>(4);                            // [0] overflow flag, [1] bits of the largest database rho, [2] of the largest raw sum of squares
-  w.bytes = a.off;
-  return w;
+// fp16 panels: f(first query, queries, their operand image) for every chunk of q_chunk queries
+template <class F> int each_query_chunk(const TopkCall& c, F f) {
+  for (int64_t q0 = 0, i = 0; q0 < c.p.nq; q0 += c.p.q_chunk, ++i)
+    ANYLOC_TRY(f(q0, std::min(c.p.q_chunk, c.p.nq - q0), c.w.qimg + i * h2_bytes(c.p.q_chunk, c.p.dim)));
+  return ANYLOC_OK;
+}
+
+// A database panel as the score GEMM's operand: image, row scales, the rows' raw sums of squares (where the call uses them), and,
+// normalising, its dnorm / dn.  Source: the slot of the prepared index; or the rows quantised now (split_h2_wide); or, screening on
+// the rows, their leading plane alone (split_h1_wide), whose residual norms -- the bound -- come out of the quantiser itself.
+struct DbPanel { const unsigned char* img; const float *inv, *ss; };
+int db_panel(const TopkCall& c, int64_t c0, int64_t pc, bool leading_plane, DbPanel& d) {
+  const TopkWs& w = c.w;
+  const int64_t dim = c.p.dim;
+  if (c.p.indexed) {
+    d = {c.iv.img + (size_t)(c0 / c.iv.panel) * c.iv.slot, c.iv.dinv + c0, c.iv.dss + c0};
+  } else if (leading_plane) {
+    d = {w.dimg, w.dinv, w.dss + c0};
+    ANYLOC_HIP(hipMemsetAsync(w.resid, 0, (size_t)pc * sizeof(float), c.stream));
+    ANYLOC_TRY(split_h1_wide(c.db + c0 * dim, dim, pc, dim, w.dimg, w.dinv, w.dss + c0, w.resid, c.stream));
+    ANYLOC_TRY(screen_rho_from_resid(w.resid, w.dinv, w.dss + c0, pc, w.rho_d + c0, reinterpret_cast<unsigned*>(w.overflow + 1), c.stream));
+  } else {   // the sums of squares are the L2 term as they are, or, normalising, what dnorm / dn are made of
+    float* ss = c.norm_db ? w.dss + c0 : c.metric == 1 ? w.dn + c0 : nullptr;
+    d = {w.dimg, w.dinv, ss};
+    ANYLOC_TRY(split_h2_wide(c.db + c0 * dim, dim, pc, dim, w.dimg, w.dinv, ss, c.stream));
+  }
+  return c.norm_db ? launch_dbnorm(d.ss, pc, w.dnorm + c0, w.dn + c0, c.stream) : ANYLOC_OK;
+}
+
+// scores of all queries against one panel on the fp16 planes -> C[nq, ldc], k-chunk by k-chunk (the later ones add):
+// exact = the two-term GEMM in chunks of SCORE_KC16 k-blocks, otherwise the leading planes alone in chunks of SCREEN_KC16
+int score_panel(const TopkCall& c, const DbPanel& d, int64_t pc, bool exact, float* C, int64_t ldc) {
+  const int64_t K16 = c.p.dim / 16, KC16 = exact ? SCORE_KC16 : SCREEN_KC16;
+  return each_query_chunk(c, [&](int64_t q0, int64_t qc, const unsigned char* qimg) {
+    for (int64_t kb0 = 0; kb0 < K16; kb0 += KC16) {
+      H3Problem h{};
+      h.A2 = qimg + kb0 * (2 * qc * 32); h.RA = qc; h.a_inv = c.w.qinv + q0;
+      h.W2 = d.img + kb0 * (2 * pc * 32); h.RW = pc; h.w_inv = d.inv;
+      h.C = C + q0 * ldc; h.ldc = ldc;
+      h.M = qc; h.N = pc; h.K16 = (int)std::min<int64_t>(KC16, K16 - kb0);
+      h.accumulate = kb0 > 0; h.tag = exact ? "topk_scores_gemm" : "topk_screen_gemm";
+      ANYLOC_TRY(exact ? gemm_h3(h, EPI_STORE, c.stream) : gemm_screen(h, c.stream));
+    }
+    return (int)ANYLOC_OK;
+  });
+}
+
+// what both searches start from: the queries' squared norms (L2, and the screening bound), the database rows' norms where no
+// scoring pass delivers them (fp32 panels), and the queries' operand images, built once per call
+int prologue(const TopkCall& c, bool screen) {
+  const TopkWs& w = c.w;
+  const int64_t nq = c.p.nq, ndb = c.p.ndb, dim = c.p.dim;
+  if (c.metric == 1 || screen) ANYLOC_TRY(launch_rownorm(c.queries, nq, dim, w.qn, "rownorm_sq_kernel(q)", c.stream));
+  if ((c.metric == 1 || c.norm_db) && c.p.path == PATH_F32) {
+    ProfScope prof("topk_db_norms", c.stream, 2.0 * ndb * dim, 4.0 * ndb * dim);
+    float* ss = c.norm_db ? w.dss : w.dn;
+    for (int64_t r0 = 0; r0 < ndb; r0 += (1ll << 30))
+      ANYLOC_TRY(launch_rownorm(c.db + r0 * dim, std::min<int64_t>(1ll << 30, ndb - r0), dim, ss + r0, "rownorm_sq_kernel(db)", c.stream));
+    if (c.norm_db && ndb > 0) ANYLOC_TRY(launch_dbnorm(w.dss, ndb, w.dnorm, w.dn, c.stream));
+  }
+  if (ndb == 0) return ANYLOC_OK;
+  if (c.p.path == PATH_H3) {
+    ANYLOC_TRY(each_query_chunk(c, [&](int64_t q0, int64_t qc, unsigned char* qimg) {
+      return split_h2_wide(c.queries + q0 * dim, dim, qc, dim, qimg, w.qinv + q0, nullptr, c.stream);
+    }));
+  } else if (c.p.path == PATH_FEWQ && c.p.fewq == 2) {   // few queries on fp16 planes: their row scales and, pre-split, their planes
+    ANYLOC_TRY(row_scales_h2(c.queries, dim, nq, dim, w.qinv, nullptr, c.stream));
+    if (c.p.qdma) ANYLOC_TRY(fewq_query_image(c.queries, dim, nq, w.qinv, dim, w.qimg, c.stream));
+  }
+  return ANYLOC_OK;
+}
+
+// every panel scored exactly and merged into the caller's lists (values still in merge order: topk_impl finishes them)
+int panel_search(const TopkCall& c) {
+  const TopkWs& w = c.w;
+  const int64_t nq = c.p.nq, ndb = c.p.ndb, dim = c.p.dim;
+  if (ndb == 0) ANYLOC_TRY(launch_merge(c, w.scores, 0, 0, 0, w.dn, nullptr, c.dist, c.idx, 1));   // nothing to search: the padding list
+  for (int64_t c0 = 0; c0 < ndb; c0 += c.p.panel) {
+    const int64_t pc = std::min<int64_t>(c.p.panel, ndb - c0);
+    const float* dn = w.dn + c0;                            // the merge kernel's squared-norm term of the panel's rows (L2)
+    if (c.p.path == PATH_H3) {
+      DbPanel d;
+      ANYLOC_TRY(db_panel(c, c0, pc, false, d));
+      if (!c.norm_db) dn = d.ss;
+      ANYLOC_TRY(score_panel(c, d, pc, true, w.scores, pc));
+    } else if (c.p.path == PATH_FEWQ) {
+      // K cut into slices: enough workgroups to stream the panel at HBM rate; the rows' sums of squares come out of the same pass
+      const int S = choose_ksplit(pc, dim);
+      const float* rows = c.db + c0 * dim;
+      float* ss = (c.norm_db ? w.dss : w.dn) + c0;
+      if (c.p.fewq == 2) {
+        ANYLOC_TRY(scores_fewq_h3(rows, dim, pc, c.queries, dim, nq, w.qinv, c.p.qdma ? w.qimg : nullptr, dim / S, S, w.part, w.rsq_part, c.stream));
+      } else if (c.p.fewq != 0) {
+        ANYLOC_TRY(scores_fewq_x6(rows, dim, pc, c.queries, dim, nq, dim / S, S, w.part, w.rsq_part, c.stream));
+      } else {
+        GemmProblem g{};
+        g.A = rows; g.lda = dim; g.W = c.queries; g.ldw = dim;
+        g.C = w.part; g.ldc = 64; g.ksplit = S; g.c_split_stride = pc * 64; g.rowsq = w.rsq_part;
+        g.M = pc; g.N = nq; g.K = dim / S; g.tag = "topk_scores_gemm";
+        ANYLOC_TRY(gemm_nt_splitk(g, c.stream));
+      }
+      {
+        ProfScope prof("topk_combine", c.stream, (double)S * pc * 64, 4.0 * ((double)S * pc * 65 + (double)nq * pc));
+        hipLaunchKernelGGL(splitk_combine_kernel, dim3((unsigned)cdiv(pc, 256)), dim3(256), 0, c.stream, w.part, w.rsq_part, S, pc,
+                           (int)nq, w.scores, ss);
+        ANYLOC_TRY(launch_status("splitk_combine_kernel"));
+      }
+      if (c.norm_db) ANYLOC_TRY(launch_dbnorm(ss, pc, w.dnorm + c0, w.dn + c0, c.stream));
+    } else {
+      GemmProblem g{};
+      g.A = c.queries; g.lda = dim; g.W = c.db + c0 * dim; g.ldw = dim;
+      g.C = w.scores; g.ldc = pc;
+      g.M = nq; g.N = pc; g.K = dim; g.tag = "topk_scores_gemm";
+      ANYLOC_TRY(gemm_nt(g, EPI_STORE, c.stream));
+    }
+    ANYLOC_TRY(launch_merge(c, w.scores, pc, pc, c0, dn, c.norm_db ? w.dnorm + c0 : nullptr, c.dist, c.idx, c0 == 0));
+  }
+  return ANYLOC_OK;
+}
+
+// The candidates are re-scored from the fp32 rows (a prepared index WITH its rows: anyloc_topk_search_index_rows) or, with
+// ANYLOC_TOPK_RESCORE_PLANES, from the two planes of the index (the 22-bit rows it holds, which the unscreened indexed search scores
+// too): no rows needed, and none read when they are given.  The bound of a query is one number: its own norm and residual x the
+// LARGEST row norm the compared value sees -- 1 with ANYLOC_TOPK_NORMALIZE_DB, the largest raw row norm of the database without it.
+// Leaves w.overflow[0] != 0 when some query has more candidates than SCREEN_CMAX inside its bound (near-duplicate rows).
+int screened_search(const TopkCall& c) {
+  const TopkWs& w = c.w;
+  const int64_t nq = c.p.nq, ndb = c.p.ndb, dim = c.p.dim, K16 = dim / 16;
+  ANYLOC_HIP(hipMemsetAsync(w.overflow, 0, 3 * sizeof(int), c.stream));
+  unsigned* rho_max = reinterpret_cast<unsigned*>(w.overflow + 1);
+  unsigned* ss_max = reinterpret_cast<unsigned*>(w.overflow + 2);   // bits of the largest raw sum of squares (searches without NORMALIZE_DB)
+  // the queries' relative residual norms, from the residual planes of their images
+  ANYLOC_TRY(each_query_chunk(c, [&](int64_t q0, int64_t qc, const unsigned char* qimg) {
+    return screen_resid(qimg, qc, (int)K16, qc, w.qinv + q0, w.qn + q0, w.rho_q + q0, nullptr, c.stream);
+  }));
+  for (int64_t s0 = 0; s0 < ndb; s0 += c.p.sc_cols) {
+    const int64_t sn = std::min<int64_t>(c.p.sc_cols, ndb - s0);
+    const float* dnorm_s = c.norm_db ? w.dnorm + s0 : nullptr;      // the divisors of the compared value, or none
+    for (int64_t c0 = s0; c0 < s0 + sn; c0 += c.p.panel) {
+      const int64_t pc = std::min<int64_t>(c.p.panel, s0 + sn - c0);
+      DbPanel d;
+      ANYLOC_TRY(db_panel(c, c0, pc, true, d));
+      if (!c.norm_db) {
+        // raw rows: the L2 term is the raw sum of squares; the bound scales with the largest raw norm seen so far
+        ANYLOC_HIP(hipMemcpyAsync(w.dn + c0, d.ss, (size_t)pc * sizeof(float), hipMemcpyDeviceToDevice, c.stream));
+        ANYLOC_TRY(screen_rho_max(d.ss, pc, ss_max, c.stream));
+      }
+      ANYLOC_TRY(score_panel(c, d, pc, false, w.sbuf + (c0 - s0), sn));
+      ANYLOC_TRY(launch_merge(c, w.sbuf + (c0 - s0), sn, pc, c0, w.dn + c0, c.norm_db ? w.dnorm + c0 : nullptr, w.scr_v, w.scr_i, c0 == s0));
+    }
+    if (c.p.indexed) ANYLOC_TRY(screen_rho_max(c.iv.drho + s0, sn, rho_max, c.stream));
+    ANYLOC_TRY(screen_margins(w.qn, w.rho_q, rho_max, c.norm_db ? nullptr : ss_max, nq, c.metric,
+                              screen_accum((int)std::min(SCREEN_KC16, K16), (int)cdiv(K16, SCREEN_KC16)), w.margin, c.stream));
+    ANYLOC_TRY(screen_compact(w.sbuf, sn, sn, nq, (int)c.p.k, c.metric, w.qn, w.dn + s0, dnorm_s, w.scr_v, w.margin, SCREEN_CMAX, w.cand,
+                              w.count, w.overflow, c.stream));
+    if (c.rescore_planes)
+      ANYLOC_TRY(screen_rescore_planes(c.queries, c.iv.img, c.iv.slot, c.iv.panel, ndb, s0, c.iv.dinv, dim, nq, SCREEN_CMAX, w.cand, w.count,
+                                       c.metric, w.qn, w.dn + s0, dnorm_s, w.cand_v, c.stream));
+    else
+      ANYLOC_TRY(screen_rescore(c.queries, c.db + s0 * dim, dim, nq, SCREEN_CMAX, w.cand, w.count, c.metric, w.qn, w.dn + s0, dnorm_s,
+                                w.cand_v, c.stream));
+    ANYLOC_TRY(screen_select(w.cand, w.cand_v, w.count, SCREEN_CMAX, c.index_base + s0, nq, (int)c.p.k, c.dist,
+                             reinterpret_cast<int64_t*>(c.idx), s0 == 0, c.stream));
+  }
+  return ANYLOC_OK;
+}
+
+// `index` != nullptr: the database side comes from a prepared index (db may be null)
+int topk_impl(const float* queries, int64_t nq, const float* db, int64_t ndb, int64_t dim, int64_t k, int metric, unsigned flags,
+              int64_t index_base, float* dist, int64_t* idx, void* workspace, size_t workspace_bytes, const void* index, hipStream_t stream) {
+  ANYLOC_CHECK_ARG(nq >= 0 && ndb >= 0, "topk: negative size");
+  if (nq == 0 || k == 0) return ANYLOC_OK;
+  ANYLOC_CHECK_ARG(queries && dist && idx, "topk: null pointer");
+  ANYLOC_CHECK_ARG(db || ndb == 0 || index, "topk: null database");
+  const bool indexed = index != nullptr;
+  ANYLOC_CHECK_ARG(k >= 1 && k <= KMAX, "topk: k=%lld outside [1,%d]", (long long)k, KMAX);
+  ANYLOC_CHECK_ARG(metric == 0 || metric == 1, "topk: metric %d", metric);
+  ANYLOC_CHECK_ARG(dim >= 4 && dim % 4 == 0, "topk: dim %lld must be a positive multiple of 4", (long long)dim);
+  ANYLOC_CHECK_ARG(nq < (1ll << 31), "topk: too many queries");
+  ANYLOC_CHECK_ARG((flags & ~(ANYLOC_TOPK_NORMALIZE_DB | (indexed ? ANYLOC_TOPK_RESCORE_PLANES : 0u))) == 0, "topk: unknown flags %u", flags);
+  TopkCall c{queries, db, metric, (flags & ANYLOC_TOPK_NORMALIZE_DB) != 0, indexed && (flags & ANYLOC_TOPK_RESCORE_PLANES) != 0,
+             index_base, dist, reinterpret_cast<long long*>(idx), stream, topk_plan(nq, ndb, dim, k, indexed)};
+  c.w = carve(workspace, workspace_bytes, c.p);
+  if (!workspace || c.w.bytes > workspace_bytes) {
+    set_error("topk: workspace %zu < %zu", workspace_bytes, c.w.bytes);
+    return ANYLOC_ERR_WORKSPACE;
+  }
+  if (indexed) c.iv = index_view(const_cast<void*>(index), ndb, dim);
+  static DynLds dyn_lds_once;   // the merge kernel's dynamic LDS at the largest k
+  ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(topk_merge_kernel), (int)(16 * (KMAX + CAP) + 12 * KMAX + 16)));
+  // whether this call screens: the plan allows it, and there is something to re-score the candidates from
+  const bool screen = c.p.sc_cols > 0 && (db != nullptr || c.rescore_planes) && ndb > 0;
+  ANYLOC_TRY(prologue(c, screen));
+  int overflow = 0;
+  if (screen) {   // the one wait of a call: the overflow flag decides between finishing and the unscreened search
+    ANYLOC_TRY(screened_search(c));
+    ANYLOC_HIP(hipMemcpyAsync(&overflow, c.w.overflow, sizeof(int), hipMemcpyDeviceToHost, stream));
+    ANYLOC_HIP(hipStreamSynchronize(stream));
+  }
+  if (!screen || overflow) ANYLOC_TRY(panel_search(c));
+  // padding entries carry index -1 regardless of index_base (faiss); L2 distances are sign-flipped back
+  hipLaunchKernelGGL(topk_finish_kernel, dim3((unsigned)cdiv(nq * k, 256)), dim3(256), 0, stream, dist, c.idx, nq * k, metric);
+  return launch_status("topk_finish_kernel");
 }
 
 }  // namespace
@@ -383,265 +637,11 @@ using namespace anyloc;
 extern "C" {
 
 size_t anyloc_topk_workspace_bytes(int64_t nq, int64_t ndb, int64_t dim, int64_t k) {
-  return carve(nullptr, 0, nq, ndb, dim, false, k).bytes + 256;
+  return carve(nullptr, 0, topk_plan(nq, ndb, dim, k, false)).bytes + 256;
 }
 
-}  // extern "C"
-
-// the search; `index` != nullptr: the database side comes from a prepared index (db may be null), every query count runs
-// on the fp16 score panels
-static int topk_impl(const float* queries, int64_t nq, const float* db, int64_t ndb, int64_t dim, int64_t k, int metric,
-                     unsigned flags, int64_t index_base, float* dist, int64_t* idx, void* workspace, size_t workspace_bytes,
-                     const void* index, hipStream_t stream, bool allow_screen = true) {
-  ANYLOC_CHECK_ARG(nq >= 0 && ndb >= 0, "topk: negative size");
-  if (nq == 0 || k == 0) return ANYLOC_OK;
-  ANYLOC_CHECK_ARG(queries && dist && idx, "topk: null pointer");
-  ANYLOC_CHECK_ARG(db || ndb == 0 || index, "topk: null database");
-  const bool indexed = index != nullptr;
-  const IndexView iv = indexed ? index_view(const_cast<void*>(index), ndb, dim) : IndexView{};
-  ANYLOC_CHECK_ARG(k >= 1 && k <= KMAX, "topk: k=%lld outside [1,%d]", (long long)k, KMAX);
-  ANYLOC_CHECK_ARG(metric == 0 || metric == 1, "topk: metric %d", metric);
-  ANYLOC_CHECK_ARG(dim >= 4 && dim % 4 == 0, "topk: dim %lld must be a positive multiple of 4", (long long)dim);
-  ANYLOC_CHECK_ARG(nq < (1ll << 31), "topk: too many queries");
-  ANYLOC_CHECK_ARG((flags & ~(ANYLOC_TOPK_NORMALIZE_DB | (indexed ? ANYLOC_TOPK_RESCORE_PLANES : 0u))) == 0, "topk: unknown flags %u", flags);
-  TopkWs w = carve(workspace, workspace_bytes, nq, ndb, dim, indexed, k);
-  const bool norm_db = (flags & ANYLOC_TOPK_NORMALIZE_DB) != 0;
-  const bool few = !indexed && few_queries(nq, dim);
-  const bool h3 = indexed || h3_scores(nq, ndb, dim);
-  const int64_t PANEL_ROWS = w.panel;
-  if (!workspace || w.bytes > workspace_bytes) {
-    set_error("topk: workspace %zu < %zu", workspace_bytes, w.bytes);
-    return ANYLOC_ERR_WORKSPACE;
-  }
-  static_assert(PANEL <= 0x8000 && H3_PANEL <= PANEL && CAP + KMAX + 2 <= 0xffff,
-                "merge keys hold the column in 15 bits and the slot in 16");
-  const size_t k2 = (size_t)((k + 1) & ~1ll);
-  const size_t lds = 16 * (k2 + CAP) + 12 * k2 + 16;      // 37 KiB at k = 20: four blocks per CU
-  static DynLds dyn_lds_once;
-  ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(topk_merge_kernel), (int)(16 * (KMAX + CAP) + 12 * KMAX + 16)));
-  // screened search (scores_screen.hip): the panels are scored on the leading fp16 planes alone, the rows their error bound
-  // cannot rule out are re-scored exactly from the fp32 rows -- needs those rows (a prepared index WITH its rows:
-  // anyloc_topk_search_index_rows).  The bound of a query is one number: its own norm and residual x the LARGEST row norm the
-  // compared value sees -- 1 with ANYLOC_TOPK_NORMALIZE_DB, the largest raw row norm of the database without it.
-  // ANYLOC_TOPK_RESCORE_PLANES: the candidates are re-scored from the two planes of the index instead (the 22-bit rows the
-  // index holds, which the unscreened indexed search scores too) -- no rows needed, and none read when they are given
-  const bool rescore_planes = indexed && (flags & ANYLOC_TOPK_RESCORE_PLANES) != 0;
-  const bool screen = allow_screen && h3 && w.sc_cols > 0 && (db != nullptr || rescore_planes) && ndb > 0;
-  if (metric == 1 || screen) {
-    hipLaunchKernelGGL(rownorm_sq_kernel, dim3((unsigned)nq), dim3(256), 0, stream, queries, dim, w.qn);
-    ANYLOC_TRY(launch_status("rownorm_sq_kernel(q)"));
-  }
-  if ((metric == 1 || norm_db) && !few && !h3) {   // (the few-query and fp16 paths get the rows' sums of squares from their own pass)
-    ProfScope prof("topk_db_norms", stream, 2.0 * ndb * dim, 4.0 * ndb * dim);
-    float* ss = norm_db ? w.dss : w.dn;
-    for (int64_t r0 = 0; r0 < ndb; r0 += (1ll << 30)) {
-      const int64_t cnt = std::min<int64_t>(1ll << 30, ndb - r0);
-      hipLaunchKernelGGL(rownorm_sq_kernel, dim3((unsigned)cnt), dim3(256), 0, stream, db + r0 * dim, dim, ss + r0);
-      ANYLOC_TRY(launch_status("rownorm_sq_kernel(db)"));
-    }
-    if (norm_db && ndb > 0) {
-      hipLaunchKernelGGL(dbnorm_kernel, dim3((unsigned)((ndb + 255) / 256)), dim3(256), 0, stream, w.dss, ndb, w.dnorm, w.dn);
-      ANYLOC_TRY(launch_status("dbnorm_kernel"));
-    }
-  }
-  long long* idx_ll = reinterpret_cast<long long*>(idx);
-  int first = 1;
-  if (ndb == 0) {
-    // nothing to search: emit the padding list
-    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)nq), dim3(256), lds, stream, w.scores, (int64_t)0,
-                       (int64_t)0, index_base, (int)k, metric, w.qn, w.dn, (const float*)nullptr, dist, idx_ll, 1);
-    ANYLOC_TRY(launch_status("topk_merge_kernel"));
-  }
-  if (h3 && ndb > 0)
-    for (int64_t q0 = 0, c = 0; q0 < nq; q0 += w.q_chunk, ++c) {
-      const int64_t qc = std::min<int64_t>(w.q_chunk, nq - q0);
-      ANYLOC_TRY(split_h2_wide(queries + q0 * dim, dim, qc, dim, w.qimg + c * h2_bytes(w.q_chunk, dim), w.qinv + q0, nullptr, stream));
-    }
-  if (screen) {
-    const int64_t K16 = dim / 16;
-    const int64_t KC16 = 1536;                               // k-blocks per accumulated chunk (the bound's accumulation term)
-    const int nchunks = (int)((K16 + KC16 - 1) / KC16);
-    ANYLOC_HIP(hipMemsetAsync(w.overflow, 0, 3 * sizeof(int), stream));
-    unsigned* rho_max = reinterpret_cast<unsigned*>(w.overflow + 1);
-    unsigned* ss_max = reinterpret_cast<unsigned*>(w.overflow + 2);   // bits of the largest raw sum of squares (searches without NORMALIZE_DB)
-    const float* dnorm_all = norm_db ? w.dnorm : nullptr;             // the divisor array of the compared value, or none
-    // the queries' relative residual norms, from the residual planes of their images
-    for (int64_t q0 = 0, c = 0; q0 < nq; q0 += w.q_chunk, ++c) {
-      const int64_t qc = std::min<int64_t>(w.q_chunk, nq - q0);
-      ANYLOC_TRY(screen_resid(w.qimg + c * h2_bytes(w.q_chunk, dim), qc, (int)K16, qc, w.qinv + q0, w.qn + q0, w.rho_q + q0, nullptr, stream));
-    }
-    int first_exact = 1;
-    for (int64_t s0 = 0; s0 < ndb; s0 += w.sc_cols) {
-      const int64_t sn = std::min<int64_t>(w.sc_cols, ndb - s0);
-      int first_scr = 1;
-      for (int64_t c0 = s0; c0 < s0 + sn; c0 += PANEL_ROWS) {
-        const int64_t pc = std::min<int64_t>(PANEL_ROWS, s0 + sn - c0);
-        const unsigned char* dimg = w.dimg;
-        const float* dinv = w.dinv;
-        const float* dss = w.dss + c0;
-        if (indexed) {
-          dimg = iv.img + (size_t)(c0 / iv.panel) * iv.slot;
-          dinv = iv.dinv + c0;
-          dss = iv.dss + c0;
-        } else {
-          // leading plane only; the residual norms come out of the quantiser itself
-          ANYLOC_HIP(hipMemsetAsync(w.resid, 0, (size_t)pc * sizeof(float), stream));
-          ANYLOC_TRY(split_h1_wide(db + c0 * dim, dim, pc, dim, w.dimg, w.dinv, w.dss + c0, w.resid, stream));
-          ANYLOC_TRY(screen_rho_from_resid(w.resid, w.dinv, w.dss + c0, pc, w.rho_d + c0, rho_max, stream));
-        }
-        if (norm_db) {
-          hipLaunchKernelGGL(dbnorm_kernel, dim3((unsigned)((pc + 255) / 256)), dim3(256), 0, stream, dss, pc, w.dnorm + c0, w.dn + c0);
-          ANYLOC_TRY(launch_status("dbnorm_kernel"));
-        } else {
-          // raw rows: the L2 term is the raw sum of squares; the bound scales with the largest raw norm seen so far
-          if (dss != w.dn + c0) ANYLOC_HIP(hipMemcpyAsync(w.dn + c0, dss, (size_t)pc * sizeof(float), hipMemcpyDeviceToDevice, stream));
-          ANYLOC_TRY(screen_rho_max(dss, pc, ss_max, stream));
-        }
-        for (int64_t q0 = 0, c = 0; q0 < nq; q0 += w.q_chunk, ++c) {
-          const int64_t qc = std::min<int64_t>(w.q_chunk, nq - q0);
-          for (int64_t kb0 = 0; kb0 < K16; kb0 += KC16) {
-            H3Problem h{};
-            h.A2 = w.qimg + c * h2_bytes(w.q_chunk, dim) + kb0 * (2 * qc * 32); h.RA = qc; h.a_inv = w.qinv + q0;
-            h.W2 = dimg + kb0 * (2 * pc * 32); h.RW = pc; h.w_inv = dinv;
-            h.C = w.sbuf + q0 * sn + (c0 - s0); h.ldc = sn;
-            h.M = qc; h.N = pc; h.K16 = (int)std::min<int64_t>(KC16, K16 - kb0);
-            h.accumulate = kb0 > 0;
-            h.tag = "topk_screen_gemm";
-            ANYLOC_TRY(gemm_screen(h, stream));
-          }
-        }
-        {
-          ProfScope prof("topk_merge", stream, 0.0, 4.0 * nq * pc);
-          hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)nq), dim3(256), lds, stream, w.sbuf + (c0 - s0), sn, pc, index_base + c0,
-                             (int)k, metric, w.qn, w.dn + c0, dnorm_all ? dnorm_all + c0 : (const float*)nullptr, w.scr_v, w.scr_i, first_scr);
-          ANYLOC_TRY(launch_status("topk_merge_kernel"));
-        }
-        first_scr = 0;
-      }
-      if (indexed) ANYLOC_TRY(screen_rho_max(iv.drho + s0, sn, rho_max, stream));
-      ANYLOC_TRY(screen_margins(w.qn, w.rho_q, rho_max, norm_db ? nullptr : ss_max, nq, metric,
-                                screen_accum((int)std::min(KC16, K16), nchunks), w.margin, stream));
-      const float* dnorm_s = dnorm_all ? dnorm_all + s0 : nullptr;
-      ANYLOC_TRY(screen_compact(w.sbuf, sn, sn, nq, (int)k, metric, w.qn, w.dn + s0, dnorm_s, w.scr_v, w.margin, SCREEN_CMAX, w.cand,
-                                w.count, w.overflow, stream));
-      if (rescore_planes)
-        ANYLOC_TRY(screen_rescore_planes(queries, iv.img, iv.slot, iv.panel, ndb, s0, iv.dinv, dim, nq, SCREEN_CMAX, w.cand, w.count,
-                                         metric, w.qn, w.dn + s0, dnorm_s, w.cand_v, stream));
-      else
-        ANYLOC_TRY(screen_rescore(queries, db + s0 * dim, dim, nq, SCREEN_CMAX, w.cand, w.count, metric, w.qn, w.dn + s0, dnorm_s,
-                                  w.cand_v, stream));
-      ANYLOC_TRY(screen_select(w.cand, w.cand_v, w.count, SCREEN_CMAX, index_base + s0, nq, (int)k, dist, idx, first_exact, stream));
-      first_exact = 0;
-    }
-    int over = 0;
-    ANYLOC_HIP(hipMemcpyAsync(&over, w.overflow, sizeof(int), hipMemcpyDeviceToHost, stream));
-    ANYLOC_HIP(hipStreamSynchronize(stream));
-    if (over)   // some query has more candidates than SCREEN_CMAX inside its bound (near-duplicate rows): the unscreened search
-      return topk_impl(queries, nq, db, ndb, dim, k, metric, flags, index_base, dist, idx, workspace, workspace_bytes, index, stream, false);
-    hipLaunchKernelGGL(topk_finish_kernel, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, stream, dist, idx_ll, nq * k, metric);
-    return launch_status("topk_finish_kernel");
-  }
-  for (int64_t c0 = 0; c0 < ndb; c0 += PANEL_ROWS) {
-    const int64_t pc = std::min<int64_t>(PANEL_ROWS, ndb - c0);
-    GemmProblem g{};
-    g.tag = "topk_scores_gemm";
-    const float* dn_panel = w.dn + c0;                       // the merge kernel's squared-norm term of the panel's rows (L2)
-    if (h3) {
-      // the panel's operand image + its rows' sums of squares (raw: the L2 term; or, normalising, the F.normalize divisor):
-      // quantised here, or -- prepared index -- read where anyloc_topk_index_build left them
-      const bool want_ss = metric == 1 || norm_db;
-      const unsigned char* dimg = w.dimg;
-      const float* dinv = w.dinv;
-      const float* dss = w.dss + c0;
-      if (indexed) {
-        dimg = iv.img + (size_t)(c0 / iv.panel) * iv.slot;
-        dinv = iv.dinv + c0;
-        dss = iv.dss + c0;
-        if (metric == 1 && !norm_db) dn_panel = dss;
-      } else {
-        ANYLOC_TRY(split_h2_wide(db + c0 * dim, dim, pc, dim, w.dimg, w.dinv, want_ss ? (norm_db ? w.dss : w.dn) + c0 : nullptr, stream));
-      }
-      if (norm_db) {
-        hipLaunchKernelGGL(dbnorm_kernel, dim3((unsigned)((pc + 255) / 256)), dim3(256), 0, stream, dss, pc, w.dnorm + c0,
-                           w.dn + c0);
-        ANYLOC_TRY(launch_status("dbnorm_kernel"));
-      }
-      // A 49 152-long contraction in ONE fp32 accumulator takes ~9 000 rounded additions: 4e-6 on a score of 1.  Cut into
-      // chunks of 8192 k (one launch each, the later ones adding into the panel) the error is that of ~1 500 additions plus
-      // six: 5e-7 -- the chunked summation of the fp32-MFMA path (gemm_f32.hip, ABL bit 5) at the price of re-reading and
-      // re-writing the score panel per chunk (3 % of the GEMM time).
-      const int64_t K16 = dim / 16, KC16 = 512;
-      for (int64_t q0 = 0, c = 0; q0 < nq; q0 += w.q_chunk, ++c) {
-        const int64_t qc = std::min<int64_t>(w.q_chunk, nq - q0);
-        for (int64_t kb0 = 0; kb0 < K16; kb0 += KC16) {
-          H3Problem h{};
-          h.A2 = w.qimg + c * h2_bytes(w.q_chunk, dim) + kb0 * (2 * qc * 32); h.RA = qc; h.a_inv = w.qinv + q0;
-          h.W2 = dimg + kb0 * (2 * pc * 32); h.RW = pc; h.w_inv = dinv;
-          h.C = w.scores + q0 * pc; h.ldc = pc;
-          h.M = qc; h.N = pc; h.K16 = (int)std::min<int64_t>(KC16, K16 - kb0);
-          h.accumulate = kb0 > 0;
-          h.tag = "topk_scores_gemm";
-          ANYLOC_TRY(gemm_h3(h, EPI_STORE, stream));
-        }
-      }
-    } else if (few) {
-      // database rows as the M operand, the (<= 64) queries as N, K cut into slices: enough workgroups to stream the
-      // panel at HBM rate; the row sums of squares of the database come out of the same pass
-      const int S = choose_ksplit(pc, dim);
-      g.A = db + c0 * dim; g.lda = dim;
-      g.W = queries; g.ldw = dim;
-      g.C = w.part; g.ldc = 64;
-      g.M = pc; g.N = nq; g.K = dim / S;
-      g.ksplit = S; g.c_split_stride = pc * 64;
-      g.rowsq = w.rsq_part;
-      const int64_t fewq = option(OPT_TOPK_FEWQ_X6);
-      if (fewq == 2) {
-        const bool qdma = option(OPT_TOPK_FEWQ_QDMA) != 0;
-        if (c0 == 0) {                                                                 // once per call: the queries' row scales and planes
-          ANYLOC_TRY(row_scales_h2(queries, dim, nq, dim, w.qinv, nullptr, stream));
-          if (qdma) ANYLOC_TRY(fewq_query_image(queries, dim, nq, w.qinv, dim, w.qimg, stream));
-        }
-        ANYLOC_TRY(scores_fewq_h3(g.A, g.lda, pc, queries, dim, nq, w.qinv, qdma ? w.qimg : nullptr, g.K, S, w.part, w.rsq_part, stream));
-      } else if (fewq != 0)
-        ANYLOC_TRY(scores_fewq_x6(g.A, g.lda, pc, queries, dim, nq, g.K, S, w.part, w.rsq_part, stream));
-      else
-        ANYLOC_TRY(gemm_nt_splitk(g, stream));
-      ProfScope prof("topk_combine", stream, (double)S * pc * 64, 4.0 * ((double)S * pc * 65 + (double)nq * pc));
-      hipLaunchKernelGGL(splitk_combine_kernel, dim3((unsigned)((pc + 255) / 256)), dim3(256), 0, stream, w.part, w.rsq_part, S,
-                         pc, (int)nq, w.scores, (norm_db ? w.dss : w.dn) + c0);
-      ANYLOC_TRY(launch_status("splitk_combine_kernel"));
-      if (norm_db) {
-        hipLaunchKernelGGL(dbnorm_kernel, dim3((unsigned)((pc + 255) / 256)), dim3(256), 0, stream, w.dss + c0, pc, w.dnorm + c0,
-                           w.dn + c0);
-        ANYLOC_TRY(launch_status("dbnorm_kernel"));
-      }
-    } else {
-      g.A = queries; g.lda = dim;
-      g.W = db + c0 * dim; g.ldw = dim;
-      g.C = w.scores; g.ldc = pc;
-      g.M = nq; g.N = pc; g.K = dim;
-      ANYLOC_TRY(gemm_nt(g, EPI_STORE, stream));
-    }
-    {
-      ProfScope prof("topk_merge", stream, 0.0, 4.0 * nq * pc);
-      hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)nq), dim3(256), lds, stream, w.scores, pc, pc,
-                         index_base + c0, (int)k, metric, w.qn, dn_panel, norm_db ? w.dnorm + c0 : (const float*)nullptr, dist,
-                         idx_ll, first);
-      ANYLOC_TRY(launch_status("topk_merge_kernel"));
-    }
-    first = 0;
-  }
-  // padding entries carry index -1 regardless of index_base (faiss); L2 distances are sign-flipped back
-  hipLaunchKernelGGL(topk_finish_kernel, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, stream, dist, idx_ll,
-                     nq * k, metric);
-  return launch_status("topk_finish_kernel");
-}
-
-extern "C" {
-
-int anyloc_topk(const float* queries, int64_t nq, const float* db, int64_t ndb, int64_t dim, int64_t k, int metric,
-                unsigned flags, int64_t index_base, float* dist, int64_t* idx, void* workspace, size_t workspace_bytes,
-                void* stream) {
+int anyloc_topk(const float* queries, int64_t nq, const float* db, int64_t ndb, int64_t dim, int64_t k, int metric, unsigned flags,
+                int64_t index_base, float* dist, int64_t* idx, void* workspace, size_t workspace_bytes, void* stream) {
   ANYLOC_CHECK_ARG((flags & ANYLOC_TOPK_RESCORE_PLANES) == 0,
                    "topk: ANYLOC_TOPK_RESCORE_PLANES needs a prepared index (anyloc_topk_search_index / anyloc_topk_search_index_rows)");
   return topk_impl(queries, nq, db, ndb, dim, k, metric, flags, index_base, dist, idx, workspace, workspace_bytes, nullptr,
@@ -649,8 +649,7 @@ int anyloc_topk(const float* queries, int64_t nq, const float* db, int64_t ndb, 
 }
 
 int anyloc_topk_path(int64_t nq, int64_t ndb, int64_t dim) {
-  if (nq <= 0 || ndb < 0 || dim < 4 || dim % 4) return -1;
-  return h3_scores(nq, ndb, dim) ? 2 : few_queries(nq, dim) ? 1 : 0;
+  return nq <= 0 || ndb < 0 || dim < 4 || dim % 4 ? -1 : topk_plan(nq, ndb, dim, 0, false).path;
 }
 
 size_t anyloc_topk_index_bytes(int64_t ndb, int64_t dim) {
@@ -704,20 +703,19 @@ int anyloc_topk_index_build_range(const float* rows, int64_t row0, int64_t nrows
 }
 
 size_t anyloc_topk_index_workspace_bytes(int64_t nq, int64_t ndb, int64_t dim, int64_t k) {
-  return index_supported(ndb, dim) ? carve(nullptr, 0, nq, ndb, dim, true, k).bytes + 256 : 0;
+  return index_supported(ndb, dim) ? carve(nullptr, 0, topk_plan(nq, ndb, dim, k, true)).bytes + 256 : 0;
 }
 
 int anyloc_topk_search_index(const float* queries, int64_t nq, const void* index, int64_t ndb, int64_t dim, int64_t k, int metric,
-                             unsigned flags, int64_t index_base, float* dist, int64_t* idx, void* workspace,
-                             size_t workspace_bytes, void* stream) {
+                             unsigned flags, int64_t index_base, float* dist, int64_t* idx, void* workspace, size_t workspace_bytes, void* stream) {
   ANYLOC_CHECK_ARG(index && index_supported(ndb, dim), "topk_search_index: no index / shape not served by the fp16 score panels");
   return topk_impl(queries, nq, nullptr, ndb, dim, k, metric, flags, index_base, dist, idx, workspace, workspace_bytes, index,
                    static_cast<hipStream_t>(stream));
 }
 
-int anyloc_topk_search_index_rows(const float* queries, int64_t nq, const float* db, const void* index, int64_t ndb, int64_t dim,
-                                  int64_t k, int metric, unsigned flags, int64_t index_base, float* dist, int64_t* idx, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
+int anyloc_topk_search_index_rows(const float* queries, int64_t nq, const float* db, const void* index, int64_t ndb, int64_t dim, int64_t k,
+                                  int metric, unsigned flags, int64_t index_base, float* dist, int64_t* idx, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
   ANYLOC_CHECK_ARG(index && index_supported(ndb, dim), "topk_search_index_rows: no index / shape not served by the fp16 score panels");
   return topk_impl(queries, nq, db, ndb, dim, k, metric, flags, index_base, dist, idx, workspace, workspace_bytes, index,
                    static_cast<hipStream_t>(stream));
