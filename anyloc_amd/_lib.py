@@ -75,6 +75,8 @@ SIGNATURES = {
     "anyloc_pool_tokens": (C.c_int, [c_f32p, C.c_void_p, c_i64, c_i64, c_i64, C.c_int, C.c_float, c_f32p, C.c_void_p]),
     "anyloc_pca_gram_f64": (C.c_int, [c_f32p, c_i64, c_i64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "anyloc_pca_axes_f64": (C.c_int, [C.c_void_p, c_i64, c_i64, c_i64, c_f32p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "anyloc_gemm_nt_f64": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, C.c_int, C.c_void_p,
+                                     C.c_void_p]),
     "anyloc_x3_bytes": (C.c_size_t, [c_i64, c_i64]),
     "anyloc_split_x3": (C.c_int, [c_f32p, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p]),
     "anyloc_gemm_nt_x6": (C.c_int, [C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_i64, c_i64, c_i64, c_i64, C.c_void_p]),

@@ -23,6 +23,7 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 // How a thread fetches it is a template parameter of the kernel: 0 one element at a time (any strides, either type),
 // 1 fp32 four at a time along c (cs == 1, the mean runs along c), 2 fp32 four at a time along r (rs == 1, the mean runs
 // along r and is loaded once); the host picks 1 / 2 when pointer and strides are 16-byte aligned and 4 | extent.
+// 3 / 4 are the same two for float64 (anyloc_gemm_nt_f64): two doubles per 16-byte load along c / along r, no mean.
 struct F64Operand {
   const float* p32;
   const double* p64;
@@ -44,9 +45,18 @@ struct F64Regs {                                  // one operand's share of a st
   double d[V ? 1 : EPT];
 };
 
+template <>
+struct F64Regs<3> { double2 q[EPT / 2]; };
+template <>
+struct F64Regs<4> { double2 q[EPT / 2]; };
+
 template <int V>
 __device__ __forceinline__ void f64_coords(int idx, int cs_is_1, int& rr, int& cc) {
-  if (V == 1) { rr = idx / (TK / 4); cc = 4 * (idx % (TK / 4)); }          // 4 c's of one row
+  if (V == 3) { rr = (idx >> 2) % TM; cc = 2 * ((idx & 3) + 4 * (idx / (4 * TM))); }   // 2 c's of one row; 4 lanes read 64
+                                                   // contiguous bytes of it and a wave stashes 16 rows: rows of even c share their
+                                                   // LDS banks (2 LDT = 0 mod 32), so 4 lanes per bank pair instead of 16
+  else if (V == 4) { rr = 2 * (idx % (TM / 2)); cc = idx / (TM / 2); }     // 2 rows at one c
+  else if (V == 1) { rr = idx / (TK / 4); cc = 4 * (idx % (TK / 4)); }          // 4 c's of one row
   else if (V == 2) { rr = 4 * (idx % (TM / 4)); cc = idx / (TM / 4); }     // 4 rows at one c
   else if (cs_is_1) { cc = idx % TK; rr = idx / TK; }
   else { rr = idx % TM; cc = idx / TM; }
@@ -65,11 +75,20 @@ __device__ __forceinline__ void f64_row_means(const F64Operand& o, F64Regs<V>& g
   }
 }
 
-// (R, K are multiples of 4 in the vector modes -- the host checks -- so a fetched group is inside or outside as a whole;
-// outside groups become zeros: padding contributes nothing and has no mean subtracted)
+// (R, K are multiples of the group in the vector modes -- the host checks -- so a fetched group is inside or outside as a
+// whole; outside groups become zeros: padding contributes nothing and has no mean subtracted)
 template <int V>
 __device__ __forceinline__ void f64_fetch(const F64Operand& o, F64Regs<V>& g, int tid, int64_t r0, int64_t k0, int64_t R, int64_t K) {
-  if constexpr (V != 0) {
+  if constexpr (V >= 3) {
+#pragma unroll
+    for (int e = 0; e < EPT / 2; ++e) {
+      int rr, cc;
+      f64_coords<V>(e * NT + tid, 0, rr, cc);
+      const int64_t r = r0 + rr, c = k0 + cc;
+      const double* at = V == 3 ? o.p64 + r * o.rs + c : o.p64 + c * o.cs + r;
+      g.q[e] = (r < R && c < K) ? *reinterpret_cast<const double2*>(at) : double2{0.0, 0.0};
+    }
+  } else if constexpr (V != 0) {
 #pragma unroll
     for (int e = 0; e < EPT / 4; ++e) {
       int rr, cc;
@@ -104,7 +123,15 @@ __device__ __forceinline__ void f64_fetch(const F64Operand& o, F64Regs<V>& g, in
 template <int V>
 __device__ __forceinline__ void f64_stash(const F64Operand& o, const F64Regs<V>& g, double (*T)[LDT], int tid, int64_t r0,
                                           int64_t k0, int64_t R, int64_t K) {
-  if constexpr (V != 0) {
+  if constexpr (V >= 3) {
+#pragma unroll
+    for (int e = 0; e < EPT / 2; ++e) {
+      int rr, cc;
+      f64_coords<V>(e * NT + tid, 0, rr, cc);
+      if (V == 3) { T[cc][rr] = g.q[e].x; T[cc + 1][rr] = g.q[e].y; }
+      else *reinterpret_cast<double2*>(&T[cc][rr]) = g.q[e];          // rr and LDT are even: 16-byte aligned
+    }
+  } else if constexpr (V != 0) {
 #pragma unroll
     for (int e = 0; e < EPT / 4; ++e) {
       int rr, cc;
@@ -214,7 +241,15 @@ __global__ __launch_bounds__(NT) void gemm_f64_kernel(F64Operand A, F64Operand B
 }
 
 // vector fetches need whole groups of four inside the matrix, 16-byte aligned addresses and the mean along the other index
-int pick_vec(const F64Operand& o, int64_t R, int64_t K) {
+// (float64 operands: groups of two, no mean, and only where the caller asks for them -- the eigenvectors of
+// anyloc_pca_axes_f64 keep the element-wise fetch they were measured with)
+int pick_vec(const F64Operand& o, int64_t R, int64_t K, bool f64_vec) {
+  if (o.p64) {
+    if (!f64_vec || o.mean || (reinterpret_cast<uintptr_t>(o.p64) & 15)) return 0;
+    if (o.cs == 1 && K % 2 == 0 && o.rs % 2 == 0) return 3;
+    if (o.rs == 1 && R % 2 == 0 && o.cs % 2 == 0) return 4;
+    return 0;
+  }
   if (!o.p32 || (reinterpret_cast<uintptr_t>(o.p32) & 15)) return 0;
   if (o.cs == 1 && K % 4 == 0 && o.rs % 4 == 0 && (!o.mean || o.mean_on_c)) return 1;
   if (o.rs == 1 && R % 4 == 0 && o.cs % 4 == 0 && (!o.mean || !o.mean_on_c)) return 2;
@@ -235,10 +270,12 @@ int launch_f64(const F64Operand& A, const F64Operand& B, int64_t M, int64_t N, i
 }
 
 int gemm_f64(const F64Operand& A, const F64Operand& B, int64_t M, int64_t N, int64_t K, bool symmetric, double* C,
-             hipStream_t stream, const char* what) {
+             hipStream_t stream, const char* what, bool f64_vec = false) {
   ANYLOC_CHECK_ARG(M > 0 && N > 0 && K > 0 && ((M + TM - 1) / TM) * ((N + TM - 1) / TM) < (1ll << 31),
                    "%s: bad shape %lld x %lld x %lld", what, (long long)M, (long long)N, (long long)K);
-  const int va = pick_vec(A, M, K), vb = pick_vec(B, N, K);
+  const int va = pick_vec(A, M, K, f64_vec), vb = pick_vec(B, N, K, f64_vec);
+  if (va == 3 && vb == 3) return launch_f64<3, 3>(A, B, M, N, K, symmetric, C, stream, what);   // block x S, block x block^T
+  if (va == 3 && vb == 4) return launch_f64<3, 4>(A, B, M, N, K, symmetric, C, stream, what);   // small matrix x block
   if (va == 1 && vb == 1) return launch_f64<1, 1>(A, B, M, N, K, symmetric, C, stream, what);   // Gram
   if (va == 2 && vb == 2) return launch_f64<2, 2>(A, B, M, N, K, symmetric, C, stream, what);   // scatter
   if (vb == 2) return launch_f64<0, 2>(A, B, M, N, K, symmetric, C, stream, what);              // eigenvectors x data
@@ -272,4 +309,17 @@ extern "C" int anyloc_pca_axes_f64(const double* vec, int64_t sample_stride, int
   const F64Operand a{nullptr, vec, axis_stride, sample_stride, nullptr, 0};   // A(i, c) = component c of eigenvector i
   const F64Operand b{X, nullptr, 1, f, mean, 0};                              // B(j, c) = X[c, j] - mean[j]
   return gemm_f64(a, b, k, f, n, false, out, (hipStream_t)stream, "pca_axes_f64");
+}
+
+extern "C" int anyloc_gemm_nt_f64(const double* A, int64_t a_rs, int64_t a_cs, const double* B, int64_t b_rs, int64_t b_cs,
+                                  int64_t M, int64_t N, int64_t K, int symmetric, double* C, void* stream) {
+  using namespace anyloc;
+  ANYLOC_CHECK_ARG(A && B && C, "gemm_nt_f64: null pointer");
+  ANYLOC_CHECK_ARG(a_rs > 0 && a_cs > 0 && b_rs > 0 && b_cs > 0, "gemm_nt_f64: strides %lld / %lld, %lld / %lld must be positive",
+                   (long long)a_rs, (long long)a_cs, (long long)b_rs, (long long)b_cs);
+  ANYLOC_CHECK_ARG(!symmetric || (A == B && a_rs == b_rs && a_cs == b_cs && M == N),
+                   "gemm_nt_f64: symmetric needs A and B to be the same operand (and M == N)");
+  const F64Operand a{nullptr, A, a_rs, a_cs, nullptr, 0};
+  const F64Operand b{nullptr, B, b_rs, b_cs, nullptr, 0};
+  return gemm_f64(a, b, M, N, K, symmetric != 0, C, (hipStream_t)stream, "gemm_nt_f64", true);
 }

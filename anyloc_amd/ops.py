@@ -425,6 +425,32 @@ def pca_axes_f64(vec, k, x, mean64):
     return out
 
 
+def gemm_nt_f64(a, b, symmetric=False):
+    """a [M, K] @ b [N, K]^T in float64 on the double-precision matrix cores.  Both operands are read where they lie, WITH
+    their strides (a ``.t()`` view costs no copy); 16-byte loads serve an operand that is contiguous along either index,
+    16-byte aligned, with even extent and stride.  ``symmetric``: ``b`` is ``a`` -- the tiles on and above the diagonal are
+    computed and mirrored."""
+    _need_cuda(a, b)
+    if a.dtype != torch.float64 or b.dtype != torch.float64 or a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError(f"gemm_nt_f64 needs float64 [M, K] and [N, K], got {a.dtype} {tuple(a.shape)} and {b.dtype} {tuple(b.shape)}")
+    if symmetric and (a.data_ptr() != b.data_ptr() or a.shape != b.shape or a.stride() != b.stride()):
+        raise ValueError("gemm_nt_f64(symmetric=True) needs the same operand twice")
+    if min(a.stride()) < 1:                      # (expanded / size-1 views)
+        a = a.contiguous()
+        b = a if symmetric else b
+    if min(b.stride()) < 1:
+        b = b.contiguous()
+    (M, K), N = a.shape, b.shape[0]
+    out = torch.empty(M, N, dtype=torch.float64, device=a.device)
+    if out.numel() == 0:
+        return out
+    if K == 0:
+        return out.zero_()
+    _lib.check(_lib.load().anyloc_gemm_nt_f64(_lib.ptr(a), a.stride(0), a.stride(1), _lib.ptr(b), b.stride(0), b.stride(1), M, N, K,
+                                              int(bool(symmetric)), _lib.ptr(out), _lib.stream_ptr()), "anyloc_gemm_nt_f64")
+    return out
+
+
 def kmeans_step(x, centers, mode="cosine", want_labels=False):
     """One assign + accumulate pass: returns (sums [K,D], counts [K], labels|None)."""
     _need_cuda(x, centers)

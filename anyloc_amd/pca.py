@@ -10,8 +10,9 @@ run on the fp32 MFMA GEMM of the library (``anyloc_gemm_nt``):
 * fit:  centre on the device; the smaller of the Gram matrix  Xc Xc^T [n, n]  and the scatter matrix
   Xc^T Xc [f, f]  is one GEMM (in float64 on the double-precision matrix cores by default -- ``anyloc_pca_gram_f64``,
   csrc/pca_f64.hip -- see ``precise``); its symmetric eigendecomposition (float64, ``torch.linalg.eigh`` -- a
-  dense-solver library call, the one step of the fit that is not a kernel of this package) gives the singular values
-  and one side of the SVD; for the Gram side the principal axes follow from one more GEMM,
+  dense-solver library call, the one step of the fit that is not a kernel of this package; ``solver="subspace"`` takes
+  only the leading pairs instead, by subspace iteration on the same float64 kernel, ``anyloc_amd/eigs.py``) gives the
+  singular values and one side of the SVD; for the Gram side the principal axes follow from one more GEMM,
   V^T = diag(1/s) U^T Xc (``anyloc_pca_axes_f64``).
   Signs follow sklearn's ``svd_flip``: by default the rule of the sklearn installed next to this package (what the
   reference's own call would produce here): u-based (largest-magnitude entry of every U column positive) for the
@@ -25,7 +26,7 @@ as device tensors.
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, eigs, ops
 
 
 def _gemm(a, w, bias=None):
@@ -49,8 +50,14 @@ def default_sign_convention():
 
 
 class PCA:
-    def __init__(self, n_components: int, whiten: bool = False, precise: bool = True, sign_convention: str = "auto"):
-        """``sign_convention``: which factor of the SVD fixes the sign of every axis -- "u": the largest-magnitude entry
+    def __init__(self, n_components: int, whiten: bool = False, precise: bool = True, sign_convention: str = "auto",
+                 solver: str = "full", tol: float = 1e-11):
+        """``solver``: "full" (default) decomposes the whole Gram / scatter matrix with ``torch.linalg.eigh``; "subspace"
+        computes only the leading ``n_components`` eigenpairs with ``eigs.sym_topk`` (residuals below ``tol`` x the largest
+        eigenvalue) and falls back to the full decomposition when the shape is not eligible or the iteration breaks down.
+        ``solver_used_`` and ``n_iter_`` (0 for the full solver) say what a fit did.
+
+        ``sign_convention``: which factor of the SVD fixes the sign of every axis -- "u": the largest-magnitude entry
         of each column of U is positive, the ``svd_flip`` of sklearn < 1.5 incl. the 0.24.2 / 1.0.2 the reference pins
         (``setup_conda.sh:234``); "v": the largest-magnitude entry of each principal axis is positive, sklearn >= 1.5
         (``svd_flip(u, vt, u_based_decision=False)``); "auto" (default): what the reference's own
@@ -62,7 +69,10 @@ class PCA:
             sign_convention = default_sign_convention()
         if sign_convention not in ("v", "u"):
             raise ValueError("sign_convention must be 'auto', 'v' or 'u'")
+        if solver not in ("full", "subspace"):
+            raise ValueError("solver must be 'full' or 'subspace'")
         self.sign_convention = sign_convention
+        self.solver, self.tol = solver, float(tol)
         self.n_components = int(n_components)
         self.whiten = bool(whiten)
         # The Gram / scatter matrix squares the condition number: formed with fp32 sums, the axes whose variance is
@@ -95,7 +105,7 @@ class PCA:
         xc = None if self.precise else X - self.mean_
         if n <= f:
             gram = ops.pca_gram_f64(X, mean64, 0) if self.precise else _gemm(xc, xc)         # [n, n] = Xc Xc^T
-            lam, vec = self._eigh_desc(gram)
+            lam, vec, trace = self._decompose(gram, k)
             s = lam.clamp_min(0).sqrt()
             if self.precise:
                 axes = ops.pca_axes_f64(vec, k, X, mean64) / s[:k].clamp_min(1e-300)[:, None]  # [k, f] = U^T Xc / s
@@ -110,7 +120,7 @@ class PCA:
             else:
                 xt = xc.t().contiguous()
                 scatter = _gemm(xt, xt)
-            lam, vec = self._eigh_desc(scatter)
+            lam, vec, trace = self._decompose(scatter, k)
             s = lam.clamp_min(0).sqrt()
             axes = vec[:, :k].t().to(torch.float32).contiguous()
         # axes of (numerically) zero variance -- rank-deficient data, e.g. n_components == n_samples after centring -- carry
@@ -160,11 +170,25 @@ class PCA:
         self._dead = dead
         self.singular_values_ = s[:k].to(torch.float32)
         self.explained_variance_ = (lam[:k].clamp_min(0) / max(n - 1, 1)).to(torch.float32)
-        total = float(lam.clamp_min(0).sum() / max(n - 1, 1))
+        # (the subspace solver holds k eigenvalues only: the total variance is the trace of the symmetric matrix)
+        total = float((lam.clamp_min(0).sum() if trace is None else trace) / max(n - 1, 1))
         self.explained_variance_ratio_ = self.explained_variance_ / total if total > 0 else self.explained_variance_
         self.n_components_, self.n_samples_, self.n_features_in_ = k, n, f
         self._w = None
         return self
+
+    def _decompose(self, sym, k):
+        """-> (eigenvalues descending, eigenvectors as columns, trace or None): all m pairs from the full solver, the leading
+        k from the subspace solver (then with the trace, which the discarded eigenvalues no longer sum to)."""
+        self.solver_used_, self.n_iter_ = "full", 0
+        if self.solver == "subspace" and eigs.eligible(sym.shape[0], k):
+            sym = sym.to(torch.float64)
+            got = eigs.sym_topk(sym, k, tol=self.tol)
+            if got is not None:
+                lam, vec_t, self.n_iter_ = got
+                self.solver_used_ = "subspace"
+                return lam, vec_t.t(), sym.diagonal().sum()
+        return self._eigh_desc(sym) + (None,)
 
     @staticmethod
     def _eigh_desc(sym):
@@ -229,13 +253,14 @@ def joint_pca_project(db_descs, qu_descs, lower_dim: int = 512, whiten: bool = F
 def reduce_pca(train_descs, test_descs, lower_dim: int, low_factor: float = 0.0, fallback: int = 256,
                svd_solver: str = "full", whitening: bool = False):
     """Device version of reference ``utilities.py:522-586`` (same arguments and return convention: numpy in ->
-    numpy out; tensors in -> tensors on the input's device).  ``svd_solver`` is accepted for signature
-    compatibility: the decomposition is always the exact (full) one."""
+    numpy out; tensors in -> tensors on the input's device).  ``svd_solver="arpack"`` (sklearn's truncated solver) selects
+    ``PCA(solver="subspace")`` where only the leading components are used (``low_factor == 0``); every other value, and the
+    ``low_factor > 0`` branch, which needs every component, runs the exact (full) decomposition."""
     assert 0 <= low_factor <= 1
     as_np = isinstance(train_descs, np.ndarray)
     tr, ts = torch.as_tensor(train_descs), torch.as_tensor(test_descs)
     if low_factor == 0.0:
-        pca = PCA(lower_dim, whiten=whitening)
+        pca = PCA(lower_dim, whiten=whitening, solver="subspace" if svd_solver == "arpack" else "full")
         out_tr, out_ts = pca.fit_transform(tr), pca.transform(ts)
     else:
         n_samples, n_components = tr.shape

@@ -255,6 +255,17 @@ int anyloc_pca_axes_f64(const double* vec, int64_t sample_stride, int64_t axis_s
                         const float* X, int64_t n, int64_t f, const double* mean, double* out,
                         void* stream);
 
+/* C[i*N + j] = sum_c A[i*a_rs + c*a_cs] * B[j*b_rs + c*b_cs], float64, on v_mfma_f64_16x16x4_f64.
+ * symmetric != 0: A and B are the same operand; tiles on and above the diagonal, mirrored.
+ * An operand that is contiguous along c (cs == 1) or along its row index (rs == 1), 16-byte aligned, with an even
+ * extent along that index and an even other stride, is fetched two doubles at a time; any other positive strides are
+ * served one element at a time.  Stream-ordered, no workspace, no synchronisation.  Added within ABI 10.
+ * replaces: the products inside sklearn PCA's decomposition, utilities.py:561-564 */
+int anyloc_gemm_nt_f64(const double* A, int64_t a_rs, int64_t a_cs,
+                       const double* B, int64_t b_rs, int64_t b_cs,
+                       int64_t M, int64_t N, int64_t K, int symmetric,
+                       double* C, void* stream);
+
 /* ------------------------------------------------------------- matmul ----
  * C[M,N] = A[M,K] * W[N,K]^T (+ bias[N] when bias != NULL): the exact-fp32 MFMA GEMM
  * (v_mfma_f32_32x32x2_f32) behind retrieval, the VLAD / k-means scores, the patch
