@@ -26,6 +26,38 @@ constexpr int HD = 64;        // head dim
 constexpr int KT = 32;        // keys per tile
 constexpr int KLD = HD + 4;   // padded K row (ds_read_b128 conflict-free)
 
+// Address, in plane 0 of the P-plane operand image img of R rows (x3 layout of gemm_x6.hip, h2 layout of gemm_h3.hip: [k/16][plane]
+// [row][32 B], the 16-byte halves of a row swapped when (row >> 3) & 1), of the four consecutive columns k0 .. k0 + 3 of a row:
+// 8 bytes in each plane, the planes R * 32 bytes apart.  (The two OUT3 stores below keep their own copy of it with P = 3: with
+// this function their kernels compile to other instructions.)
+template <int P>
+__device__ __forceinline__ unsigned char* plane_image_ptr(unsigned char* img, int k0, int64_t row, int64_t R) {
+  const int e = k0 & 15;
+  return img + (((int64_t)(k0 >> 4) * P) * R + row) * 32 + (((e >> 3) ^ (int)((row >> 3) & 1)) << 4) + (e & 7) * 2;
+}
+
+// ---- the parts attention_kernel and attention_x6_kernel share (arguments by value: by reference the kernels compile to other
+// instructions, as they do with the ragged prologue and the normalise-and-store epilogue in functions, which stay copies) ----
+// K and V rows of a key tile into registers: descriptor = this image's QKV rows (keys past T read as zeros), so = the tile's offset
+template <int NLD>
+__device__ __forceinline__ void kv_fetch(const __amdgpu_buffer_rsrc_t kv_rsrc, const unsigned (&kv_off)[NLD], unsigned k_col,
+                                         unsigned v_col, unsigned so, f32x4 (&rk)[NLD], f32x4 (&rv)[NLD]) {
+#pragma unroll
+  for (int i = 0; i < NLD; ++i) {
+    rk[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(kv_rsrc, kv_off[i] + k_col, so, 0));
+    rv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(kv_rsrc, kv_off[i] + v_col, so, 0));
+  }
+}
+// lane (ql, h2) holds the scores of keys kbase + (r & 3) + 8 * (r >> 2): a tile that reaches past the last key T - 1 is masked
+__device__ __forceinline__ f32x16 mask_tail(f32x16 sacc, int kbase, int T) {
+  if (kbase + 28 + 3 >= T) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if (kbase + (r & 3) + 8 * (r >> 2) >= T) sacc[r] = -INFINITY;
+  }
+  return sacc;
+}
+
 // WB = waves (32-query tiles) per workgroup; FASTEXP = v_exp_f32-based exponential
 // PRELOAD: read the whole K fragment set and the whole V column set of a tile into registers before
 //          the MFMA chains that consume them (2 waves/SIMD instead of 3, but no LDS wait inside a chain)
@@ -82,14 +114,7 @@ __global__ __launch_bounds__(64 * WB, PRELOAD ? 2 : 1) void attention_kernel(con
   for (int i = 0; i < NLD; ++i) kv_off[i] = (unsigned)(((int64_t)(sr + RPP * i) * ld + h * HD + 4 * sc) * 4);
   const unsigned k_col = (unsigned)D * 4, v_col = (unsigned)D * 8, tile_bytes = (unsigned)(KT * ld * 4);
   f32x4 rk[NLD], rv[NLD];
-  auto fetch = [&](int kt) {
-    const unsigned so = (unsigned)kt * tile_bytes;
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      rk[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(kv_rsrc, kv_off[i] + k_col, so, 0));
-      rv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(kv_rsrc, kv_off[i] + v_col, so, 0));
-    }
-  };
+  auto fetch = [&](int kt) { kv_fetch(kv_rsrc, kv_off, k_col, v_col, (unsigned)kt * tile_bytes, rk, rv); };
   auto stash = [&](int buf) {
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
@@ -143,11 +168,7 @@ __global__ __launch_bounds__(64 * WB, PRELOAD ? 2 : 1) void attention_kernel(con
       }
       // lane (ql, h2) now holds S[q = q0+ql][key = kt*32 + (r&3) + 8*(r>>2) + 4*h2]
       const int kbase = kt * KT + 4 * h2;
-      if (kbase + 28 + 3 >= T) {   // tile reaches past the last key: mask
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kbase + (r & 3) + 8 * (r >> 2) >= T) sacc[r] = -INFINITY;
-      }
+      sacc = mask_tail(sacc, kbase, T);
       float mloc = sacc[0];
 #pragma unroll
       for (int r = 1; r < 16; ++r) mloc = fmaxf(mloc, sacc[r]);
@@ -288,14 +309,7 @@ __global__ __launch_bounds__(256, 2) void attention_x6_kernel(const float* __res
   for (int i = 0; i < 2; ++i) kv_off[i] = (unsigned)(((int64_t)(sr + 16 * i) * ld + h * HD + 4 * sc) * 4);
   const unsigned k_col = (unsigned)D * 4, v_col = (unsigned)D * 8, tile_bytes = (unsigned)(KT * ld * 4);
   f32x4 rk[2], rv[2];
-  auto fetch = [&](int kt) {
-    const unsigned so = (unsigned)kt * tile_bytes;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      rk[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(kv_rsrc, kv_off[i] + k_col, so, 0));
-      rv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(kv_rsrc, kv_off[i] + v_col, so, 0));
-    }
-  };
+  auto fetch = [&](int kt) { kv_fetch(kv_rsrc, kv_off, k_col, v_col, (unsigned)kt * tile_bytes, rk, rv); };
   auto stash = [&](int buf) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -367,11 +381,7 @@ __global__ __launch_bounds__(256, 2) void attention_x6_kernel(const float* __res
       const int kbase = kt * KT + 4 * h2;
 #pragma unroll
       for (int r = 0; r < 16; ++r) sacc[r] *= scale;                 // power of two: exact
-      if (kbase + 28 + 3 >= T) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kbase + (r & 3) + 8 * (r >> 2) >= T) sacc[r] = -INFINITY;
-      }
+      sacc = mask_tail(sacc, kbase, T);
       float mloc = sacc[0];
 #pragma unroll
       for (int r = 1; r < 16; ++r) mloc = fmaxf(mloc, sacc[r]);
@@ -772,8 +782,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_h3_kernel(const unsigned
       for (int db = 0; db < 2; ++db)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          const int k0 = h * HD + db * 32 + 8 * g + 4 * h2, e = k0 & 15;
-          unsigned char* dst = out2 + (((int64_t)(k0 >> 4) * 2) * R + row) * 32 + (((e >> 3) ^ (int)((row >> 3) & 1)) << 4) + (e & 7) * 2;
+          unsigned char* dst = plane_image_ptr<2>(out2, h * HD + db * 32 + 8 * g + 4 * h2, row, R);
           uint2 ph, plo;
           ah_pack2(oacc[qg][db][4 * g + 0] * f, oacc[qg][db][4 * g + 1] * f, ph.x, plo.x);
           ah_pack2(oacc[qg][db][4 * g + 2] * f, oacc[qg][db][4 * g + 3] * f, ph.y, plo.y);
@@ -833,27 +842,40 @@ __global__ __launch_bounds__(256) void qkv_planes_kernel(const float* __restrict
   }
 }
 
-}  // namespace
+// ============================================================== host side ==============================================================
+// Every launch decision is taken by one of the two plan functions below, before the first HIP call; every kernel template has
+// one launch site.
 
-int qkv_planes_from_f32(const float* qkv, int64_t rows, int D, int heads, unsigned char* planes, float* inv, hipStream_t stream) {
-  ANYLOC_CHECK_ARG(qkv && planes && inv && rows > 0 && D == heads * HD, "qkv_planes: bad arguments");
-  const int64_t G = (rows + 31) / 32;
-  ANYLOC_CHECK_ARG(G < (1ll << 31), "qkv_planes: too many rows");
-  hipLaunchKernelGGL(qkv_planes_kernel, dim3((unsigned)G, heads, 3), dim3(256), 0, stream, qkv, rows, D, heads, G, planes, inv);
-  return launch_status("qkv_planes_kernel");
-}
+// ---- the two-term fp16 kernel ----
+// How one attention_h3 call runs.  attn_plan is the only reader of the options attn_h3_ks, attn_h3_qg and attn_h3_ragged_xcd.
+// Precedence of the options, as it always was: the key split wins over the query-group shape -- attn_h3_ks = 2, or the rule at
+// attn_h3_ks = 0, picks (QG, NW, KS) = (1, 4, 2) whatever attn_h3_qg says; attn_h3_qg = 2 picks (2, 2, 1) only for an unsplit
+// UNIFORM call -- ragged calls have no 64-query shape and ignore it; everything else runs (1, 4, 1).
+struct AttnPlan {
+  int QG, NW, KS;        // 32-query groups per wave, waves per workgroup, key splits (attention_h3_kernel)
+  int ragged;            // 0 = uniform, 1 = ragged in the uniform order (contiguous units per XCD), 2 = ragged, units dealt over the XCDs
+  int QB;                // workgroups per (image, head) unit: each covers QG * NW / KS of the longest image's 32-query groups
+  int64_t units, slots;  // (image, head) units; the grid's unit slots (ragged = 2: padded to whole rounds of 8)
+  unsigned grid;         // QB * slots, 1-D
+  size_t lds;            // 2 x KS stages + the block reduction
+  int64_t G;             // 32-row groups of the operand tiles
+  int t_or_n_img;        // the kernel's T argument: the images' length, but ragged = 2 -- which reads every length from tok_off --
+                         // takes the NUMBER OF IMAGES there, to tell the padding slots from units
+  const char* what;      // for launch_status
+};
 
-int attention_h3(const unsigned char* planes, const float* inv, int64_t batch, int T, int D, int heads, unsigned char* out2,
-                 float* out_inv, hipStream_t stream) {
-  ANYLOC_CHECK_ARG(planes && inv && out2 && out_inv, "attention_h3: null pointer");
-  ANYLOC_CHECK_ARG(D == heads * HD, "attention_h3: head_dim must be 64 (D=%d heads=%d)", D, heads);
-  ANYLOC_CHECK_ARG(T > 0 && batch > 0 && batch < 65536, "attention_h3: bad T/batch");
-  const int64_t R = batch * T, G = (R + 31) / 32;
-  ANYLOC_CHECK_ARG((int64_t)heads * G * 8192 < (1ll << 31), "attention_h3: operand tiles exceed the 2 GiB buffer-addressing range");
-  const double flops = 4.0 * (double)batch * heads * (double)T * T * HD;
-  ProfScope prof("attention", stream, flops, 8.0 * batch * T * D * 2);
-  const int qgroups = (T + 31) / 32 + 1;                    // an image intersects at most this many 32-row groups
-  const size_t lds = 2 * AH_STAGE + 64;
+int attn_plan(int64_t n_img, int max_T, int64_t rows, int heads, bool ragged, AttnPlan* plan) {
+  AttnPlan& p = *plan;
+  p.G = (rows + 31) / 32;
+  ANYLOC_CHECK_ARG((int64_t)heads * p.G * 8192 < (1ll << 31), "attention_h3: operand tiles exceed the 2 GiB buffer-addressing range");
+  // the grid of a ragged call is that of a uniform call of n_img images of the longest length (same workgroup shapes, same KS
+  // rule); the workgroups of a shorter image past its last query group exit at once.  Option attn_h3_ragged_xcd (1, default): the
+  // (image, head) units dealt round-robin over the XCDs, grid padded to whole rounds of 8 units; 0: the uniform order
+  p.ragged = !ragged ? 0 : option(OPT_ATTN_H3_RAGGED_XCD) != 0 ? 2 : 1;
+  p.units = (int64_t)heads * n_img;
+  p.slots = p.ragged == 2 ? (p.units + 7) / 8 * 8 : p.units;
+  p.t_or_n_img = p.ragged == 2 ? (int)n_img : max_T;
+  const int qgroups = (max_T + 31) / 32 + 1;                // an image intersects at most this many 32-row groups
   // four waves of 32 queries per workgroup.  Measured: two waves of 64 queries (13.9 against 13.1 ms per step at B = 61,
   // 34 against 25 us per launch at B = 1: kept as option attn_h3_qg = 2, profiles/r05_attention_qg2.log); measured and
   // removed: a software-pipelined loop with a 3-stage ring (15.0 ms), and (round 3) all K fragments of a tile read first with
@@ -864,124 +886,139 @@ int attention_h3(const unsigned char* planes, const float* inv, int64_t batch, i
   // chain of key tiles per wave -- as long as all of them are resident at once (two per CU: 64 KiB of LDS each);
   // option attn_h3_ks: 0 = this rule, 1 / 2 force.  One ViT-g image (322 x 322): 27.7 -> 20.8 us per launch, two images 31.8 -> 26.3;
   // three and more (648+ workgroups) lose 3 - 12 us, as does the same split with 64-query waves (profiles/r05_attention_ks.log)
-  const int QB2 = (qgroups + 1) / 2;
   const int64_t ks_opt = option(OPT_ATTN_H3_KS);
-  if (ks_opt == 2 || (ks_opt == 0 && (int64_t)QB2 * heads * batch <= 512)) {
-    const dim3 grid2((unsigned)((int64_t)QB2 * heads * batch));
-    const size_t lds2 = 4 * AH_STAGE + 64;
-    static DynLds dyn_lds_once;                          // (per device: a process may drive several GPUs)
-    ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(attention_h3_kernel<1, 4, 2>), (int)lds2));
-    hipLaunchKernelGGL((attention_h3_kernel<1, 4, 2>), grid2, dim3(256), lds2, stream, planes, inv, T, heads, G, out2, out_inv, R, QB2, nullptr);
-    return launch_status("attention_h3_kernel<1,4,2>");
+  if (ks_opt == 2 || (ks_opt == 0 && (int64_t)((qgroups + 1) / 2) * p.units <= 512)) {
+    p.QG = 1; p.NW = 4; p.KS = 2;
+    p.what = p.ragged ? "attention_h3_kernel<1,4,2,ragged>" : "attention_h3_kernel<1,4,2>";
+  } else if (!p.ragged && option(OPT_ATTN_H3_QG) == 2) {
+    // (A/B) two waves of 64 queries per workgroup -- a wave's K / V fragments serve 64 queries (half the LDS reads, DMA issues
+    // and barriers per unit of work) at one wave per SIMD and workgroup
+    p.QG = 2; p.NW = 2; p.KS = 1;
+    p.what = "attention_h3_kernel<2,2>";
+  } else {
+    p.QG = 1; p.NW = 4; p.KS = 1;
+    p.what = p.ragged ? "attention_h3_kernel<ragged>" : "attention_h3_kernel";
   }
-  const int QB = (qgroups + 3) / 4;                         // workgroups (of four 32-query groups) per image and head
-  ANYLOC_CHECK_ARG((int64_t)QB * heads * batch < (1ll << 31), "attention_h3: grid too large");
-  const dim3 grid((unsigned)((int64_t)QB * heads * batch));
-  // option attn_h3_qg = 2 (A/B): two waves of 64 queries per workgroup -- a wave's K / V fragments serve 64 queries (half the
-  // LDS reads, DMA issues and barriers per unit of work) at one wave per SIMD and workgroup
-  if (option(OPT_ATTN_H3_QG) == 2) {
-    hipLaunchKernelGGL((attention_h3_kernel<2, 2>), grid, dim3(128), lds, stream, planes, inv, T, heads, G, out2, out_inv, R, QB, nullptr);
-    return launch_status("attention_h3_kernel<2,2>");
-  }
-  hipLaunchKernelGGL((attention_h3_kernel<1, 4>), grid, dim3(256), lds, stream, planes, inv, T, heads, G, out2, out_inv, R, QB, nullptr);
-  return launch_status("attention_h3_kernel");
+  const int per_wg = p.QG * p.NW / p.KS;                    // 32-query groups per workgroup: 2 with the key split, 4 without
+  p.QB = (qgroups + per_wg - 1) / per_wg;
+  ANYLOC_CHECK_ARG((int64_t)p.QB * p.slots < (1ll << 31), "attention_h3: grid too large");
+  p.grid = (unsigned)((int64_t)p.QB * p.slots);
+  p.lds = (size_t)2 * p.KS * AH_STAGE + 64;
+  return ANYLOC_OK;
 }
 
-// qkv [B*T, 3D] (q | k | v, each head-major 64-wide), out [B*T, D]
-int attention(const float* qkv, float* out, int64_t batch, int T, int D, int heads, hipStream_t stream,
-              unsigned char* out3, bool x6) {
-  ANYLOC_CHECK_ARG(D == heads * HD, "attention: head_dim must be 64 (D=%d heads=%d)", D, heads);
-  ANYLOC_CHECK_ARG(T > 0 && batch > 0 && batch < 65536, "attention: bad T/batch");
-  const double flops = 4.0 * (double)batch * heads * (double)T * T * HD;
-  ProfScope prof("attention", stream, flops, 16.0 * batch * T * D);
-  // option attn_cfg (micro-benchmarks): 0 = default (fast exp + operand preload), 1 = neither, 2 = fast exp, 3 = preload
-  const int cfg = (int)option(OPT_ATTN_CFG);
-  const dim3 g4((T + 127) / 128, heads, (unsigned)batch), g2((T + 63) / 64, heads, (unsigned)batch);
-  (void)g2;
-  const int64_t R3 = batch * T;
-  // option attn_x6: 1 = split-bf16 kernel for every call (kernel tests), 0 = never, -1 (default) = when the caller asks
-  if (option(OPT_ATTN_X6) >= 0) x6 = option(OPT_ATTN_X6) != 0;
-  if (x6) {
-    if (out3) hipLaunchKernelGGL((attention_x6_kernel<true>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3, nullptr);
-    else hipLaunchKernelGGL((attention_x6_kernel<false>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3, nullptr);
-    return launch_status("attention_x6_kernel");
+struct AttnH3Args {
+  const unsigned char* planes; const float* inv; int heads; unsigned char* out2; float* out_inv; int64_t rows; const int64_t* tok_off;
+};
+
+// the launch site of attention_h3_kernel.  The key-split shapes hold more than 64 KiB of LDS: each of their instantiations has
+// its own DynLds (per device: a process may drive several GPUs)
+template <int QG, int NW, int KS, int RAGGED>
+int launch_h3(const AttnPlan& p, const AttnH3Args& a, hipStream_t stream) {
+  if constexpr (KS == 2) {
+    static DynLds dyn_lds;
+    ANYLOC_TRY(ensure_dyn_lds(dyn_lds, reinterpret_cast<const void*>(attention_h3_kernel<QG, NW, KS, RAGGED>), (int)p.lds));
   }
-  if (out3) {
-    hipLaunchKernelGGL((attention_kernel<4, true, true, true>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3, nullptr);
-    return launch_status("attention_kernel");
-  }
-  switch (cfg) {
-    case 1: hipLaunchKernelGGL((attention_kernel<4, false, false>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3, nullptr); break;
-    case 2: hipLaunchKernelGGL((attention_kernel<4, true, false>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3, nullptr); break;
-    case 3: hipLaunchKernelGGL((attention_kernel<4, false, true>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3, nullptr); break;
-    default: hipLaunchKernelGGL((attention_kernel<4, true, true>), g4, dim3(256), 0, stream, qkv, out, T, D, 0.125f, out3, R3, nullptr); break;
-  }
-  return launch_status("attention_kernel");
+  hipLaunchKernelGGL((attention_h3_kernel<QG, NW, KS, RAGGED>), dim3(p.grid), dim3(64 * NW), p.lds, stream, a.planes, a.inv,
+                     p.t_or_n_img, a.heads, p.G, a.out2, a.out_inv, a.rows, p.QB, a.tok_off);
+  return launch_status(p.what);
 }
 
-int attention_h3_ragged(const unsigned char* planes, const float* inv, int n_img, int max_T, const int64_t* tok_off, int64_t rows,
-                        int D, int heads, unsigned char* out2, float* out_inv, hipStream_t stream) {
-  ANYLOC_CHECK_ARG(planes && inv && out2 && out_inv && tok_off, "attention_h3: null pointer");
-  ANYLOC_CHECK_ARG(D == heads * HD, "attention_h3: head_dim must be 64 (D=%d heads=%d)", D, heads);
-  ANYLOC_CHECK_ARG(max_T > 0 && n_img > 0 && n_img < 65536 && rows >= max_T, "attention_h3: bad T/batch");
+// ---- the fp32-MFMA and the split-bf16 kernel ----
+// attn_f32_plan is the only reader of the options attn_x6 and attn_cfg.  attn_x6: 1 = split-bf16 kernel for every call (kernel
+// tests), 0 = never, -1 (default) = when the caller asks.  attn_cfg (micro-benchmarks) shapes the fp32-MFMA kernel of a uniform
+// call with fp32 output: 0 = default (fast exp + operand preload), 1 = neither, 2 = fast exp, 3 = preload; a call that writes the
+// plane image and every RAGGED call always take fast exp + preload, whatever attn_cfg says.
+struct AttnF32Plan {
+  bool x6, fastexp, preload, out3, ragged;
+  dim3 grid;             // (128-query blocks of the longest image, heads, images)
+  const char* what;
+};
+
+AttnF32Plan attn_f32_plan(int64_t n_img, int max_T, int heads, bool ragged, bool out3, bool x6_asked) {
+  AttnF32Plan p;
+  p.x6 = option(OPT_ATTN_X6) >= 0 ? option(OPT_ATTN_X6) != 0 : x6_asked;
+  const int cfg = out3 || ragged ? 0 : (int)option(OPT_ATTN_CFG);
+  p.fastexp = cfg != 1 && cfg != 3;
+  p.preload = cfg != 1 && cfg != 2;
+  p.out3 = out3;
+  p.ragged = ragged;
+  p.grid = dim3((max_T + 127) / 128, heads, (unsigned)n_img);
+  p.what = p.x6 ? (ragged ? "attention_x6_kernel<ragged>" : "attention_x6_kernel")
+                : (ragged ? "attention_kernel<ragged>" : "attention_kernel");
+  return p;
+}
+
+struct AttnF32Args {
+  const float* qkv; float* out; int max_T, D; unsigned char* out3; int64_t rows; const int64_t* tok_off;
+};
+
+template <bool FASTEXP, bool PRELOAD, bool OUT3, bool RAGGED>
+int launch_f32(const AttnF32Plan& p, const AttnF32Args& a, hipStream_t stream) {
+  hipLaunchKernelGGL((attention_kernel<4, FASTEXP, PRELOAD, OUT3, RAGGED>), p.grid, dim3(256), 0, stream, a.qkv, a.out, a.max_T, a.D,
+                     0.125f, a.out3, a.rows, a.tok_off);
+  return launch_status(p.what);
+}
+
+template <bool OUT3, bool RAGGED>
+int launch_x6(const AttnF32Plan& p, const AttnF32Args& a, hipStream_t stream) {
+  hipLaunchKernelGGL((attention_x6_kernel<OUT3, RAGGED>), p.grid, dim3(256), 0, stream, a.qkv, a.out, a.max_T, a.D, 0.125f, a.out3,
+                     a.rows, a.tok_off);
+  return launch_status(p.what);
+}
+
+}  // namespace
+
+int qkv_planes_from_f32(const float* qkv, int64_t rows, int D, int heads, unsigned char* planes, float* inv, hipStream_t stream) {
+  ANYLOC_CHECK_ARG(qkv && planes && inv && rows > 0 && D == heads * HD, "qkv_planes: bad arguments");
   const int64_t G = (rows + 31) / 32;
-  ANYLOC_CHECK_ARG((int64_t)heads * G * 8192 < (1ll << 31), "attention_h3: operand tiles exceed the 2 GiB buffer-addressing range");
-  ProfScope prof("attention", stream, 4.0 * heads * (double)rows * max_T * HD, 8.0 * rows * D * 2);
-  // the grid of the uniform launcher for n_img images of the longest length (same workgroup shapes, same KS rule); the
-  // workgroups of a shorter image past its last query group exit at once.  Option attn_h3_ragged_xcd (1, default): the
-  // (image, head) units dealt round-robin over the XCDs, grid padded to whole rounds of 8 units; 0: the uniform order
-  const int qgroups = (max_T + 31) / 32 + 1;
-  const int QB2 = (qgroups + 1) / 2;
-  const int64_t units = (int64_t)heads * n_img;
-  const bool deal = option(OPT_ATTN_H3_RAGGED_XCD) != 0;
-  const int64_t slots = deal ? (units + 7) / 8 * 8 : units;
-  const int targ = deal ? n_img : max_T;
-  const int64_t ks_opt = option(OPT_ATTN_H3_KS);
-  if (ks_opt == 2 || (ks_opt == 0 && (int64_t)QB2 * units <= 512)) {
-    const size_t lds2 = 4 * AH_STAGE + 64;
-    const dim3 grid2((unsigned)((int64_t)QB2 * slots));
-    if (deal) {
-      static DynLds dyn_lds_deal;
-      ANYLOC_TRY(ensure_dyn_lds(dyn_lds_deal, reinterpret_cast<const void*>(attention_h3_kernel<1, 4, 2, 2>), (int)lds2));
-      hipLaunchKernelGGL((attention_h3_kernel<1, 4, 2, 2>), grid2, dim3(256), lds2, stream, planes, inv, targ, heads, G, out2,
-                         out_inv, rows, QB2, tok_off);
-    } else {
-      static DynLds dyn_lds_once;
-      ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(attention_h3_kernel<1, 4, 2, 1>), (int)lds2));
-      hipLaunchKernelGGL((attention_h3_kernel<1, 4, 2, 1>), grid2, dim3(256), lds2, stream, planes, inv, targ, heads, G, out2,
-                         out_inv, rows, QB2, tok_off);
-    }
-    return launch_status("attention_h3_kernel<1,4,2,ragged>");
-  }
-  const int QB = (qgroups + 3) / 4;
-  ANYLOC_CHECK_ARG((int64_t)QB * slots < (1ll << 31), "attention_h3: grid too large");
-  const dim3 grid((unsigned)((int64_t)QB * slots));
-  if (deal)
-    hipLaunchKernelGGL((attention_h3_kernel<1, 4, 1, 2>), grid, dim3(256), 2 * AH_STAGE + 64, stream, planes, inv, targ, heads, G,
-                       out2, out_inv, rows, QB, tok_off);
-  else
-    hipLaunchKernelGGL((attention_h3_kernel<1, 4, 1, 1>), grid, dim3(256), 2 * AH_STAGE + 64, stream, planes, inv, targ, heads, G,
-                       out2, out_inv, rows, QB, tok_off);
-  return launch_status("attention_h3_kernel<ragged>");
+  ANYLOC_CHECK_ARG(G < (1ll << 31), "qkv_planes: too many rows");
+  hipLaunchKernelGGL(qkv_planes_kernel, dim3((unsigned)G, heads, 3), dim3(256), 0, stream, qkv, rows, D, heads, G, planes, inv);
+  return launch_status("qkv_planes_kernel");
 }
 
-int attention_ragged(const float* qkv, float* out, int n_img, int max_T, const int64_t* tok_off, int64_t rows, int D, int heads,
-                     hipStream_t stream, unsigned char* out3, bool x6) {
-  ANYLOC_CHECK_ARG(D == heads * HD, "attention: head_dim must be 64 (D=%d heads=%d)", D, heads);
-  ANYLOC_CHECK_ARG(qkv && tok_off && (out || out3) && max_T > 0 && n_img > 0 && n_img < 65536, "attention: bad T/batch");
-  ProfScope prof("attention", stream, 4.0 * heads * (double)rows * max_T * HD, 16.0 * rows * D);
-  const dim3 g4((max_T + 127) / 128, heads, (unsigned)n_img);
-  if (option(OPT_ATTN_X6) >= 0) x6 = option(OPT_ATTN_X6) != 0;
-  if (x6) {
-    if (out3) hipLaunchKernelGGL((attention_x6_kernel<true, true>), g4, dim3(256), 0, stream, qkv, out, max_T, D, 0.125f, out3, rows, tok_off);
-    else hipLaunchKernelGGL((attention_x6_kernel<false, true>), g4, dim3(256), 0, stream, qkv, out, max_T, D, 0.125f, out3, rows, tok_off);
-    return launch_status("attention_x6_kernel<ragged>");
+int attention_h3(const unsigned char* planes, const float* inv, int64_t n_img, int T, const int64_t* tok_off, int64_t rows, int D,
+                 int heads, unsigned char* out2, float* out_inv, hipStream_t stream) {
+  ANYLOC_CHECK_ARG(planes && inv && out2 && out_inv, "attention_h3: null pointer");
+  ANYLOC_CHECK_ARG(D == heads * HD, "attention_h3: head_dim must be 64 (D=%d heads=%d)", D, heads);
+  ANYLOC_CHECK_ARG(T > 0 && n_img > 0 && n_img < 65536 && (tok_off ? rows >= T : rows == n_img * T), "attention_h3: bad T/batch");
+  AttnPlan p;
+  ANYLOC_TRY(attn_plan(n_img, T, rows, heads, tok_off != nullptr, &p));
+  // (uniform: rows = n_img * T)
+  ProfScope prof("attention", stream, 4.0 * heads * (double)rows * T * HD, 8.0 * rows * D * 2);
+  const AttnH3Args a{planes, inv, heads, out2, out_inv, rows, tok_off};
+  switch (100 * p.ragged + 10 * p.QG + p.KS) {              // the seven instantiations
+    case 12: return launch_h3<1, 4, 2, 0>(p, a, stream);
+    case 21: return launch_h3<2, 2, 1, 0>(p, a, stream);
+    case 11: return launch_h3<1, 4, 1, 0>(p, a, stream);
+    case 112: return launch_h3<1, 4, 2, 1>(p, a, stream);
+    case 111: return launch_h3<1, 4, 1, 1>(p, a, stream);
+    case 212: return launch_h3<1, 4, 2, 2>(p, a, stream);
+    case 211: return launch_h3<1, 4, 1, 2>(p, a, stream);
   }
-  if (out3)
-    hipLaunchKernelGGL((attention_kernel<4, true, true, true, true>), g4, dim3(256), 0, stream, qkv, out, max_T, D, 0.125f, out3, rows, tok_off);
-  else
-    hipLaunchKernelGGL((attention_kernel<4, true, true, false, true>), g4, dim3(256), 0, stream, qkv, out, max_T, D, 0.125f, out3, rows, tok_off);
-  return launch_status("attention_kernel<ragged>");
+  set_error("attention_h3: no kernel for the plan (ragged %d, QG %d, KS %d)", p.ragged, p.QG, p.KS);
+  return ANYLOC_ERR_INVALID_ARG;
+}
+
+// qkv [rows, 3D] (q | k | v, each head-major 64-wide), out [rows, D]
+int attention(const float* qkv, float* out, int64_t n_img, int T, const int64_t* tok_off, int64_t rows, int D, int heads,
+              hipStream_t stream, unsigned char* out3, bool x6) {
+  ANYLOC_CHECK_ARG(D == heads * HD, "attention: head_dim must be 64 (D=%d heads=%d)", D, heads);
+  ANYLOC_CHECK_ARG(qkv && (out || out3) && T > 0 && n_img > 0 && n_img < 65536 && (tok_off || rows == n_img * T),
+                   "attention: bad T/batch");
+  const AttnF32Plan p = attn_f32_plan(n_img, T, heads, tok_off != nullptr, out3 != nullptr, x6);
+  // (uniform: rows = n_img * T)
+  ProfScope prof("attention", stream, 4.0 * heads * (double)rows * T * HD, 16.0 * rows * D);
+  const AttnF32Args a{qkv, out, T, D, out3, rows, tok_off};
+  if (p.x6) {
+    if (p.ragged) return p.out3 ? launch_x6<true, true>(p, a, stream) : launch_x6<false, true>(p, a, stream);
+    return p.out3 ? launch_x6<true, false>(p, a, stream) : launch_x6<false, false>(p, a, stream);
+  }
+  if (p.ragged) return p.out3 ? launch_f32<true, true, true, true>(p, a, stream) : launch_f32<true, true, false, true>(p, a, stream);
+  if (p.out3) return launch_f32<true, true, true, false>(p, a, stream);
+  if (p.fastexp)
+    return p.preload ? launch_f32<true, true, false, false>(p, a, stream) : launch_f32<true, false, false, false>(p, a, stream);
+  return p.preload ? launch_f32<false, true, false, false>(p, a, stream) : launch_f32<false, false, false, false>(p, a, stream);
 }
 
 }  // namespace anyloc

@@ -355,9 +355,11 @@ int split_h1_wide(const float* x, int64_t ldx, int64_t rows, int64_t K, void* h2
 // (Cauchy-Schwarz: |fc1 output| <= ||ln(x)||_2 * max_j ||W_j||_2 + max |b|), bound = {gate_norm, gate_bias, val_norm, val_bias}
 int layernorm_h2(const float* x, const float* w, const float* b, int64_t rows, int dim, float eps, void* h2,
                  float* inv_scale, hipStream_t stream, const float* bound = nullptr, float* bound_inv = nullptr);
-// attention on the tiles of EPI_QKV_PLANES; writes the h2 image (+ per-row 2^-e) the projection GEMM reads
-int attention_h3(const unsigned char* planes, const float* inv, int64_t batch, int T, int D, int heads,
-                 unsigned char* out2, float* out_inv, hipStream_t stream);
+// attention on the tiles of EPI_QKV_PLANES; writes the h2 image (+ per-row 2^-e) the projection GEMM reads.  tok_off == nullptr:
+// n_img images of T rows each (rows = n_img * T); otherwise images of different lengths, tok_off = device [n_img + 1] row offsets,
+// T the longest image, rows the total
+int attention_h3(const unsigned char* planes, const float* inv, int64_t n_img, int T, const int64_t* tok_off, int64_t rows, int D,
+                 int heads, unsigned char* out2, float* out_inv, hipStream_t stream);
 // test / fallback producer of the same tiles from an fp32 [rows, 3D] buffer
 int qkv_planes_from_f32(const float* qkv, int64_t rows, int D, int heads, unsigned char* planes, float* inv,
                         hipStream_t stream);
@@ -428,7 +430,8 @@ int cls_rows(float* x, const float* cls, const float* pos, int64_t batch, int T,
 int facet_rows(const float* src, int64_t lds_, int coff, float* out, int64_t ldo, int ooff,
                int64_t batch, int T, int skip, int gap, int rows_per_img, int dim, int normalize, float eps,
                hipStream_t stream);
-int attention(const float* qkv, float* out, int64_t batch, int T, int D, int heads,
+// fp32 / split-bf16 attention on qkv [rows, 3D]; n_img, T, tok_off, rows as attention_h3's
+int attention(const float* qkv, float* out, int64_t n_img, int T, const int64_t* tok_off, int64_t rows, int D, int heads,
               hipStream_t stream, unsigned char* out3 = nullptr,    // out3: write the result as a plane image instead
               bool x6 = false);                                      // x6: split-bf16 matrix products
 
@@ -450,11 +453,6 @@ int embed_rows(float* x, const float* patch, const float* cls, const float* reg,
 int rope_rows(float* qkv, int64_t rows, int heads, const RopeRows& rp, hipStream_t stream);
 int facet_rows_ragged(const float* src, int64_t lds_, int coff, float* out, int64_t ldo, int ooff, const int64_t* meta,
                       int n_img, int64_t out_rows, int skip, int gap, int dim, int normalize, float eps, hipStream_t stream);
-// attention over images of different lengths: tok_off = device [n_img + 1] row offsets, max_T the longest image
-int attention_ragged(const float* qkv, float* out, int n_img, int max_T, const int64_t* tok_off, int64_t rows, int D, int heads,
-                     hipStream_t stream, unsigned char* out3, bool x6);
-int attention_h3_ragged(const unsigned char* planes, const float* inv, int n_img, int max_T, const int64_t* tok_off, int64_t rows,
-                        int D, int heads, unsigned char* out2, float* out_inv, hipStream_t stream);
 // FFN-bound telemetry, one figure per (block, image) of a ragged batch
 int ffn_looseness_ragged(const unsigned* rowmax, int nblocks, int64_t M, const int64_t* tok_off, int n_img, float* out,
                          hipStream_t stream);

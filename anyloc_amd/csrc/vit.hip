@@ -233,7 +233,7 @@ int anyloc_layernorm(const float* x, float* y, const float* weight, const float*
 int anyloc_attention(const float* qkv, float* out, int64_t batch, int64_t tokens, int64_t dim, int64_t heads,
                      void* stream) {
   ANYLOC_CHECK_ARG(qkv && out, "attention: null pointer");
-  return attention(qkv, out, batch, (int)tokens, (int)dim, (int)heads, static_cast<hipStream_t>(stream));
+  return attention(qkv, out, batch, (int)tokens, nullptr, batch * tokens, (int)dim, (int)heads, static_cast<hipStream_t>(stream));
 }
 
 size_t anyloc_attention_h3_workspace_bytes(int64_t batch, int64_t tokens, int64_t heads) {
@@ -242,21 +242,29 @@ size_t anyloc_attention_h3_workspace_bytes(int64_t batch, int64_t tokens, int64_
   return align_up(qkv_planes_bytes(rows, (int)heads), 256) + align_up(qkv_inv_count(rows, (int)heads) * sizeof(float), 256) + 256;
 }
 
+// anyloc_attention_h3 and anyloc_attention_h3_ragged: the q | k | v tiles of fp32 qkv [rows, 3 * dim] in the caller's workspace
+static int h3_tiles_in_workspace(const char* who, const float* qkv, int64_t rows, int64_t dim, int64_t heads, void* workspace,
+                                 size_t workspace_bytes, hipStream_t stream, unsigned char** planes, float** inv) {
+  if (workspace_bytes < anyloc_attention_h3_workspace_bytes(1, rows, heads)) {
+    set_error("%s: workspace %zu < %zu", who, workspace_bytes, anyloc_attention_h3_workspace_bytes(1, rows, heads));
+    return ANYLOC_ERR_WORKSPACE;
+  }
+  Arena a(workspace, workspace_bytes);
+  *planes = a.take<unsigned char>(qkv_planes_bytes(rows, (int)heads));
+  *inv = a.take<float>(qkv_inv_count(rows, (int)heads));
+  return qkv_planes_from_f32(qkv, rows, (int)dim, (int)heads, *planes, *inv, stream);
+}
+
 int anyloc_attention_h3(const float* qkv, void* out_img, float* out_inv, int64_t batch, int64_t tokens, int64_t dim,
                         int64_t heads, void* workspace, size_t workspace_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   ANYLOC_CHECK_ARG(qkv && out_img && out_inv && workspace, "attention_h3: null pointer");
   ANYLOC_CHECK_ARG(batch > 0 && tokens > 0 && heads > 0 && dim == heads * 64, "attention_h3: bad shape");
-  if (workspace_bytes < anyloc_attention_h3_workspace_bytes(batch, tokens, heads)) {
-    set_error("attention_h3: workspace %zu < %zu", workspace_bytes, anyloc_attention_h3_workspace_bytes(batch, tokens, heads));
-    return ANYLOC_ERR_WORKSPACE;
-  }
-  Arena a(workspace, workspace_bytes);
-  const int64_t rows = batch * tokens;
-  unsigned char* planes = a.take<unsigned char>(qkv_planes_bytes(rows, (int)heads));
-  float* inv = a.take<float>(qkv_inv_count(rows, (int)heads));
-  ANYLOC_TRY(qkv_planes_from_f32(qkv, rows, (int)dim, (int)heads, planes, inv, stream));
-  return attention_h3(planes, inv, batch, (int)tokens, (int)dim, (int)heads, static_cast<unsigned char*>(out_img), out_inv, stream);
+  unsigned char* planes;
+  float* inv;
+  ANYLOC_TRY(h3_tiles_in_workspace("attention_h3", qkv, batch * tokens, dim, heads, workspace, workspace_bytes, stream, &planes, &inv));
+  return attention_h3(planes, inv, batch, (int)tokens, nullptr, batch * tokens, (int)dim, (int)heads,
+                      static_cast<unsigned char*>(out_img), out_inv, stream);
 }
 
 int anyloc_vit_create(anyloc_vit_t** out, const anyloc_vit_config* cfg, const float* patch_w, const float* patch_b,
@@ -582,10 +590,8 @@ static int vit_forward_launches(anyloc_vit_t* h, const float* img, int64_t batch
     // ---- a = softmax((q/8) k^T) v ----
     const unsigned char* tiles = reinterpret_cast<const unsigned char*>(w.qkv);
     unsigned char* a_img = fuse_attn ? w.a3 : nullptr;     // x6: the output as the plane image instead of fp32 rows in w.y
-    if (h3_attn && rg) ANYLOC_TRY(attention_h3_ragged(tiles, w.qinv, (int)batch, T, meta, M, D, c.heads, w.a3, w.ainv, stream));
-    else if (h3_attn) ANYLOC_TRY(attention_h3(tiles, w.qinv, batch, T, D, c.heads, w.a3, w.ainv, stream));
-    else if (rg) ANYLOC_TRY(attention_ragged(w.qkv, w.y, (int)batch, T, meta, M, D, c.heads, stream, a_img, x6 || h3));
-    else ANYLOC_TRY(attention(w.qkv, w.y, batch, T, D, c.heads, stream, a_img, x6 || h3));
+    if (h3_attn) ANYLOC_TRY(attention_h3(tiles, w.qinv, batch, T, meta, M, D, c.heads, w.a3, w.ainv, stream));
+    else ANYLOC_TRY(attention(w.qkv, w.y, batch, T, meta, M, D, c.heads, stream, a_img, x6 || h3));
     // ---- x += ls1 * (a Wproj^T + b)  (h3, unfused: a is fp32 -- its rows span all heads, the row maximum is only known now) ----
     const Act attn{w.y, w.a3, w.ainv, M, D, fuse_attn};
     BlockGemm proj = describe(arith, "vit_proj_gemm", attn, Wproj, 0, D, b.proj_b, w.x, D, h3_attn ? H3_KIND_PROJ : H3_KIND_OTHER, w);
@@ -708,8 +714,7 @@ int anyloc_attention_ragged(const float* qkv, float* out, int32_t n_img, const i
   int64_t rows = 0;
   int max_T = 0;
   ANYLOC_TRY(attention_ragged_shape(n_img, tokens, &rows, &max_T));
-  return attention_ragged(qkv, out, n_img, max_T, tok_off, rows, (int)dim, (int)heads, static_cast<hipStream_t>(stream), nullptr,
-                          false);
+  return attention(qkv, out, n_img, max_T, tok_off, rows, (int)dim, (int)heads, static_cast<hipStream_t>(stream));
 }
 
 int anyloc_attention_h3_ragged(const float* qkv, void* out_img, float* out_inv, int32_t n_img, const int32_t* tokens,
@@ -721,16 +726,11 @@ int anyloc_attention_h3_ragged(const float* qkv, void* out_img, float* out_inv, 
   int64_t rows = 0;
   int max_T = 0;
   ANYLOC_TRY(attention_ragged_shape(n_img, tokens, &rows, &max_T));
-  if (workspace_bytes < anyloc_attention_h3_workspace_bytes(1, rows, heads)) {
-    set_error("attention_h3_ragged: workspace %zu < %zu", workspace_bytes, anyloc_attention_h3_workspace_bytes(1, rows, heads));
-    return ANYLOC_ERR_WORKSPACE;
-  }
-  Arena a(workspace, workspace_bytes);
-  unsigned char* planes = a.take<unsigned char>(qkv_planes_bytes(rows, (int)heads));
-  float* inv = a.take<float>(qkv_inv_count(rows, (int)heads));
-  ANYLOC_TRY(qkv_planes_from_f32(qkv, rows, (int)dim, (int)heads, planes, inv, stream));
-  return attention_h3_ragged(planes, inv, n_img, max_T, tok_off, rows, (int)dim, (int)heads, static_cast<unsigned char*>(out_img),
-                             out_inv, stream);
+  unsigned char* planes;
+  float* inv;
+  ANYLOC_TRY(h3_tiles_in_workspace("attention_h3_ragged", qkv, rows, dim, heads, workspace, workspace_bytes, stream, &planes, &inv));
+  return attention_h3(planes, inv, n_img, max_T, tok_off, rows, (int)dim, (int)heads, static_cast<unsigned char*>(out_img), out_inv,
+                      stream);
 }
 
 }  // extern "C"

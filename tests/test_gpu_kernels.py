@@ -125,6 +125,77 @@ def test_attention_h3(dev, B, T, heads, qg, ks):
     assert bool((torch.log2(inv_c) == torch.log2(inv_c).round()).all())
 
 
+def _attention_h3_raw(qkv, heads, tokens=None):
+    """anyloc_attention_h3 on qkv [B, T, 3D], or (tokens = the images' lengths) anyloc_attention_h3_ragged on the packed
+    qkv [sum(tokens), 3D]  ->  (h2 image, out_inv) as the kernel left them, in zeroed buffers."""
+    import ctypes as C
+    from anyloc_amd import _lib
+    lib = _lib.load()
+    D = heads * 64
+    rows = qkv.numel() // (3 * D)
+    img = torch.zeros(lib.anyloc_h2_bytes(rows, D), dtype=torch.uint8, device=qkv.device)
+    inv = torch.zeros(rows, dtype=torch.float32, device=qkv.device)
+    ws = _lib.workspace(lib.anyloc_attention_h3_workspace_bytes(1, rows, heads), qkv.device, "attn_h3")
+    if tokens is None:
+        B, T = qkv.shape[:2]
+        _lib.check(lib.anyloc_attention_h3(_lib.ptr(qkv), _lib.ptr(img), _lib.ptr(inv), B, T, D, heads, _lib.ptr(ws), ws.numel(),
+                                           _lib.stream_ptr()), "anyloc_attention_h3")
+    else:
+        off = torch.zeros(len(tokens) + 1, dtype=torch.int64)
+        off[1:] = torch.cumsum(torch.tensor(tokens), 0)
+        off_d = off.to(qkv.device)
+        _lib.check(lib.anyloc_attention_h3_ragged(_lib.ptr(qkv), _lib.ptr(img), _lib.ptr(inv), len(tokens),
+                                                  (C.c_int32 * len(tokens))(*tokens), _lib.ptr(off_d), D, heads, _lib.ptr(ws),
+                                                  ws.numel(), _lib.stream_ptr()), "anyloc_attention_h3_ragged")
+    torch.cuda.synchronize()
+    return img, inv
+
+
+@pytest.mark.parametrize("ragged_xcd", [None, 0, 1], ids=["uniform", "ragged-xcd-ranges", "ragged-xcd-dealt"])
+@pytest.mark.parametrize("n_img,ks_rule", [(85, 2), (86, 1)])
+def test_attention_h3_automatic_key_split_at_its_boundary(dev, n_img, ks_rule, ragged_xcd):
+    """attn_h3_ks = 0 takes the two-key-wave workgroups (KS = 2) while QB2 * heads * images <= 512, QB2 the workgroups of
+    two 32-query groups that cover the (longest) image.  At T = 100 an image intersects at most (100 + 31) // 32 + 1 = 5
+    groups, QB2 = (5 + 1) // 2 = 3, and with 2 heads the count is 3 * 2 * n_img: 510 for 85 images (KS = 2), 516 for 86
+    (KS = 1).  The automatic choice must give the bits of the forced value the rule names -- and the two forced values
+    differ in bits (the key waves' partial sums meet in another order), so that tells which kernel ran.  Uniform batches and
+    ragged packs (lengths alternating 100 and 37: the longest image sets the grid), both ragged workgroup orders."""
+    from anyloc_amd import ops
+    heads, T = 2, 100
+    D = heads * 64
+    g = torch.Generator().manual_seed(n_img)
+    if ragged_xcd is None:
+        tokens = None
+        qkv = torch.randn(n_img, T, 3 * D, generator=g) * 1.5
+        qkv[:, ::7] *= 0.05                               # the spiky generator of test_attention_h3
+        qkv[0, 3, :D] *= 6.0
+        qkv[0, T - 2, D:2 * D] *= 6.0
+        qkv[:, 5, 2 * D:] *= 40.0
+    else:
+        tokens = [T if i % 2 == 0 else 37 for i in range(n_img)]
+        qkv = torch.randn(sum(tokens), 3 * D, generator=g) * 1.5
+        qkv[::7] *= 0.05
+        qkv[3, :D] *= 6.0
+        qkv[T - 2, D:2 * D] *= 6.0
+        qkv[5::137, 2 * D:] *= 40.0
+    assert 3 * heads * 85 <= 512 < 3 * heads * 86
+    names = ("attn_h3_ks", "attn_h3_qg", "attn_h3_ragged_xcd")
+    before = {k: ops.get_option(k) for k in names}
+    try:
+        ops.set_option("attn_h3_qg", 1)
+        if ragged_xcd is not None:
+            ops.set_option("attn_h3_ragged_xcd", ragged_xcd)
+        got = {}
+        for ks in (0, 1, 2):
+            ops.set_option("attn_h3_ks", ks)
+            got[ks] = _attention_h3_raw(qkv.to(dev), heads, tokens)
+    finally:
+        for k, v in before.items():
+            ops.set_option(k, v)
+    assert not torch.equal(got[1][0], got[2][0])          # the two shapes are told apart by their bits
+    assert torch.equal(got[0][0], got[ks_rule][0]) and torch.equal(got[0][1], got[ks_rule][1])
+
+
 @pytest.mark.parametrize("H,W", [(224, 224), (333, 481), (126, 155)])
 def test_preprocess_u8_matches_totensor_normalize_centercrop(dev, H, W):
     """uint8 HWC -> float CHW ingest == ToTensor + Normalize + CenterCrop(h//14*14, w//14*14), bit-exact."""
