@@ -36,6 +36,23 @@
  *     tests/test_stream_contract_cpu.py keeps blocking calls out of the sources.
  *   - scratch space is caller-provided: query the size with the matching
  *     *_workspace_bytes() and pass a buffer at least that large.
+ *   - Buffers.  A call writes only the documented extent of its outputs and the
+ *     first `workspace_bytes` bytes of the workspace: an output [M, N] with a
+ *     leading dimension (ldc) is written in columns [0, N) of its M rows, never in
+ *     the columns between N and ldc and never behind element (M - 1) * ldc + N - 1;
+ *     a plane image within its anyloc_x3_bytes / anyloc_h2_bytes / anyloc_topk_index_bytes
+ *     bytes (anyloc_split_x3 and anyloc_split_h2 write all of them, the zero padding
+ *     of the last k-block included).  A call
+ *     never writes its inputs (an operand documented as in place, or as allowed to
+ *     alias an output, is that output).  Any leading dimension >= the row length
+ *     is served where no multiple is asked for (anyloc_gemm_nt: lda and ldw multiples
+ *     of 4, anyloc_split_h2: ldx a multiple of 4; ldc and the ldx of anyloc_split_x3
+ *     may be odd).  The workspace must be 16-byte aligned: the library carves it in
+ *     256-byte steps from the pointer it is given, so every piece has the alignment
+ *     of that pointer, and the kernels access it 16 bytes at a time; the sizes the
+ *     *_workspace_bytes() functions answer hold for any such pointer.
+ *     tests/test_gpu_guard_bands.py holds every entry point to this between guard
+ *     bands, at exactly the documented sizes.
  *   - return value: 0 on success, a negative anyloc_status otherwise;
  *     anyloc_last_error() returns a thread-local description of the last
  *     failure.  No C++ exception crosses the ABI.
@@ -561,8 +578,11 @@ int anyloc_vit_attach_h2(anyloc_vit_t* h, const anyloc_vit_block_h2* blocks /*ho
  * operand image) -- how loose the bound was: the epilogue leaves the rows' maxima by atomicMax (no extra read of the image),
  * one small launch at the end of the forward reduces them.  per_image = 0: ffn_looseness[depth], one figure per block over
  * all rows of the call; per_image = 1: ffn_looseness[depth][batch] (row-major, the call's batch), one figure per block and
- * image, so that a caller can decide per IMAGE -- independent of what else is in the batch and of earlier calls.  A block that
- * did not run fused (exact mode, not executed) reports 0.  NULL switches it off (default).
+ * image, so that a caller can decide per IMAGE -- independent of what else is in the batch and of earlier calls.  A forward
+ * writes the figures of the blocks it EXECUTES, layers 0 .. its last tapped layer: the first (last layer + 1) entries / rows of
+ * the array, and nothing behind them; a block among them whose FFN did not run fused (exact mode; the last block of a forward
+ * that ends at a q / k / v tap, which it leaves before the FFN) reports 0.  NULL switches it off
+ * (default).
  * anyloc_vit_block_ffn_exact(h, layer, 1) makes that block write its activation as fp32 and quantise it against the exact
  * row maximum instead (the data flow of fc1_bound = 0).  The Python host checks EVERY call: images with a block above 2^14
  * are run again with exactly their own loose blocks switched, and the switches are cleared after the call. */
