@@ -173,6 +173,7 @@ class HipDinoV2:
         self.name, self.dim, self.depth, self.heads, self.hidden = name, dim, depth, heads, hidden
         self.n_reg = n_registers(name)     # register rows between CLS and the patches
         self.ffn_kind = 0 if ffn == "mlp" else 1
+        self.fc1_layout = 0                # h3, SwiGLU: 1 = the fc1 image in the 16-channel block layout (option h3_swiglu_t)
         self.device = device
         dev = lambda t: t.detach().to(device, torch.float32).contiguous()
         self._keep = []          # device tensors the C handle points into
@@ -228,6 +229,7 @@ class HipDinoV2:
                 # channel 16 B + 8 h + 4 q + i of the gates (v = 0) / values (v = 1), the order in which the transposed
                 # MFMA accumulators of gemm_h3's SwiGLU epilogue hold them
                 swiglu_t = self.ffn_kind == 1 and hidden % 64 == 0 and ops.get_option("h3_swiglu_t") != 0
+                self.fc1_layout = 1 if swiglu_t else 0        # what the handle was given (anyloc_vit_block_h2.fc1_layout)
                 for f in ("qkv", "proj", "fc1", "fc2"):
                     mat = dev(vals[f + "_w"])
                     if f == "fc1" and swiglu_t:

@@ -87,7 +87,10 @@ const char* anyloc_last_error(void);
  * call path reads the environment.  The one environment variable,
  * ANYLOC_OPTIONS="name=value,name=value", is parsed once, when the first
  * option is looked up (and again by anyloc_reset_options).  Names:
- *   gemm_f32_cfg x6_cfg h3_cfg        tile configuration of the three GEMM kernels (0 = default)
+ *   gemm_f32_cfg x6_cfg h3_cfg        tile configuration of the three GEMM kernels (0 = default).  Held to the float64 reference by
+ *                                     tests/test_gpu_tile_configs.py: gemm_f32_cfg 1 - 4, 10, 11, 20; x6_cfg 1 - 9; h3_cfg 1 - 5.
+ *                                     gemm_f32_cfg 5 - 8 compute WRONG results (no staging in the K loop / no barrier): timing-only
+ *                                     ablations for tools/microbench_gemm.py alone
  *   h3_group_m (8)                    gemm_h3 tile rows per XCD scheduling group
  *   h3_tiny_max (256) h3_deep_max (320) h3_deep2_max (500)
  *                                     gemm_h3 small-problem tile / ring-depth thresholds (tile counts)

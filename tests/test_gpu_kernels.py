@@ -71,13 +71,22 @@ def test_layernorm(dev, rows, dim):
     assert float((out.double() - ref).abs().max()) < 5e-6
 
 
-@pytest.mark.parametrize("kernel", ["fp32-mfma", "split-bf16"])
-@pytest.mark.parametrize("B,T,heads", [(2, 257, 6), (1, 530, 24), (3, 33, 2), (1, 128, 1), (2, 1370, 2)])
+# option attn_cfg shapes the fp32-MFMA kernel alone (csrc/attention.hip, attn_f32_plan): 1 = exact expf and no operand preload,
+# 2 = no preload, 3 = exact expf -- three more instantiations of attention_kernel; the split-bf16 kernel does not read it
+ATTN_KERNELS = {"fp32-mfma": (0, 0), "split-bf16": (1, 0), "fp32-mfma-cfg1": (0, 1), "fp32-mfma-cfg2": (0, 2), "fp32-mfma-cfg3": (0, 3)}
+
+
+@pytest.mark.parametrize("kernel", list(ATTN_KERNELS))
+@pytest.mark.parametrize("B,T,heads", [(2, 257, 6), (1, 530, 24), (3, 33, 2), (1, 128, 1), (2, 1370, 2), (1, 129, 1)])
 def test_attention(dev, B, T, heads, kernel, monkeypatch):
-    """Both attention kernels behind anyloc_attention against float64: the exact-fp32 MFMA one and the
-    six-product split-bf16 one the x6 forward uses (option attn_x6 selects it for anyloc_attention)."""
+    """Both attention kernels behind anyloc_attention against float64: the exact-fp32 MFMA one -- under every value of option
+    attn_cfg -- and the six-product split-bf16 one the x6 forward uses (option attn_x6 selects it for anyloc_attention).
+    (1, 129, 1): one query in the second 128-query block."""
     from anyloc_amd import ops
-    ops.set_option("attn_x6", 1 if kernel == "split-bf16" else 0)
+    attn_x6, attn_cfg = ATTN_KERNELS[kernel]
+    ops.set_option("attn_x6", attn_x6)
+    ops.set_option("attn_cfg", attn_cfg)
+    assert ops.get_option("attn_x6") == attn_x6 and ops.get_option("attn_cfg") == attn_cfg
     D = heads * 64
     g = torch.Generator().manual_seed(B * T + heads)
     qkv = torch.randn(B, T, 3 * D, generator=g) * 1.5

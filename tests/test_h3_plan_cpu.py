@@ -225,6 +225,35 @@ def test_the_other_epilogues_and_the_public_gemm_shapes(lib):
         assert np.all(p["ksplit"] == 1)                                  # no workspace: the table's split-K 2 is dropped
 
 
+H3_CFG_SHAPES = ((1, 33, 16), (5, 7, 48), (257, 257, 16), (300, 200, 48), (530, 1536, 1536), (1153, 257, 112), (1153, 700, 64),
+                 (2051, 4608, 1536), (2999, 8192, 1536))
+
+
+@pytest.mark.parametrize("cfg", [1, 2, 3, 4, 5])
+def test_h3_cfg_names_its_tile_at_every_size(lib, cfg):
+    """Option h3_cfg = 1 ... 5 (the sweeps' candidates, kH3Tile[1 ... 5]) bypasses the small-M table: whatever the shape -- a
+    single row, a single k-block, the block GEMMs of ViT-g --, the epilogue, the kind and the flags, the plan is the batched
+    route on exactly that tile with that tile's ring depth, unsplit, without a lead role, one workgroup per tile.  The GPU tests
+    of tests/test_gpu_tile_configs.py rely on this to know which kernel they ran."""
+    t = H3_TILES[cfg]
+    rows, cols = _bm(t), _bn(t)
+    assert (rows, cols, t[4]) == {1: (128, 256, 2), 2: (256, 256, 3), 3: (256, 256, 4), 4: (256, 256, 4), 5: (256, 256, 3)}[cfg]
+    try:
+        _set(lib, {"h3_cfg": cfg})
+        for (M, N, K), epi, kind, flags in itertools.product(H3_CFG_SHAPES, SMALL_EPILOGUES + ("gelu", "swiglu", "swiglu_t", "patch"),
+                                                             (pe.KIND_OTHER, pe.KIND_QKV, pe.KIND_FC2), FLAGS):
+            p = pe.describe(lib, M, N, K, epi, kind, flags)
+            case = (cfg, M, N, K, epi, kind, flags, p)
+            assert p["route"] == ROUTE_BATCHED and p["tile"] == cfg, case
+            assert (p["tile_rows"], p["tile_cols"], p["stages"]) == (rows, cols, t[4]), case
+            assert p["kb"] == 1 and p["ksplit"] == 1 and p["kper"] == K // 16 and p["lead"] == 0, case
+            assert p["tiles_m"] == -(-M // rows) and p["tiles_n"] == -(-N // cols), case
+            assert p["grid"] == p["tiles_m"] * p["tiles_n"], case
+            assert p["mfma16"] == 0, case                                   # (none of these shapes has 256 tiles of 256 x 256)
+    finally:
+        lib.anyloc_reset_options()
+
+
 def test_documented_winners_of_the_table(lib):
     """The measured winners named in the comments of choose() (ViT-g, one / two 322 x 322 images and one 476 x 630 image)."""
     assert lib.anyloc_reset_options() == 0
