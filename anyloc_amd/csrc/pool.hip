@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void pool_kernel(const float* __restrict__ tok
 int pool_tokens(const float* tokens, const int64_t* offsets, int64_t n_img, int64_t uniform_n, int64_t D,
                 int mode, float p, float* out, hipStream_t stream) {
   ANYLOC_CHECK_ARG(tokens && out, "pool: null pointer");
-  ANYLOC_CHECK_ARG(n_img > 0 && n_img < 65536 && D > 0 && D < (1 << 30), "pool: bad n_img=%lld / D=%lld",
+  ANYLOC_CHECK_ARG(n_img > 0 && n_img < 65536 && D > 0 && D < (1 << 30), "pool: n_img=%lld outside [1, 65535] / bad D=%lld",
                    (long long)n_img, (long long)D);
   ANYLOC_CHECK_ARG(offsets || uniform_n >= 0, "pool: need offsets or a uniform token count");
   ANYLOC_CHECK_ARG(mode >= POOL_AVG && mode <= POOL_GEM_ABS, "pool: unknown mode %d", mode);

@@ -417,6 +417,11 @@ int launch_merge(const TopkCall& c, const float* scores, int64_t ld, int64_t nco
                  float* run_v, long long* run_i, int first) {
   static_assert(PANEL <= 0x8000 && H3_PANEL <= PANEL && CAP + KMAX + 2 <= 0xffff, "merge keys hold the column in 15 bits and the slot in 16");
   const size_t k2 = (size_t)((c.p.k + 1) & ~1ll), lds = 16 * (k2 + CAP) + 12 * k2 + 16;   // 37 KiB at k = 20: four blocks per CU
+  // k = 1023 and 1024 ask for 65 552 bytes (k = 1022: 65 496), 16 more than the default limit of dynamic LDS
+  constexpr int LDS_KMAX = 16 * (KMAX + CAP) + 12 * KMAX + 16;
+  static_assert(KMAX % 2 == 0 && LDS_KMAX > 65536, "the merge kernel's dynamic LDS at the largest k is above the default limit");
+  static DynLds dyn_lds_once;
+  ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(topk_merge_kernel), LDS_KMAX));
   std::optional<ProfScope> prof;
   if (ncols > 0) prof.emplace("topk_merge", c.stream, 0.0, 4.0 * c.p.nq * ncols);
   hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)c.p.nq), dim3(256), lds, c.stream, scores, ld, ncols, c.index_base + col0,
@@ -595,11 +600,11 @@ int screened_search(const TopkCall& c) {
 int topk_impl(const float* queries, int64_t nq, const float* db, int64_t ndb, int64_t dim, int64_t k, int metric, unsigned flags,
               int64_t index_base, float* dist, int64_t* idx, void* workspace, size_t workspace_bytes, const void* index, hipStream_t stream) {
   ANYLOC_CHECK_ARG(nq >= 0 && ndb >= 0, "topk: negative size");
-  if (nq == 0 || k == 0) return ANYLOC_OK;
+  ANYLOC_CHECK_ARG(k >= 1 && k <= KMAX, "topk: k=%lld outside [1,%d]", (long long)k, KMAX);
+  if (nq == 0) return ANYLOC_OK;
   ANYLOC_CHECK_ARG(queries && dist && idx, "topk: null pointer");
   ANYLOC_CHECK_ARG(db || ndb == 0 || index, "topk: null database");
   const bool indexed = index != nullptr;
-  ANYLOC_CHECK_ARG(k >= 1 && k <= KMAX, "topk: k=%lld outside [1,%d]", (long long)k, KMAX);
   ANYLOC_CHECK_ARG(metric == 0 || metric == 1, "topk: metric %d", metric);
   ANYLOC_CHECK_ARG(dim >= 4 && dim % 4 == 0, "topk: dim %lld must be a positive multiple of 4", (long long)dim);
   ANYLOC_CHECK_ARG(nq < (1ll << 31), "topk: too many queries");
@@ -612,8 +617,6 @@ int topk_impl(const float* queries, int64_t nq, const float* db, int64_t ndb, in
     return ANYLOC_ERR_WORKSPACE;
   }
   if (indexed) c.iv = index_view(const_cast<void*>(index), ndb, dim);
-  static DynLds dyn_lds_once;   // the merge kernel's dynamic LDS at the largest k
-  ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(topk_merge_kernel), (int)(16 * (KMAX + CAP) + 12 * KMAX + 16)));
   // whether this call screens: the plan allows it, and there is something to re-score the candidates from
   const bool screen = c.p.sc_cols > 0 && (db != nullptr || c.rescore_planes) && ndb > 0;
   ANYLOC_TRY(prologue(c, screen));

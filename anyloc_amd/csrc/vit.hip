@@ -233,6 +233,7 @@ int anyloc_layernorm(const float* x, float* y, const float* weight, const float*
 int anyloc_attention(const float* qkv, float* out, int64_t batch, int64_t tokens, int64_t dim, int64_t heads,
                      void* stream) {
   ANYLOC_CHECK_ARG(qkv && out, "attention: null pointer");
+  ANYLOC_CHECK_ARG(batch > 0 && batch < 65536, "attention: batch %lld outside [1, 65535]", (long long)batch);
   return attention(qkv, out, batch, (int)tokens, nullptr, batch * tokens, (int)dim, (int)heads, static_cast<hipStream_t>(stream));
 }
 
@@ -260,6 +261,7 @@ int anyloc_attention_h3(const float* qkv, void* out_img, float* out_inv, int64_t
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   ANYLOC_CHECK_ARG(qkv && out_img && out_inv && workspace, "attention_h3: null pointer");
   ANYLOC_CHECK_ARG(batch > 0 && tokens > 0 && heads > 0 && dim == heads * 64, "attention_h3: bad shape");
+  ANYLOC_CHECK_ARG(batch < 65536, "attention_h3: batch %lld outside [1, 65535]", (long long)batch);   // (before the tiles are built)
   unsigned char* planes;
   float* inv;
   ANYLOC_TRY(h3_tiles_in_workspace("attention_h3", qkv, batch * tokens, dim, heads, workspace, workspace_bytes, stream, &planes, &inv));

@@ -699,7 +699,8 @@ int anyloc_vlad_assigned(const float* tokens, int64_t n_tok, int64_t D, const fl
   // (an assignment of no tokens has no address: both may be NULL then, and the result is the zero vector either way)
   ANYLOC_CHECK_ARG(n_tok == 0 || (labels != nullptr) != (soft_weights != nullptr),
                    "vlad_assigned: pass labels (hard) or soft weights, not both");
-  ANYLOC_CHECK_ARG(n_tok >= 0 && n_tok < (1ll << 31) && K >= 1 && K <= 256 && D >= 4 && D % 4 == 0, "vlad_assigned: bad shape");
+  ANYLOC_CHECK_ARG(n_tok >= 0 && n_tok < (1ll << 31) && K >= 1 && K <= 256 && D >= 4 && D % 4 == 0,
+                   "vlad_assigned: bad shape (n_tok < 2^31, K in [1, 256], D a positive multiple of 4)");
   ANYLOC_CHECK_ARG(n_tok == 0 || labels || K <= 64, "vlad_assigned: soft weights need K <= 64");
   VladWs w = carve(workspace, workspace_bytes, n_tok, D, K);
   ANYLOC_TRY(check_workspace("vlad_assigned", workspace, workspace_bytes, w.bytes));

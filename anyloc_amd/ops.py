@@ -359,15 +359,23 @@ def vlad_assigned(tokens, centers, labels=None, soft=None, norm_descs=True, intr
 
 
 POOL_MODES = {"average": 0, "avg": 0, "max": 1, "gem": 2, "gem_abs": 3}
+POOL_MAX_IMAGES = 65535    # images per anyloc_pool_tokens call (one grid row each)
 
 
 def pool(tokens, method="average", gem_p=3.0):
     """One pooled descriptor per image: "average" / "max" (reference scripts/dino_v2_gp.py:130-133),
     "gem" (|mean(t^p)|^(1/p) * sign, scripts/dino_v2_gem.py:186-188) or "gem_abs" (:174-175).
 
-    tokens: device tensor [n_img, N, D] / [N, D], or a list of [N_i, D] tensors.  Returns [n_img, D]."""
+    tokens: device tensor [n_img, N, D] / [N, D], or a list of [N_i, D] tensors.  Returns [n_img, D].
+    At most 65 535 images per call (ValueError beyond)."""
     if method not in POOL_MODES:
         raise NotImplementedError(f"ID: {method}")
+    if torch.is_tensor(tokens) and tokens.dim() in (2, 3):
+        asked = 1 if tokens.dim() == 2 else tokens.shape[0]
+    else:
+        asked = tokens[1].numel() - 1 if is_packed_pair(tokens) else len(tokens)
+    if asked > POOL_MAX_IMAGES:
+        raise ValueError(f"pool: {asked} images in one call, anyloc_pool_tokens takes at most {POOL_MAX_IMAGES} (pool the batch in pieces)")
     device = _lib.require_gpu()
     lib = _lib.load()
     if torch.is_tensor(tokens) and tokens.dim() in (2, 3):

@@ -167,7 +167,9 @@ int anyloc_l2norm_rows(const float* x, float* out, int64_t rows, int64_t dim,
  *   CenterCrop to multiples of 14 (scripts/dino_v2_vlad.py:173-176,
  *   demo/anyloc_vlad_generate.py:179-181) that precede the extractor.
  *   img_hwc [B,H,W,3] uint8 (device), mean3/std3: HOST arrays of 3 floats,
- *   out [B,3,crop_h,crop_w] float32 (device). */
+ *   out [B,3,crop_h,crop_w] float32 (device).
+ *   Limits: batch in [1, 65535] and height <= 65535 (one grid plane per image, one grid row per image row); more images
+ *   are ANYLOC_ERR_INVALID_ARG -- ingest them in several calls. */
 int anyloc_preprocess_u8(const unsigned char* img_hwc, int64_t batch, int64_t height,
                          int64_t width, int64_t crop_h, int64_t crop_w,
                          const float* mean3, const float* std3, float* out, void* stream);
@@ -177,7 +179,8 @@ int anyloc_preprocess_u8(const unsigned char* img_hwc, int64_t batch, int64_t he
  * multiples of 14).  in [planes, H, W] fp32 (planes = B*3) is resized to (out_h, out_w) with torch's bicubic
  * convolution (A = -0.75, align_corners = False, no antialias) and only the window
  * [crop_top, crop_top + crop_h) x [crop_left, crop_left + crop_w) of the resized image is written:
- * out [planes, crop_h, crop_w]. */
+ * out [planes, crop_h, crop_w].  Limits: planes in [1, 65535] (21 845 RGB images) and out_h <= 65535; more are
+ * ANYLOC_ERR_INVALID_ARG. */
 int anyloc_resize_bicubic(const float* in, int64_t planes, int64_t height, int64_t width,
                           int64_t out_h, int64_t out_w, int64_t crop_top, int64_t crop_left,
                           int64_t crop_h, int64_t crop_w, float* out, void* stream);
@@ -249,7 +252,9 @@ int anyloc_h3_plan_describe(int64_t M, int64_t N, int64_t K, const char* epilogu
  *   ANYLOC_POOL_GEM_ABS  mean(|t|^p)^(1/p)         (scripts/dino_v2_gem.py:174-175)
  *   tokens  [total_tokens, D]; image i = rows offsets[i] .. offsets[i+1]
  *           (offsets: n_img+1 int64 on the device), or offsets == NULL and every
- *           image has n_tok rows.  out [n_img, D].  p is read by the GeM modes only. */
+ *           image has n_tok rows.  out [n_img, D].  p is read by the GeM modes only.
+ *   Limits: n_img in [1, 65535] (one grid row per image) and D < 2^30; more images are ANYLOC_ERR_INVALID_ARG -- pool them
+ *   in several calls. */
 #define ANYLOC_POOL_AVG 0
 #define ANYLOC_POOL_MAX 1
 #define ANYLOC_POOL_GEM 2
@@ -299,7 +304,8 @@ int anyloc_gemm_nt(const float* A, int64_t lda, const float* W, int64_t ldw,
 /* Building blocks of the ViT forward, exposed for unit tests:
  * LayerNorm over the last dim (eps as given; DINOv2 uses 1e-6) and multi-head
  * self-attention softmax((q/8) k^T) v with head_dim 64 on a packed QKV buffer
- * [B*T, 3*D] (q | k | v, heads contiguous) -> out [B*T, D]. */
+ * [B*T, 3*D] (q | k | v, heads contiguous) -> out [B*T, D].  batch in [1, 65535] for both
+ * attention entry points (65 536 images and more: ANYLOC_ERR_INVALID_ARG). */
 int anyloc_layernorm(const float* x, float* y, const float* weight, const float* bias,
                      int64_t rows, int64_t dim, float eps, void* stream);
 int anyloc_attention(const float* qkv, float* out, int64_t batch, int64_t tokens,
@@ -324,6 +330,9 @@ int anyloc_attention_h3(const float* qkv, void* out_img, float* out_inv, int64_t
  *   centers  [K, D]              raw k-means centroids (c_centers)
  *   out      [n_img, K*D]        normalised VLAD descriptors
  *   labels   [total_tokens] int64 or NULL: hard assignment of every token
+ * Limits: K in [1, 256] (anyloc_vlad_soft, anyloc_vlad_soft_weights and the soft weights of anyloc_vlad_assigned: K in
+ *   [1, 64]), D a positive multiple of 4; anything else is ANYLOC_ERR_INVALID_ARG.  n_img is not limited by a grid
+ *   dimension: the two-pass kernels run in groups of 65 535 images, the one-pass kernel on a 1-D grid.
  * flags: ANYLOC_VLAD_NORM_DESCS re-normalises tokens before the residual
  *   (utilities.py:959-960); ANYLOC_VLAD_INTRA_NORM normalises each cluster
  *   block (:859-860).  Labels are argmax_k of the fast-pytorch-kmeans cosine
@@ -390,7 +399,8 @@ int anyloc_vlad_assigned(const float* tokens, int64_t n_tok, int64_t D, const fl
  *   utilities.py:766, :786 (and predict at :849).  The division by counts, the
  *   NaN->0 rule, the tolerance test and (multi-GPU) the all-reduce of
  *   sums/counts are done by the host (anyloc_amd/kmeans.py).
- *   mode 0 = cosine (rows/(norm+1e-8)), 1 = euclidean (2ab - a^2 - b^2). */
+ *   mode 0 = cosine (rows/(norm+1e-8)), 1 = euclidean (2ab - a^2 - b^2).
+ *   Limits: n >= 1, K in [1, 256], D a positive multiple of 4; anything else is ANYLOC_ERR_INVALID_ARG. */
 size_t anyloc_kmeans_workspace_bytes(int64_t n, int64_t D, int64_t K);
 int anyloc_kmeans_step(const float* x, int64_t n, int64_t D, const float* centers,
                        int64_t K, int mode, float* sums, float* counts,
@@ -410,6 +420,8 @@ int anyloc_kmeans_update(const float* sums, const float* counts, const float* ce
  *   utilities.py:439-450 (called from get_top_k_recall).
  *   metric 0: inner product, best = largest;  1: squared L2, best = smallest.
  *   dist [nq,k] fp32 and idx [nq,k] int64, best first; idx = index_base + row.
+ *   k in [1, 1024] (the running lists are merged in LDS); k = 0 and k > 1024 are ANYLOC_ERR_INVALID_ARG, in the
+ *   searches of a prepared index too.  dim a positive multiple of 4.
  *   If k > ndb the tail is padded with idx -1 (faiss behaviour).
  *   Ties are broken towards the lower database index.
  *   flags: ANYLOC_TOPK_NORMALIZE_DB -- the database is given RAW and every row is used as

@@ -93,11 +93,24 @@ def test_attention(dev, B, T, heads, kernel, monkeypatch):
     qkv[0, 3, :D] *= 6.0      # a spiky query/key pair: forces the running-max rescale path
     qkv[0, T - 2, D:2 * D] *= 6.0
     out = ops.attention(qkv.to(dev), heads).cpu()
+    check_attention(out, qkv, heads)
+
+
+def attention_f64(qkv, heads):
+    """softmax((q / 8) k^T) v per 64-wide head in float64: qkv [B, T, 3 D] -> [B, T, D]"""
+    B, T, D3 = qkv.shape
     q, k, v = qkv.double().reshape(B, T, 3, heads, 64).permute(2, 0, 3, 1, 4)
     a = torch.softmax((q * 0.125) @ k.transpose(-2, -1), dim=-1)
-    ref = (a @ v).transpose(1, 2).reshape(B, T, D)
-    assert float((out.double() - ref).abs().max()) < 2e-5, float((out.double() - ref).abs().max())
+    return (a @ v).transpose(1, 2).reshape(B, T, D3 // 3)
+
+
+def check_attention(out, qkv, heads):
+    """anyloc_attention's output (CPU) against float64; -> the largest absolute error"""
+    ref = attention_f64(qkv, heads)
+    worst = float((out.double() - ref).abs().max())
+    assert worst < 2e-5, worst
     assert _rel(out, ref) < 5e-6
+    return worst
 
 
 @pytest.mark.parametrize("qg,ks", [(1, 1), (2, 1), (1, 2)], ids=["4x32q", "2x64q", "2x32q-x-2keys"])
@@ -119,10 +132,15 @@ def test_attention_h3(dev, B, T, heads, qg, ks):
     if T > 64:
         qkv[0, 32:64, 2 * D:] = 0.0                       # an all-zero V tile (global rows 32..63): must not set the scale
     img, inv = ops.attention_h3(qkv.to(dev), heads)
+    check_attention_h3(img, inv, qkv, heads)
+
+
+def check_attention_h3(img, inv, qkv, heads):
+    """anyloc_attention_h3's output image and row scales (device) against float64; -> the largest absolute error"""
+    from anyloc_amd import ops
+    B, T, D = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
     out = ops.h2_image_to_f32(img, inv, B * T, D).reshape(B, T, D).cpu()
-    q, k, v = qkv.double().reshape(B, T, 3, heads, 64).permute(2, 0, 3, 1, 4)
-    a = torch.softmax((q * 0.125) @ k.transpose(-2, -1), dim=-1)
-    ref = (a @ v).transpose(1, 2).reshape(B, T, D)
+    ref = attention_f64(qkv, heads)
     # every row of an image carries 22 bits relative to the image's largest |v|: error <= 2^-22 of that bound
     vmax = qkv[:, :, 2 * D:].abs().amax(dim=(1, 2)).double()
     err = (out - ref).abs().amax(dim=(1, 2))
@@ -132,6 +150,7 @@ def test_attention_h3(dev, B, T, heads, qg, ks):
     inv_c = inv.cpu().reshape(B, T)
     assert bool((inv_c == inv_c[:, :1]).all())            # one power-of-two scale per image
     assert bool((torch.log2(inv_c) == torch.log2(inv_c).round()).all())
+    return float(err.max())
 
 
 def _attention_h3_raw(qkv, heads, tokens=None):
@@ -212,15 +231,22 @@ def test_preprocess_u8_matches_totensor_normalize_centercrop(dev, H, W):
     g = torch.Generator().manual_seed(H + W)
     u8 = torch.randint(0, 256, (3, H, W, 3), generator=g, dtype=torch.uint8)
     out = preprocess.images_to_input(u8).cpu()
+    ref = totensor_normalize_centercrop(u8)
+    assert out.shape == ref.shape
+    assert torch.equal(out, ref)
+
+
+def totensor_normalize_centercrop(u8):
+    """uint8 [B, H, W, 3] (CPU) -> ToTensor + Normalize + CenterCrop(H // 14 * 14, W // 14 * 14) in torch on the CPU"""
+    from anyloc_amd import synth
+    H, W = u8.shape[1:3]
     x = u8.permute(0, 3, 1, 2).float().div(255)
     mean = torch.tensor(synth.IMAGENET_MEAN).view(1, 3, 1, 1)
     std = torch.tensor(synth.IMAGENET_STD).view(1, 3, 1, 1)
     x = (x - mean) / std
     th, tw = H // 14 * 14, W // 14 * 14
     t, l = int(round((H - th) / 2.0)), int(round((W - tw) / 2.0))
-    ref = x[..., t:t + th, l:l + tw]
-    assert out.shape == ref.shape
-    assert torch.equal(out, ref)
+    return x[..., t:t + th, l:l + tw]
 
 
 @pytest.mark.parametrize("H,W,max_size", [(480, 640, 322), (700, 500, 448), (333, 1024, 1024), (2000, 1500, 1024)])

@@ -254,20 +254,24 @@ def test_kmeans_update_empty_clusters():
     """sums / counts of an assignment that leaves two clusters empty: their new centres are exactly 0 (fpk: 0/0 -> NaN -> 0),
     every other entry is one fp32 division (within one ulp, a relative 2^-23, of the float64 quotient), and the error is the
     float64 sum of the fp32 squares (new - old)^2 up to the re-ordering of 900 float64 terms (1e-12)."""
+    check_kmeans_update(9, 100, 400, [2, 6])
+
+
+def check_kmeans_update(K, D, n, empty):
+    """``n`` rows dealt at random over the K clusters but those of ``empty``: ops.kmeans_update against the expressions above."""
     from anyloc_amd import ops
-    K, D, n = 9, 100, 400
     g = torch.Generator().manual_seed(K * D)
     x = torch.randn(n, D, generator=g)
-    live = torch.tensor([0, 1, 3, 4, 5, 7, 8])                  # clusters 2 and 6 get no row
+    live = torch.tensor([k for k in range(K) if k not in empty])
     closest = live[torch.randint(0, len(live), (n,), generator=g)]
     onehot = (closest[None, :] == torch.arange(K)[:, None]).to(x.dtype)
     sums, counts = onehot @ x, onehot.sum(-1)                    # as oracle/fpk_kmeans.py forms them
-    assert counts[2] == 0 and counts[6] == 0 and float(sums[[2, 6]].abs().max()) == 0.0 and int((counts > 0).sum()) == 7
+    assert bool((counts[empty] == 0).all()) and float(sums[empty].abs().max()) == 0.0 and int((counts > 0).sum()) == K - len(empty)
     old = torch.randn(K, D, generator=g)
     new, err = ops.kmeans_update(sums.to(DEV), counts.to(DEV), old.to(DEV))
     new, err = new.cpu(), float(err.cpu())
     assert tuple(new.shape) == (K, D) and bool(torch.isfinite(new).all())
-    assert float(new[[2, 6]].abs().max()) == 0.0
+    assert float(new[empty].abs().max()) == 0.0
     used = counts > 0
     q = sums[used].double() / counts[used].double()[:, None]
     assert bool(((new[used].double() - q).abs() <= 2.0 ** -23 * q.abs()).all())

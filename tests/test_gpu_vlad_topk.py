@@ -71,22 +71,32 @@ def test_vlad_hard_golden(golden_dir, tag):
             assert float(out[0, k * D:(k + 1) * D].abs().max()) == 0.0
 
 
+VLAD_FLAG_PAIRS = ((True, True), (False, True), (True, False))      # (norm_descs, intra_norm)
+
+
+def check_vlad_hard_image(out_i, lab_i, x_i, centers, norm_descs=True, intra=True):
+    """One image's descriptor and labels against the oracle; -> its l2rel"""
+    v, l = vlad_ref.vlad_hard(x_i, centers, norm_descs, intra)
+    lab_i = lab_i.cpu()
+    if check_labels(lab_i, l, x_i, centers):
+        # a token sat on a cosine tie (< 1e-6): score the descriptor under the same assignment
+        v = vlad_ref.vlad_hard(x_i, centers, norm_descs, intra, labels=lab_i)[0]
+    err = l2rel(out_i, v)
+    assert err < VLAD_RTOL, err
+    return err
+
+
 @pytest.mark.parametrize("K,D,N", [(8, 384, 256), (32, 1536, 529), (64, 1024, 300), (5, 64, 77), (128, 128, 500), (200, 256, 700)])
 def test_vlad_hard_vs_oracle_flags_and_ragged(K, D, N):
     from anyloc_amd import ops
     g = torch.Generator().manual_seed(K * D + N)
     x = synth.clustered_tokens(3, N, D, n_modes=K, seed=K + N) * (0.5 + torch.rand(3, N, 1, generator=g))
     centers = 0.7 * synth.clustered_tokens(1, K, D, n_modes=K, seed=K + N)[0] + 0.01 * torch.randn(K, D, generator=g)
-    for norm_descs, intra in ((True, True), (False, True), (True, False)):
+    for norm_descs, intra in VLAD_FLAG_PAIRS:
         out, lab = ops.vlad(x.to(DEV), centers.to(DEV), norm_descs=norm_descs, intra_norm=intra,
                             return_labels=True)
         for i in range(2):
-            v, l = vlad_ref.vlad_hard(x[i], centers, norm_descs, intra)
-            lab_i = lab[i * N:(i + 1) * N].cpu()
-            if check_labels(lab_i, l, x[i], centers):
-                # a token sat on a cosine tie (< 1e-6): score the descriptor under the same assignment
-                v = vlad_ref.vlad_hard(x[i], centers, norm_descs, intra, labels=lab_i)[0]
-            assert l2rel(out[i], v) < VLAD_RTOL
+            check_vlad_hard_image(out[i], lab[i * N:(i + 1) * N], x[i], centers, norm_descs, intra)
     # ragged list with an empty image and a single-token image
     parts = [x[0, :N // 2], x[1, :0], x[2, :1], x[2]]
     out = ops.vlad([p.to(DEV) for p in parts], centers.to(DEV))
@@ -210,13 +220,23 @@ def test_kmeans_step_fused_path_vs_oracle(n, D, K, mode):
     x = x * (0.5 + torch.rand(n, 1, generator=g))
     c = x[torch.randperm(n, generator=g)[:K]].clone() + 0.01 * torch.randn(K, D, generator=g)
     sums, counts, lab = ops.kmeans_step(x.to(DEV), c.to(DEV), mode, True)
+    check_kmeans_step(x, c, mode, sums, counts, lab)
+
+
+def check_kmeans_step(x, c, mode, sums, counts, lab):
+    """One ops.kmeans_step of the rows ``x`` against the centres ``c`` (CPU tensors) against the fast-pytorch-kmeans rule.
+    -> (labels excused as oracle near-ties, l2rel of the sums)"""
+    from oracle.fpk_kmeans import KMeans as RefKM
+    K = c.shape[0]
     sim = RefKM.cos_sim(x, c) if mode == "cosine" else RefKM.euc_sim(x, c)
     ref_lab = sim.max(dim=-1)[1]
-    check_labels_sim(lab, ref_lab, sim)
+    excused = check_labels_sim(lab, ref_lab, sim)
     lab_c = lab.cpu()
     onehot = (lab_c[None] == torch.arange(K)[:, None]).double()
     assert torch.equal(counts.cpu(), onehot.sum(-1).float())
-    assert l2rel(sums, onehot @ x.double()) < 1e-6
+    err = l2rel(sums, onehot @ x.double())
+    assert err < 1e-6, err
+    return excused, err
 
 
 def test_vlad_fit_surface_matches_reference_semantics(golden_dir, capsys):
@@ -269,6 +289,44 @@ def test_topk_vs_oracle(nq, ndb, dim, k, metric):
     assert torch.equal(torch.where(i2.cpu() >= 0, i2.cpu() - 1000, i2.cpu()), i)
 
 
+TOPK_DIST_ATOL = 3e-6     # a returned distance against the float64 score of the row it names
+TOPK_SWAP_GAP = 1e-5      # a differing index only where the reference distances at that rank are closer than this
+
+
+def normalized_search_data(nq, ndb, dim):
+    """-> (unit queries [nq, dim], RAW database rows [ndb, dim]) of test_topk_normalize_db_vs_oracle."""
+    g = torch.Generator().manual_seed(nq + ndb + dim)
+    db = torch.randn(ndb, dim, generator=g) * (0.2 + 3.0 * torch.rand(ndb, 1, generator=g))   # norms all over the place
+    qu = torch.nn.functional.normalize(torch.randn(nq, dim, generator=g))
+    db[11] = 0.0                                        # a zero row stays zero under F.normalize
+    db[40] = 2.5 * db[7]                                # same direction, different norm: an exact tie after normalising?
+    qu[0] = torch.nn.functional.normalize(db[7], dim=0)
+    return qu, db
+
+
+def check_normalized_search(d, i, qu, db, k, metric):
+    """Lists ``d``, ``i`` (CPU) of a search of the unit queries ``qu`` against F.normalize(``db``), db the RAW rows of
+    ``normalized_search_data``: against the flat search over the fp32-normalised rows and the float64 score matrix.
+    -> the largest distance error."""
+    ndb = db.shape[0]
+    d_ref, i_ref = faiss_flat.flat_search(qu, torch.nn.functional.normalize(db), k, metric)
+    d64 = qu.double() @ torch.nn.functional.normalize(db.double()).t()
+    if metric == "l2":
+        d64 = 2.0 - 2.0 * d64
+        d64[:, 11] = 1.0                                # |q|^2 + 0 - 0 for the zero row
+    kk = min(k, ndb)
+    got64 = torch.gather(d64, 1, i[:, :kk])
+    worst = float((d[:, :kk].double() - got64).abs().max())
+    print(f"[topk {tuple(qu.shape)} x {ndb} k={k} {metric}] largest distance error to float64 {worst:.3e} (bar {TOPK_DIST_ATOL:.0e})")
+    np.testing.assert_allclose(d[:, :kk].double().numpy(), got64.numpy(), atol=TOPK_DIST_ATOL)      # each distance is the true one
+    mism = i[:, :kk] != i_ref[:, :kk]
+    if mism.any():                                      # only near-ties may swap
+        assert float((d_ref[:, :kk][mism] - d[:, :kk][mism]).abs().max()) < TOPK_SWAP_GAP
+    assert {int(i[0, 0]), int(i[0, 1])} == {7, 40}      # the two rows of the query's own direction come first
+    assert bool((d[:, :kk - 1] >= d[:, 1:kk]).all()) if metric == "ip" else bool((d[:, :kk - 1] <= d[:, 1:kk]).all())
+    return worst
+
+
 @pytest.mark.parametrize("nq,ndb,dim,k,metric", [(61, 3000, 4096, 20, "ip"), (61, 3000, 4096, 20, "l2"), (64, 700, 8192, 7, "ip"),
                                                   (1, 130, 49152, 20, "ip"), (5, 33000, 4096, 20, "ip"),
                                                   (200, 2000, 4096, 10, "ip"), (9, 103, 64, 12, "l2")])
@@ -277,28 +335,12 @@ def test_topk_normalize_db_vs_oracle(nq, ndb, dim, k, metric):
     the scores.  Covers the few-query split-K path (<= 64 queries, dim >= 4096: database rows as the GEMM's M operand,
     row norms from the same pass, several panels) and the panel-GEMM path, against normalise-then-flat-search."""
     from anyloc_amd import ops
-    g = torch.Generator().manual_seed(nq + ndb + dim)
-    db = torch.randn(ndb, dim, generator=g) * (0.2 + 3.0 * torch.rand(ndb, 1, generator=g))   # norms all over the place
-    qu = torch.nn.functional.normalize(torch.randn(nq, dim, generator=g))
-    db[11] = 0.0                                        # a zero row stays zero under F.normalize
-    db[40] = 2.5 * db[7]                                # same direction, different norm: an exact tie after normalising?
-    qu[0] = torch.nn.functional.normalize(db[7], dim=0)
+    qu, db = normalized_search_data(nq, ndb, dim)
     d, i = ops.topk(qu.to(DEV), db.to(DEV), k, metric, normalize_db=True)
     dbn = torch.nn.functional.normalize(db)
-    d_ref, i_ref = faiss_flat.flat_search(qu, dbn, k, metric)
-    d64 = qu.double() @ torch.nn.functional.normalize(db.double()).t()
-    if metric == "l2":
-        d64 = 2.0 - 2.0 * d64
-        d64[:, 11] = 1.0                                # |q|^2 + 0 - 0 for the zero row
     d, i = d.cpu(), i.cpu()
     kk = min(k, ndb)
-    got64 = torch.gather(d64, 1, i[:, :kk])
-    np.testing.assert_allclose(d[:, :kk].double().numpy(), got64.numpy(), atol=3e-6)      # each distance is the true one
-    mism = i[:, :kk] != i_ref[:, :kk]
-    if mism.any():                                      # only near-ties may swap
-        assert float((d_ref[:, :kk][mism] - d[:, :kk][mism]).abs().max()) < 1e-5
-    assert {int(i[0, 0]), int(i[0, 1])} == {7, 40}      # the two rows of the query's own direction come first
-    assert bool((d[:, :kk - 1] >= d[:, 1:kk]).all()) if metric == "ip" else bool((d[:, :kk - 1] <= d[:, 1:kk]).all())
+    check_normalized_search(d, i, qu, db, k, metric)
     # identical to normalising first and searching without the flag, up to fp32 noise
     d2, i2 = ops.topk(qu.to(DEV), dbn.to(DEV), k, metric)
     assert float((d2.cpu()[:, :kk] - d[:, :kk]).abs().max()) < 5e-6
@@ -306,13 +348,20 @@ def test_topk_normalize_db_vs_oracle(nq, ndb, dim, k, metric):
 
 
 @pytest.mark.parametrize("order", ["ascending", "descending", "constant", "blocks"])
-@pytest.mark.parametrize("k", [1, 20, 300])
+@pytest.mark.parametrize("k", [1, 20, 300, 1023, 1024])
 def test_topk_merge_adversarial_orders(order, k):
     """The merge kernel keeps only the columns that beat the running k-th entry (csrc/topk.hip): score rows that rise
     monotonically (every tile beats the threshold: one selection per tile), fall, are all equal (every entry ties: lower
-    index first) or come in equal-valued blocks must give exactly the flat search's lists -- over several panels."""
+    index first) or come in equal-valued blocks must give exactly the flat search's lists -- over several panels.
+    k = 1023 and 1024: the two list lengths whose dynamic LDS (65 552 bytes) is above the default limit, a list longer
+    than the 256 seed columns, and selections over 3 300 keys."""
+    check_adversarial_order(order, k, 70001, 8, (1.0, 2.0, -1.0))     # three 32768-row panels, the last one ragged
+
+
+def check_adversarial_order(order, k, ndb, dim, scales):
+    """One database row per score, score j along the first axis; one query per entry of ``scales``, that multiple of the
+    first axis (a negative one reverses the order)."""
     from anyloc_amd import ops
-    ndb, dim = 70001, 8                                   # three 32768-row panels, the last one ragged
     u = torch.zeros(dim)
     u[0] = 1.0
     j = torch.arange(ndb, dtype=torch.float32)
@@ -325,7 +374,7 @@ def test_topk_merge_adversarial_orders(order, k):
     else:
         s = torch.floor(j / 97.0) % 13 / 13.0 + 0.25      # blocks of 97 equal scores, 13 levels, repeating
     db = s[:, None] * u[None, :]
-    qu = torch.stack([u, 2.0 * u, -u])                    # -u reverses the order
+    qu = torch.tensor(scales)[:, None] * u[None, :]       # (u, 2 u, -u: -u reverses the order)
     for metric in ("ip", "l2"):
         d, i = ops.topk(qu.to(DEV), db.to(DEV), k, metric)
         d_ref, i_ref = faiss_flat.flat_search(qu, db, k, metric)
