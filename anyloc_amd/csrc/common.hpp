@@ -165,6 +165,11 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// A GATED launch (topk.hip, ANYLOC_TOPK_NO_WAIT): the host enqueues it without knowing whether it is needed; a device word written
+// by an earlier kernel of the stream decides.  Asked at kernel entry, before any barrier or LDS use; the answer is the same for
+// every lane of the launch.
+__device__ __forceinline__ bool gate_closed(const int* gate) { return gate != nullptr && *gate == 0; }
+
 // ---- exact three-way bf16 split (split-bf16 GEMM / attention): x = x1 + x2 + x3, round-to-nearest-even at every
 // step, residuals exact in fp32.  Two values per call: v_cvt_pk_bf16_f32 rounds and packs a pair in one instruction;
 // pk[plane] = (plane of a) | (plane of b) << 16.
@@ -329,6 +334,9 @@ struct H3Problem {
   float ln_bound[4]; int ln_has_bound;
   unsigned* ln_tickets; int ln_wgs;
   const char* tag;
+  // EPI_STORE only (the retrieval's score panels): device word that decides whether the launch works at all -- nullptr = run;
+  // *gate == 0: every workgroup returns at entry (gate_closed below).  Last member: no other field moves.
+  const int* gate;
 };
 
 // Layout of the Q / K / V operand tiles attention_h3 consumes (written by gemm_h3's EPI_QKV_PLANES epilogue).
@@ -346,7 +354,7 @@ size_t h2_bytes(int64_t rows, int64_t K);
 int split_h2(const float* x, int64_t ldx, int64_t rows, int64_t K, void* h2, float* inv_scale, hipStream_t stream);
 // rows of any width (K % 16 == 0; used above 4096 columns): also returns the rows' sums of squares when row_sumsq != nullptr
 int split_h2_wide(const float* x, int64_t ldx, int64_t rows, int64_t K, void* h2, float* inv_scale, float* row_sumsq,
-                  hipStream_t stream);
+                  hipStream_t stream, const int* gate = nullptr);
 // the first half of it alone: inv_scale[row] = 2^-e of the row-scaled split (and the rows' sums of squares when asked)
 int row_scales_h2(const float* x, int64_t ldx, int64_t rows, int64_t K, float* inv_scale, float* row_sumsq, hipStream_t stream);
 int split_h1_wide(const float* x, int64_t ldx, int64_t rows, int64_t K, void* h2, float* inv_scale, float* row_sumsq, float* resid_sq,
@@ -406,7 +414,12 @@ int screen_margins(const float* qn, const float* rho_q, const unsigned* rho_max,
                    float accum, float* margin, hipStream_t stream);
 int screen_compact(const float* scores, int64_t ld, int64_t ncols, int64_t nq, int k, int metric, const float* qn, const float* dn,
                    const float* dnorm, const float* thr, const float* margin, int cmax, int* cand, int* count, int* overflow,
-                   hipStream_t stream);
+                   int* over_q, hipStream_t stream);
+// over_q[q] != 0 for the queries that overflowed in some range -> plan[0] = how many, plan[1] = 1 <= plan[0] <= side_cap,
+// plan[2] = plan[0] > side_cap, plan[4 + j] = the j-th of them in ascending order (j < side_cap <= SCREEN_SIDE_Q; -1 beyond)
+constexpr int SCREEN_SIDE_Q = 64;
+constexpr int SCREEN_PLAN_INTS = 4 + SCREEN_SIDE_Q;
+int screen_overflow_plan(const int* over_q, int64_t nq, int side_cap, int* plan, hipStream_t stream);
 bool screen_rescore_supported(int64_t dim);
 int screen_rescore(const float* queries, const float* db, int64_t dim, int64_t nq, int cmax, const int* cand, const int* count,
                    int metric, const float* qn, const float* dn, const float* dnorm, float* cand_v, hipStream_t stream);

@@ -75,8 +75,9 @@ __global__ __launch_bounds__(256) void split_h2_stream_kernel(const float* __res
 // magnitude (-> the power-of-two scale) and its sum of squares (the caller's F.normalize / L2 terms come out of the
 // same read); (2) one workgroup per (16 rows, 2048 columns) quantises with the scales of (1).
 __global__ __launch_bounds__(256) void row_amax_sq_kernel(const float* __restrict__ x, int64_t ldx, int64_t dim,
-                                                          float* __restrict__ inv, float* __restrict__ ss) {
+                                                          float* __restrict__ inv, float* __restrict__ ss, const int* __restrict__ gate) {
   __shared__ float red_m[4], red_s[4];
+  if (gate_closed(gate)) return;
   const f32x4* r = reinterpret_cast<const f32x4*>(x + (int64_t)blockIdx.x * ldx);
   const int64_t n4 = dim >> 2;
   float amax = 0.f, sq = 0.f;
@@ -113,8 +114,9 @@ constexpr int WIDE_CHUNKS = 8;      // 256-column chunks per workgroup of the qu
 
 __global__ __launch_bounds__(256) void split_h2_wide_kernel(const float* __restrict__ x, int64_t ldx, int dim, int64_t rows,
                                                             unsigned char* __restrict__ out, const float* __restrict__ inv,
-                                                            int64_t R) {
+                                                            int64_t R, const int* __restrict__ gate) {
   __shared__ __attribute__((aligned(16))) float tile[16][256 + 4];
+  if (gate_closed(gate)) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t row0 = (int64_t)blockIdx.x * 16;
   const int c0 = blockIdx.y * WIDE_CHUNKS;
@@ -372,18 +374,18 @@ int ffn_looseness(const unsigned* rowmax, int nblocks, int64_t M, int64_t rows_p
 size_t h2_bytes(int64_t rows, int64_t K) { return (size_t)((K + 15) / 16) * 2 * (size_t)rows * 32; }
 
 int split_h2_wide(const float* x, int64_t ldx, int64_t rows, int64_t K, void* h2, float* inv_scale, float* row_sumsq,
-                  hipStream_t stream) {
+                  hipStream_t stream, const int* gate) {
   ANYLOC_CHECK_ARG(x && h2 && inv_scale && rows > 0 && K > 0 && ldx >= K, "split_h2_wide: bad arguments");
   ANYLOC_CHECK_ARG(K % 16 == 0 && ldx % 4 == 0 && K < (1ll << 31) && rows < (1ll << 31) && (reinterpret_cast<uintptr_t>(x) & 15) == 0,
                    "split_h2_wide: K must be a multiple of 16, rows 16-byte aligned (K=%lld)", (long long)K);
   ProfScope prof("split_h2_wide", stream, 0.0, 12.0 * rows * K);
-  hipLaunchKernelGGL(row_amax_sq_kernel, dim3((unsigned)rows), dim3(256), 0, stream, x, ldx, K, inv_scale, row_sumsq);
+  hipLaunchKernelGGL(row_amax_sq_kernel, dim3((unsigned)rows), dim3(256), 0, stream, x, ldx, K, inv_scale, row_sumsq, gate);
   ANYLOC_TRY(launch_status("row_amax_sq_kernel"));
   const int chunks = (int)((K + 255) / 256);
   const dim3 grid((unsigned)((rows + 15) / 16), (unsigned)((chunks + WIDE_CHUNKS - 1) / WIDE_CHUNKS));
   ANYLOC_CHECK_ARG(grid.y < 65536, "split_h2_wide: K too large");
   hipLaunchKernelGGL(split_h2_wide_kernel, grid, dim3(256), 0, stream, x, ldx, (int)K, rows, static_cast<unsigned char*>(h2),
-                     inv_scale, rows);
+                     inv_scale, rows, gate);
   return launch_status("split_h2_wide_kernel");
 }
 
@@ -395,7 +397,7 @@ int split_h1_wide(const float* x, int64_t ldx, int64_t rows, int64_t K, void* h2
   ANYLOC_CHECK_ARG(K % 16 == 0 && ldx % 4 == 0 && K < (1ll << 31) && rows < (1ll << 31) && (reinterpret_cast<uintptr_t>(x) & 15) == 0,
                    "split_h1_wide: K must be a multiple of 16, rows 16-byte aligned (K=%lld)", (long long)K);
   ProfScope prof("split_h1_wide", stream, 0.0, 10.0 * rows * K);
-  hipLaunchKernelGGL(row_amax_sq_kernel, dim3((unsigned)rows), dim3(256), 0, stream, x, ldx, K, inv_scale, row_sumsq);
+  hipLaunchKernelGGL(row_amax_sq_kernel, dim3((unsigned)rows), dim3(256), 0, stream, x, ldx, K, inv_scale, row_sumsq, nullptr);
   ANYLOC_TRY(launch_status("row_amax_sq_kernel"));
   const int chunks = (int)((K + 255) / 256);
   const dim3 grid((unsigned)((rows + 15) / 16), (unsigned)((chunks + WIDE_CHUNKS - 1) / WIDE_CHUNKS));
@@ -409,7 +411,7 @@ int row_scales_h2(const float* x, int64_t ldx, int64_t rows, int64_t K, float* i
   ANYLOC_CHECK_ARG(x && inv_scale && rows > 0 && K > 0 && ldx >= K && K % 4 == 0 && ldx % 4 == 0 &&
                        (reinterpret_cast<uintptr_t>(x) & 15) == 0 && rows < (1ll << 31),
                    "row_scales_h2: bad arguments");
-  hipLaunchKernelGGL(row_amax_sq_kernel, dim3((unsigned)rows), dim3(256), 0, stream, x, ldx, K, inv_scale, row_sumsq);
+  hipLaunchKernelGGL(row_amax_sq_kernel, dim3((unsigned)rows), dim3(256), 0, stream, x, ldx, K, inv_scale, row_sumsq, nullptr);
   return launch_status("row_amax_sq_kernel");
 }
 

@@ -314,6 +314,9 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void gemm_h3_kernel(H3Problem p,
   using Cfg = H3Cfg<MI, NI, WM, WN, STAGES, KB>;
   constexpr bool TR = EPI == EPI_SWIGLU_T || EPI == EPI_SWIGLU_T_H2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  if constexpr (EPI == EPI_STORE) {   // the retrieval's gated score panels (H3Problem::gate); no other instantiation asks
+    if (gate_closed(p.gate)) return;
+  }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
   // split-K (p.ksplit > 1, small-M plans of gemm_h3s.hip): workgroup id = split * tiles + tile; split s contracts k-blocks

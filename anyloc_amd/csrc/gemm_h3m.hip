@@ -52,6 +52,7 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void gemm_h3m_kernel(H3Problem p
   constexpr int HM_BM = Cfg::BM, HM_BN = Cfg::BN, HM_KBLK = Cfg::KBLK, HM_STAGE = Cfg::STAGE, A_PLANE = Cfg::A_PLANE,
                 W_PLANE = Cfg::W_PLANE, NW = Cfg::NW;
   extern __shared__ __attribute__((aligned(16))) unsigned char hm_smem[];
+  if (gate_closed(p.gate)) return;                         // EPI_STORE only: the retrieval's gated score panels
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
   int tm, tn;

@@ -143,11 +143,13 @@ __device__ __forceinline__ float screen_value(float s, int64_t c, int metric, fl
 // One workgroup per query: every column of the screened row whose value is within `margin[q]` of the k-th best screened value
 // thr[q * k + k - 1] is a candidate -> cand[q * cmax + i] = column (order arbitrary: the selection ranks by value and index),
 // count[q] = how many there are (may exceed cmax: the caller re-runs the query set unscreened), overflow |= count > cmax.
+// over_q != nullptr (ANYLOC_TOPK_NO_WAIT): over_q[q] = 1 as well -- sticky across the column ranges of a call, which zeroes it once.
 __global__ __launch_bounds__(256) void screen_compact_kernel(const float* __restrict__ scores, int64_t ld, int64_t ncols, int k,
                                                              int metric, const float* __restrict__ qn, const float* __restrict__ dn,
                                                              const float* __restrict__ dnorm, const float* __restrict__ thr,
                                                              const float* __restrict__ margin, int cmax, int* __restrict__ cand,
-                                                             int* __restrict__ count, int* __restrict__ overflow) {
+                                                             int* __restrict__ count, int* __restrict__ overflow,
+                                                             int* __restrict__ over_q) {
   __shared__ int n_s;
   const int tid = threadIdx.x;
   const int64_t q = blockIdx.x;
@@ -166,7 +168,51 @@ __global__ __launch_bounds__(256) void screen_compact_kernel(const float* __rest
   __syncthreads();
   if (tid == 0) {
     count[q] = n_s;
-    if (n_s > cmax) atomicOr(overflow, 1);
+    if (n_s > cmax) {
+      atomicOr(overflow, 1);
+      if (over_q) over_q[q] = 1;
+    }
+  }
+}
+
+// What the host decides from the overflow flag of a waiting call, decided on the device (ANYLOC_TOPK_NO_WAIT): one workgroup reads
+// the per-query marks (thread t: queries [t per, (t + 1) per), so that a block-wide prefix sum of the counts numbers the marked
+// queries in ascending order) and writes plan[] (common.hpp: screen_overflow_plan).  The gates are written last, by one thread.
+constexpr int PLAN_NT = 1024;
+__global__ __launch_bounds__(PLAN_NT) void screen_overflow_plan_kernel(const int* __restrict__ over_q, int64_t nq, int side_cap,
+                                                                       int* __restrict__ plan) {
+  __shared__ int wave_tot[PLAN_NT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t per = (nq + PLAN_NT - 1) / PLAN_NT, q0 = min(nq, (int64_t)tid * per), q1 = min(nq, q0 + per);
+  int n = 0;
+  for (int64_t q = q0; q < q1; ++q) n += over_q[q] != 0;
+  int incl = n;                                            // inclusive prefix sum inside the wave ...
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int up = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += up;
+  }
+  if (lane == 63) wave_tot[wave] = incl;
+  __syncthreads();
+  int before = 0, total = 0;                               // ... plus the waves in front
+#pragma unroll
+  for (int w = 0; w < PLAN_NT / 64; ++w) {
+    if (w < wave) before += wave_tot[w];
+    total += wave_tot[w];
+  }
+  int pos = before + incl - n;
+  for (int64_t q = q0; q < q1; ++q)
+    if (over_q[q] != 0) {
+      if (pos < side_cap) plan[4 + pos] = (int)q;
+      ++pos;
+    }
+  for (int j = tid; j < SCREEN_SIDE_Q; j += PLAN_NT)
+    if (j >= min(total, side_cap)) plan[4 + j] = -1;
+  if (tid == 0) {
+    plan[0] = total;
+    plan[1] = total >= 1 && total <= side_cap;
+    plan[2] = total > side_cap;
+    plan[3] = 0;
   }
 }
 
@@ -512,11 +558,17 @@ int screen_margins(const float* qn, const float* rho_q, const unsigned* rho_max,
 
 int screen_compact(const float* scores, int64_t ld, int64_t ncols, int64_t nq, int k, int metric, const float* qn, const float* dn,
                    const float* dnorm, const float* thr, const float* margin, int cmax, int* cand, int* count, int* overflow,
-                   hipStream_t stream) {
+                   int* over_q, hipStream_t stream) {
   ProfScope prof("topk_screen_compact", stream, 0.0, 4.0 * nq * ncols);
   hipLaunchKernelGGL(screen_compact_kernel, dim3((unsigned)nq), dim3(256), 0, stream, scores, ld, ncols, k, metric, qn, dn, dnorm, thr,
-                     margin, cmax, cand, count, overflow);
+                     margin, cmax, cand, count, overflow, over_q);
   return launch_status("screen_compact_kernel");
+}
+
+int screen_overflow_plan(const int* over_q, int64_t nq, int side_cap, int* plan, hipStream_t stream) {
+  ANYLOC_CHECK_ARG(over_q && plan && nq > 0 && side_cap >= 1 && side_cap <= SCREEN_SIDE_Q, "screen_overflow_plan: bad arguments");
+  hipLaunchKernelGGL(screen_overflow_plan_kernel, dim3(1), dim3(PLAN_NT), 0, stream, over_q, nq, side_cap, plan);
+  return launch_status("screen_overflow_plan_kernel");
 }
 
 bool screen_rescore_supported(int64_t dim) { return dim % 4 == 0 && dim <= 2048 * 24; }

@@ -13,10 +13,11 @@
 //                holds every panel's operand image, row scales, sums of squares and residual norms, for every query count
 // On the fp16 panels the SCREENED search (scores_screen.hip) scores whole column ranges on the leading planes alone and re-scores
 // exactly the rows its error bound cannot rule out; when a query has more of those than SCREEN_CMAX the call falls back to the
-// unscreened panel search, on the query operands it already has.
+// unscreened panel search, on the query operands it already has.  With ANYLOC_TOPK_NO_WAIT that decision is taken on the device
+// (device_fallback): both remedies are enqueued behind gates, and a few overflowed queries are searched as a batch of their own.
 // Where each decision lives: topk_plan -- path, panel height, query chunk, screened column range, few-query arithmetic; the one
 // reader of the topk_* options, asked by carve, the searches, anyloc_topk_path, the index layout and the size functions of the ABI.
-// topk_impl -- validation, the workspace check, whether THIS call screens, the fallback.  prologue -- norms and the queries' operand
+// topk_impl -- validation, the workspace check, whether THIS call screens, the fallback (device_fallback: the same without a wait).  prologue -- norms and the queries' operand
 // images, once per call.  db_panel / score_panel -- a database panel as GEMM operand with its norms / the query-chunk x k-chunk loop
 // on the fp16 planes.  screened_search, panel_search -- the two searches.  launch_* -- the one launch site of each kernel here.
 #include <algorithm>
@@ -38,8 +39,9 @@ __device__ __forceinline__ bool better(float v, long long i, float bv, long long
   return v > bv || (v == bv && i < bi);
 }
 __global__ __launch_bounds__(256) void rownorm_sq_kernel(const float* __restrict__ x, int64_t dim,
-                                                         float* __restrict__ out) {
+                                                         float* __restrict__ out, const int* __restrict__ gate) {
   __shared__ float red[4];
+  if (gate_closed(gate)) return;
   const float* r = x + (int64_t)blockIdx.x * dim;
   float ss = 0.f;
   for (int64_t i = threadIdx.x; i < dim; i += 256) ss += r[i] * r[i];
@@ -113,8 +115,9 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
                                                          const float* __restrict__ qn, const float* __restrict__ dn,
                                                          const float* __restrict__ dnorm,
                                                          float* __restrict__ run_v, long long* __restrict__ run_i,
-                                                         int first) {
+                                                         int first, const int* __restrict__ gate) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  if (gate_closed(gate)) return;
   // slots [0, k): running list, best first; slots [k, k + CAP): buffered candidates
   unsigned long long* key = reinterpret_cast<unsigned long long*>(smem_raw);          // [k2 + CAP], k2 = k rounded up to even
   const int k2 = (k + 1) & ~1;
@@ -217,9 +220,10 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
 
 // raw sums of squares -> dnorm = max(sqrt(ss), 1e-12) (F.normalize's denominator) and, for the L2 metric, the squared
 // norm of the normalised row dn = ss / dnorm^2
-__global__ void dbnorm_kernel(const float* __restrict__ ss, int64_t n, float* __restrict__ dnorm, float* __restrict__ dn) {
+__global__ void dbnorm_kernel(const float* __restrict__ ss, int64_t n, float* __restrict__ dnorm, float* __restrict__ dn,
+                              const int* __restrict__ gate) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
+  if (i >= n || gate_closed(gate)) return;
   const float d = fmaxf(sqrtf(ss[i]), 1e-12f);
   dnorm[i] = d;
   dn[i] = (ss[i] / d) / d;
@@ -256,6 +260,27 @@ __global__ void topk_finish_kernel(float* __restrict__ v, const long long* __res
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   if (metric) v[i] = idx[i] < 0 ? INFINITY : -v[i];
+}
+
+// ANYLOC_TOPK_NO_WAIT, a few overflowed queries (plan[]: common.hpp, screen_overflow_plan).  Gather: workgroup j copies query
+// plan[4 + j] into row j of the side batch, or zeroes the row when there is none.  Scatter: the side batch's list j goes to row
+// plan[4 + j] of the caller's lists.  Both behind plan[1], the gate of the side batch.
+__global__ __launch_bounds__(256) void side_gather_kernel(const float* __restrict__ queries, int64_t dim, const int* __restrict__ plan,
+                                                          float* __restrict__ rows) {
+  if (plan[1] == 0) return;
+  const int q = plan[4 + blockIdx.x];
+  float* dst = rows + (int64_t)blockIdx.x * dim;
+  for (int64_t i = threadIdx.x; i < dim; i += 256) dst[i] = q >= 0 ? queries[(int64_t)q * dim + i] : 0.f;
+}
+__global__ __launch_bounds__(64) void side_scatter_kernel(const float* __restrict__ side_v, const long long* __restrict__ side_i, int k,
+                                                          const int* __restrict__ plan, float* __restrict__ run_v,
+                                                          long long* __restrict__ run_i) {
+  if (plan[1] == 0 || (int)blockIdx.x >= plan[0]) return;
+  const int64_t q = plan[4 + blockIdx.x], j = blockIdx.x;
+  for (int i = threadIdx.x; i < k; i += 64) {
+    run_v[q * k + i] = side_v[j * k + i];
+    run_i[q * k + i] = side_i[j * k + i];
+  }
 }
 
 constexpr int SPLITK_MAX = 16;            // few-query path: K slices of the split-K launch, at most
@@ -328,6 +353,11 @@ struct TopkWs {
   float *sbuf, *scr_v, *margin, *cand_v, *rho_q, *rho_d, *resid;
   long long* scr_i;
   int *cand, *count, *overflow;
+  // ANYLOC_TOPK_NO_WAIT: per-query overflow marks, the device's plan, and the side batch of the overflowed queries -- their rows
+  // and lists; its operand image, scales, norms and score panel are those of the full fallback, which never runs in the same call
+  int *over_q, *plan;
+  float *side_rows, *side_v;
+  long long* side_i;
   float *scores, *qn, *dn, *dss, *dnorm, *part, *rsq_part;
   unsigned char *qimg, *dimg;      // h3 path: operand images of the queries (per chunk of q_chunk rows) and of one panel
   float *qinv, *dinv;              // ... and their row scales
@@ -361,6 +391,13 @@ TopkWs carve(void* ws, size_t cap, const TopkPlan& p) {
   w.rho_d = a.take<float>(sc && !p.indexed ? (size_t)ndb1 : 1);
   w.resid = a.take<float>(sc && !p.indexed ? (size_t)panel : 1);
   w.overflow = a.take<int>(4);                            // [0] overflow flag, [1] bits of the largest database rho, [2] of the largest raw sum of squares
+  // (the size functions take no flags: a screening shape carries the side batch whether or not the call asks for it)
+  const int64_t side = std::min<int64_t>(nq, SCREEN_SIDE_Q);
+  w.over_q = a.take<int>(sc ? (size_t)nq : 0);             // (a shape that does not screen needs the bytes it needed before)
+  w.plan = a.take<int>(sc ? SCREEN_PLAN_INTS : 0);
+  w.side_rows = a.take<float>(sc ? (size_t)side * p.dim : 0);
+  w.side_v = a.take<float>(sc ? (size_t)side * k : 0);
+  w.side_i = a.take<long long>(sc ? (size_t)side * k : 0);
   w.bytes = a.off;
   return w;
 }
@@ -394,7 +431,7 @@ IndexView index_view(void* p, int64_t ndb, int64_t dim) {
 struct TopkCall {
   const float *queries, *db;       // db == nullptr: a prepared index without its fp32 rows
   int metric;
-  bool norm_db, rescore_planes;
+  bool norm_db, rescore_planes, no_wait;
   int64_t index_base;
   float* dist;
   long long* idx;
@@ -402,14 +439,15 @@ struct TopkCall {
   TopkPlan p;
   TopkWs w;
   IndexView iv;                    // of the prepared index, if any
+  const int* gate;                 // nullptr, or the device word that closes every launch of this search (device_fallback)
 };
 
-int launch_rownorm(const float* x, int64_t rows, int64_t dim, float* out, const char* what, hipStream_t stream) {
-  hipLaunchKernelGGL(rownorm_sq_kernel, dim3((unsigned)rows), dim3(256), 0, stream, x, dim, out);
+int launch_rownorm(const float* x, int64_t rows, int64_t dim, float* out, const char* what, hipStream_t stream, const int* gate) {
+  hipLaunchKernelGGL(rownorm_sq_kernel, dim3((unsigned)rows), dim3(256), 0, stream, x, dim, out, gate);
   return launch_status(what);
 }
-int launch_dbnorm(const float* ss, int64_t n, float* dnorm, float* dn, hipStream_t stream) {
-  hipLaunchKernelGGL(dbnorm_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream, ss, n, dnorm, dn);
+int launch_dbnorm(const float* ss, int64_t n, float* dnorm, float* dn, hipStream_t stream, const int* gate) {
+  hipLaunchKernelGGL(dbnorm_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream, ss, n, dnorm, dn, gate);
   return launch_status("dbnorm_kernel");
 }
 // merges score columns [col0, col0 + ncols) into the lists run_v / run_i; no columns: an empty database's padding list, not profiled
@@ -425,7 +463,7 @@ int launch_merge(const TopkCall& c, const float* scores, int64_t ld, int64_t nco
   std::optional<ProfScope> prof;
   if (ncols > 0) prof.emplace("topk_merge", c.stream, 0.0, 4.0 * c.p.nq * ncols);
   hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)c.p.nq), dim3(256), lds, c.stream, scores, ld, ncols, c.index_base + col0,
-                     (int)c.p.k, c.metric, c.w.qn, dn, dnorm, run_v, run_i, first);
+                     (int)c.p.k, c.metric, c.w.qn, dn, dnorm, run_v, run_i, first, c.gate);
   return launch_status("topk_merge_kernel");
 }
 
@@ -453,9 +491,9 @@ int db_panel(const TopkCall& c, int64_t c0, int64_t pc, bool leading_plane, DbPa
   } else {   // the sums of squares are the L2 term as they are, or, normalising, what dnorm / dn are made of
     float* ss = c.norm_db ? w.dss + c0 : c.metric == 1 ? w.dn + c0 : nullptr;
     d = {w.dimg, w.dinv, ss};
-    ANYLOC_TRY(split_h2_wide(c.db + c0 * dim, dim, pc, dim, w.dimg, w.dinv, ss, c.stream));
+    ANYLOC_TRY(split_h2_wide(c.db + c0 * dim, dim, pc, dim, w.dimg, w.dinv, ss, c.stream, c.gate));
   }
-  return c.norm_db ? launch_dbnorm(d.ss, pc, w.dnorm + c0, w.dn + c0, c.stream) : ANYLOC_OK;
+  return c.norm_db ? launch_dbnorm(d.ss, pc, w.dnorm + c0, w.dn + c0, c.stream, c.gate) : ANYLOC_OK;
 }
 
 // scores of all queries against one panel on the fp16 planes -> C[nq, ldc], k-chunk by k-chunk (the later ones add):
@@ -469,7 +507,7 @@ int score_panel(const TopkCall& c, const DbPanel& d, int64_t pc, bool exact, flo
       h.W2 = d.img + kb0 * (2 * pc * 32); h.RW = pc; h.w_inv = d.inv;
       h.C = C + q0 * ldc; h.ldc = ldc;
       h.M = qc; h.N = pc; h.K16 = (int)std::min<int64_t>(KC16, K16 - kb0);
-      h.accumulate = kb0 > 0; h.tag = exact ? "topk_scores_gemm" : "topk_screen_gemm";
+      h.accumulate = kb0 > 0; h.gate = exact ? c.gate : nullptr; h.tag = exact ? "topk_scores_gemm" : "topk_screen_gemm";
       ANYLOC_TRY(exact ? gemm_h3(h, EPI_STORE, c.stream) : gemm_screen(h, c.stream));
     }
     return (int)ANYLOC_OK;
@@ -481,18 +519,18 @@ int score_panel(const TopkCall& c, const DbPanel& d, int64_t pc, bool exact, flo
 int prologue(const TopkCall& c, bool screen) {
   const TopkWs& w = c.w;
   const int64_t nq = c.p.nq, ndb = c.p.ndb, dim = c.p.dim;
-  if (c.metric == 1 || screen) ANYLOC_TRY(launch_rownorm(c.queries, nq, dim, w.qn, "rownorm_sq_kernel(q)", c.stream));
+  if (c.metric == 1 || screen) ANYLOC_TRY(launch_rownorm(c.queries, nq, dim, w.qn, "rownorm_sq_kernel(q)", c.stream, c.gate));
   if ((c.metric == 1 || c.norm_db) && c.p.path == PATH_F32) {
     ProfScope prof("topk_db_norms", c.stream, 2.0 * ndb * dim, 4.0 * ndb * dim);
     float* ss = c.norm_db ? w.dss : w.dn;
     for (int64_t r0 = 0; r0 < ndb; r0 += (1ll << 30))
-      ANYLOC_TRY(launch_rownorm(c.db + r0 * dim, std::min<int64_t>(1ll << 30, ndb - r0), dim, ss + r0, "rownorm_sq_kernel(db)", c.stream));
-    if (c.norm_db && ndb > 0) ANYLOC_TRY(launch_dbnorm(w.dss, ndb, w.dnorm, w.dn, c.stream));
+      ANYLOC_TRY(launch_rownorm(c.db + r0 * dim, std::min<int64_t>(1ll << 30, ndb - r0), dim, ss + r0, "rownorm_sq_kernel(db)", c.stream, c.gate));
+    if (c.norm_db && ndb > 0) ANYLOC_TRY(launch_dbnorm(w.dss, ndb, w.dnorm, w.dn, c.stream, c.gate));
   }
   if (ndb == 0) return ANYLOC_OK;
   if (c.p.path == PATH_H3) {
     ANYLOC_TRY(each_query_chunk(c, [&](int64_t q0, int64_t qc, unsigned char* qimg) {
-      return split_h2_wide(c.queries + q0 * dim, dim, qc, dim, qimg, w.qinv + q0, nullptr, c.stream);
+      return split_h2_wide(c.queries + q0 * dim, dim, qc, dim, qimg, w.qinv + q0, nullptr, c.stream, c.gate);
     }));
   } else if (c.p.path == PATH_FEWQ && c.p.fewq == 2) {   // few queries on fp16 planes: their row scales and, pre-split, their planes
     ANYLOC_TRY(row_scales_h2(c.queries, dim, nq, dim, w.qinv, nullptr, c.stream));
@@ -536,7 +574,7 @@ int panel_search(const TopkCall& c) {
                            (int)nq, w.scores, ss);
         ANYLOC_TRY(launch_status("splitk_combine_kernel"));
       }
-      if (c.norm_db) ANYLOC_TRY(launch_dbnorm(ss, pc, w.dnorm + c0, w.dn + c0, c.stream));
+      if (c.norm_db) ANYLOC_TRY(launch_dbnorm(ss, pc, w.dnorm + c0, w.dn + c0, c.stream, c.gate));
     } else {
       GemmProblem g{};
       g.A = c.queries; g.lda = dim; g.W = c.db + c0 * dim; g.ldw = dim;
@@ -558,6 +596,7 @@ int screened_search(const TopkCall& c) {
   const TopkWs& w = c.w;
   const int64_t nq = c.p.nq, ndb = c.p.ndb, dim = c.p.dim, K16 = dim / 16;
   ANYLOC_HIP(hipMemsetAsync(w.overflow, 0, 3 * sizeof(int), c.stream));
+  if (c.no_wait) ANYLOC_HIP(hipMemsetAsync(w.over_q, 0, (size_t)nq * sizeof(int), c.stream));
   unsigned* rho_max = reinterpret_cast<unsigned*>(w.overflow + 1);
   unsigned* ss_max = reinterpret_cast<unsigned*>(w.overflow + 2);   // bits of the largest raw sum of squares (searches without NORMALIZE_DB)
   // the queries' relative residual norms, from the residual planes of their images
@@ -583,7 +622,7 @@ int screened_search(const TopkCall& c) {
     ANYLOC_TRY(screen_margins(w.qn, w.rho_q, rho_max, c.norm_db ? nullptr : ss_max, nq, c.metric,
                               screen_accum((int)std::min(SCREEN_KC16, K16), (int)cdiv(K16, SCREEN_KC16)), w.margin, c.stream));
     ANYLOC_TRY(screen_compact(w.sbuf, sn, sn, nq, (int)c.p.k, c.metric, w.qn, w.dn + s0, dnorm_s, w.scr_v, w.margin, SCREEN_CMAX, w.cand,
-                              w.count, w.overflow, c.stream));
+                              w.count, w.overflow, c.no_wait ? w.over_q : nullptr, c.stream));
     if (c.rescore_planes)
       ANYLOC_TRY(screen_rescore_planes(c.queries, c.iv.img, c.iv.slot, c.iv.panel, ndb, s0, c.iv.dinv, dim, nq, SCREEN_CMAX, w.cand, w.count,
                                        c.metric, w.qn, w.dn + s0, dnorm_s, w.cand_v, c.stream));
@@ -594,6 +633,33 @@ int screened_search(const TopkCall& c) {
                              reinterpret_cast<int64_t*>(c.idx), s0 == 0, c.stream));
   }
   return ANYLOC_OK;
+}
+
+// ANYLOC_TOPK_NO_WAIT: what topk_impl decides from the overflow flag after a wait, decided on the device.  The host cannot know
+// the outcome, so it enqueues BOTH remedies, every launch of each behind a gate of the plan (a closed launch returns at entry):
+//   plan[1]  1 .. SCREEN_SIDE_Q queries overflowed: they are gathered into a batch of their own (unused rows zero), searched over
+//            the whole database by the unscreened panel search, and their lists scattered over those the screened search left
+//            for them; every other query keeps its screened list
+//   plan[2]  more: the unscreened panel search for all queries, as after the wait
+// The side batch quantises into the query image, scales, norms and score panel of the full search: the gates exclude each other,
+// and the screened search is done with them.
+int device_fallback(const TopkCall& c) {
+  const TopkWs& w = c.w;
+  const int side = (int)std::min<int64_t>(c.p.nq, SCREEN_SIDE_Q);
+  ANYLOC_TRY(screen_overflow_plan(w.over_q, c.p.nq, side, w.plan, c.stream));
+  TopkCall s = c;
+  s.queries = w.side_rows; s.dist = w.side_v; s.idx = w.side_i;
+  s.p.nq = side; s.p.q_chunk = side;
+  s.gate = w.plan + 1;
+  hipLaunchKernelGGL(side_gather_kernel, dim3((unsigned)side), dim3(256), 0, c.stream, c.queries, c.p.dim, w.plan, w.side_rows);
+  ANYLOC_TRY(launch_status("side_gather_kernel"));
+  ANYLOC_TRY(prologue(s, false));
+  ANYLOC_TRY(panel_search(s));
+  hipLaunchKernelGGL(side_scatter_kernel, dim3((unsigned)side), dim3(64), 0, c.stream, w.side_v, w.side_i, (int)c.p.k, w.plan, c.dist, c.idx);
+  ANYLOC_TRY(launch_status("side_scatter_kernel"));
+  TopkCall f = c;
+  f.gate = w.plan + 2;
+  return panel_search(f);
 }
 
 // `index` != nullptr: the database side comes from a prepared index (db may be null)
@@ -608,9 +674,10 @@ int topk_impl(const float* queries, int64_t nq, const float* db, int64_t ndb, in
   ANYLOC_CHECK_ARG(metric == 0 || metric == 1, "topk: metric %d", metric);
   ANYLOC_CHECK_ARG(dim >= 4 && dim % 4 == 0, "topk: dim %lld must be a positive multiple of 4", (long long)dim);
   ANYLOC_CHECK_ARG(nq < (1ll << 31), "topk: too many queries");
-  ANYLOC_CHECK_ARG((flags & ~(ANYLOC_TOPK_NORMALIZE_DB | (indexed ? ANYLOC_TOPK_RESCORE_PLANES : 0u))) == 0, "topk: unknown flags %u", flags);
+  ANYLOC_CHECK_ARG((flags & ~(ANYLOC_TOPK_NORMALIZE_DB | ANYLOC_TOPK_NO_WAIT | (indexed ? ANYLOC_TOPK_RESCORE_PLANES : 0u))) == 0,
+                   "topk: unknown flags %u", flags);
   TopkCall c{queries, db, metric, (flags & ANYLOC_TOPK_NORMALIZE_DB) != 0, indexed && (flags & ANYLOC_TOPK_RESCORE_PLANES) != 0,
-             index_base, dist, reinterpret_cast<long long*>(idx), stream, topk_plan(nq, ndb, dim, k, indexed)};
+             (flags & ANYLOC_TOPK_NO_WAIT) != 0, index_base, dist, reinterpret_cast<long long*>(idx), stream, topk_plan(nq, ndb, dim, k, indexed)};
   c.w = carve(workspace, workspace_bytes, c.p);
   if (!workspace || c.w.bytes > workspace_bytes) {
     set_error("topk: workspace %zu < %zu", workspace_bytes, c.w.bytes);
@@ -621,10 +688,14 @@ int topk_impl(const float* queries, int64_t nq, const float* db, int64_t ndb, in
   const bool screen = c.p.sc_cols > 0 && (db != nullptr || c.rescore_planes) && ndb > 0;
   ANYLOC_TRY(prologue(c, screen));
   int overflow = 0;
-  if (screen) {   // the one wait of a call: the overflow flag decides between finishing and the unscreened search
+  if (screen) {
     ANYLOC_TRY(screened_search(c));
-    ANYLOC_HIP(hipMemcpyAsync(&overflow, c.w.overflow, sizeof(int), hipMemcpyDeviceToHost, stream));
-    ANYLOC_HIP(hipStreamSynchronize(stream));
+    if (c.no_wait) {   // no wait: the device decides (a shape that does not screen never waited)
+      ANYLOC_TRY(device_fallback(c));
+    } else {           // the one wait of a call: the overflow flag decides between finishing and the unscreened search
+      ANYLOC_HIP(hipMemcpyAsync(&overflow, c.w.overflow, sizeof(int), hipMemcpyDeviceToHost, stream));
+      ANYLOC_HIP(hipStreamSynchronize(stream));
+    }
   }
   if (!screen || overflow) ANYLOC_TRY(panel_search(c));
   // padding entries carry index -1 regardless of index_base (faiss); L2 distances are sign-flipped back

@@ -493,11 +493,14 @@ def kmeans_update(sums, counts, centers_old):
 
 TOPK_NORMALIZE_DB = 1
 TOPK_RESCORE_PLANES = 2    # indexed searches only: the screened search re-scores from the planes of the index (no fp32 rows)
+TOPK_NO_WAIT = 4           # the screened search's overflow is handled on the device: the call returns once it is enqueued
 
 
-def topk(queries, db, k, metric="ip", index_base=0, normalize_db=False):
+def topk(queries, db, k, metric="ip", index_base=0, normalize_db=False, no_wait=False):
     """Exact top-k of db rows for every query: (dist [nq,k] f32, idx [nq,k] i64), best first.
-    ``normalize_db``: score against F.normalize(db) without materialising it (ANYLOC_TOPK_NORMALIZE_DB)."""
+    ``normalize_db``: score against F.normalize(db) without materialising it (ANYLOC_TOPK_NORMALIZE_DB).
+    ``no_wait`` (ANYLOC_TOPK_NO_WAIT): a screened search does not wait for its overflow flag -- the device handles the queries
+    that overflow, the call returns as soon as it is enqueued (the results are ready in stream order, as every op's)."""
     _need_cuda(queries, db)
     queries, db = _f32c(queries), _f32c(db)
     if queries.shape[1] % 4:          # the kernels read 16-byte groups: zero columns change neither metric
@@ -513,7 +516,8 @@ def topk(queries, db, k, metric="ip", index_base=0, normalize_db=False):
     ws_bytes = lib.anyloc_topk_workspace_bytes(nq, ndb, dim, k)
     ws = _lib.workspace(ws_bytes, queries.device, "topk")
     _lib.check(lib.anyloc_topk(_lib.ptr(queries), nq, _lib.ptr(db), ndb, dim, k,
-                               0 if metric == "ip" else 1, TOPK_NORMALIZE_DB if normalize_db else 0, index_base,
+                               0 if metric == "ip" else 1,
+                               (TOPK_NORMALIZE_DB if normalize_db else 0) | (TOPK_NO_WAIT if no_wait else 0), index_base,
                                _lib.ptr(dist), _lib.ptr(idx),
                                _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "anyloc_topk")
     return dist, idx
@@ -557,12 +561,13 @@ def topk_index_build_range(index, rows, row0, ndb):
     return index
 
 
-def topk_indexed(queries, index, ndb, k, metric="ip", index_base=0, normalize_db=False, db=None, rescore_planes=False):
+def topk_indexed(queries, index, ndb, k, metric="ip", index_base=0, normalize_db=False, db=None, rescore_planes=False,
+                 no_wait=False):
     """``topk`` against a database prepared by ``topk_index_build`` (same results; the fp32 rows are not read).  ``db``: the
     fp32 rows the index was built from -- with them the screened search (option ``topk_screen``) can re-score its candidates.
     ``rescore_planes`` (ANYLOC_TOPK_RESCORE_PLANES): the screened search re-scores from the planes of the index instead -- it
     runs without ``db`` (and does not read it when given); the lists are the float64-exact ones over the 22-bit rows the index
-    holds."""
+    holds.  ``no_wait``: as in ``topk``."""
     _need_cuda(queries, index)
     queries = _f32c(queries)
     if db is not None:
@@ -579,7 +584,8 @@ def topk_indexed(queries, index, ndb, k, metric="ip", index_base=0, normalize_db
     ws = _lib.workspace(lib.anyloc_topk_index_workspace_bytes(nq, ndb, dim, k), queries.device, "topk")
     _lib.check(lib.anyloc_topk_search_index_rows(_lib.ptr(queries), nq, _lib.ptr(db) if db is not None else None, _lib.ptr(index),
                                                  int(ndb), dim, k, 0 if metric == "ip" else 1,
-                                                 (TOPK_NORMALIZE_DB if normalize_db else 0) | (TOPK_RESCORE_PLANES if rescore_planes else 0),
+                                                 (TOPK_NORMALIZE_DB if normalize_db else 0) | (TOPK_RESCORE_PLANES if rescore_planes else 0) |
+                                                 (TOPK_NO_WAIT if no_wait else 0),
                                                  index_base, _lib.ptr(dist), _lib.ptr(idx),
                                                  _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
                "anyloc_topk_search_index_rows")

@@ -80,8 +80,10 @@ class FlatIndex:
     def has_planes(self):
         return self.planes is not None
 
-    def search(self, qu, k):
-        """(dist, idx) device tensors of the top ``k`` rows for every query (``index.search``)."""
+    def search(self, qu, k, no_wait=False):
+        """(dist, idx) device tensors of the top ``k`` rows for every query (``index.search``).  ``no_wait``
+        (``ops.TOPK_NO_WAIT``): a screened search returns once it is enqueued; queries that overflow it are handled on the
+        device."""
         dev = _lib.require_gpu()
         qu_d = ops._f32c(torch.as_tensor(qu), dev)
         if qu_d.dim() == 1:
@@ -89,11 +91,12 @@ class FlatIndex:
         if self.norm_descs:
             qu_d = ops.l2norm_rows(qu_d)
         metric = "ip" if self.method == "cosine" else "l2"
+        flag = {"no_wait": True} if no_wait else {}       # (asked for only when set: a stand-in for ops.topk need not know it)
         if self.planes is not None and (self.db is None or
                                         _lib.load().anyloc_topk_path(int(qu_d.shape[0]), self.ntotal, self.dim) == 2):
             return ops.topk_indexed(qu_d, self.planes, self.ntotal, int(k), metric, normalize_db=self.norm_descs, db=self.db,
-                                    rescore_planes=self.rescore == "planes")
-        return ops.topk(qu_d, self.db, int(k), metric, normalize_db=self.norm_descs)
+                                    rescore_planes=self.rescore == "planes", **flag)
+        return ops.topk(qu_d, self.db, int(k), metric, normalize_db=self.norm_descs, **flag)
 
     @classmethod
     def from_chunks(cls, chunks, ntotal, dim, method="cosine", norm_descs=True):
@@ -136,12 +139,13 @@ class FlatIndex:
         return self
 
 
-def search(db, qu, k, method="cosine", norm_descs=True):
-    """Normalise (optionally) and search: returns device tensors (dist, idx).  ``db``: the rows, or a ``FlatIndex``."""
+def search(db, qu, k, method="cosine", norm_descs=True, no_wait=False):
+    """Normalise (optionally) and search: returns device tensors (dist, idx).  ``db``: the rows, or a ``FlatIndex``.
+    ``no_wait``: the search does not wait for the device (``ops.topk``)."""
     if isinstance(db, FlatIndex):
         if (db.method, db.norm_descs) != (method, bool(norm_descs)):
             raise ValueError(f"FlatIndex built for ({db.method}, norm_descs={db.norm_descs}), searched with ({method}, {norm_descs})")
-        return db.search(qu, k)
+        return db.search(qu, k, no_wait=no_wait)
     dev = _lib.require_gpu()
     db_d, qu_d = ops._f32c(db, dev), ops._f32c(qu, dev)
     if method == "cosine":
@@ -154,7 +158,8 @@ def search(db, qu, k, method="cosine", norm_descs=True):
         # F.normalize of both sides (reference utilities.py:436-437): the queries are normalised here, the database
         # rows inside the search (their norms come out of the scoring pass; no normalised copy of the database)
         qu_d = ops.l2norm_rows(qu_d)
-    return ops.topk(qu_d, db_d, int(k), metric, normalize_db=bool(norm_descs))
+    # (the keyword is passed only when set: a stand-in for ops.topk, as the CPU oracle of the tests, need not know it)
+    return ops.topk(qu_d, db_d, int(k), metric, normalize_db=bool(norm_descs), **({"no_wait": True} if no_wait else {}))
 
 
 def get_top_k_recall(top_k: List[int], db: torch.Tensor, qu: torch.Tensor, gt_pos: np.ndarray,
@@ -231,7 +236,7 @@ def gather_rows(local, counts, rank, group, comm):
 
 
 def sharded_search(db_shard, shard_base, qu_local, k, method="cosine", norm_descs=True,
-                   group=None, search_fn=None, counts=None, timings=None, overlap="auto"):
+                   group=None, search_fn=None, counts=None, timings=None, overlap="auto", no_wait=False):
     """Database-sharded retrieval, one process per GPU.
 
     Every rank owns ``db_shard`` (rows ``shard_base ...`` of the global database)
@@ -250,7 +255,9 @@ def sharded_search(db_shard, shard_base, qu_local, k, method="cosine", norm_desc
     are searched while the all-gather of the others' is in flight (``async_op``: RCCL runs it on its own stream over xGMI)
     and the rest afterwards -- two searches over the shard instead of one, so it pays only where a second pass costs no
     second quantisation of the database: "auto" = when ``db_shard`` is a ``FlatIndex`` with prepared planes, the shares
-    are equal (one ``all_gather_into_tensor``) and the call is not an instrumented one.  Same lists either way."""
+    are equal (one ``all_gather_into_tensor``) and the call is not an instrumented one.  Same lists either way.
+    ``no_wait``: passed to the searches on the shard (``search``), which then do not stall the host while the all-gather or the
+    next search is waiting to be enqueued; a padded or repeated query costs a few-query search instead of a second whole one."""
     import time
 
     import torch.distributed as dist
@@ -281,7 +288,7 @@ def sharded_search(db_shard, shard_base, qu_local, k, method="cosine", norm_desc
 
     def run_search(q):
         if search_fn is None:
-            dd, ii = search(db_shard, q, k, method, norm_descs)
+            dd, ii = search(db_shard, q, k, method, norm_descs, **({"no_wait": True} if no_wait else {}))
             return dd, torch.where(ii >= 0, ii + shard_base, ii)
         return search_fn(db_shard, q, k, method, norm_descs, shard_base)
     equal = len(set(counts)) == 1 and counts[0] > 0

@@ -22,7 +22,9 @@
  *       anyloc_topk, anyloc_topk_search_index, anyloc_topk_search_index_rows
  *         when the SCREENED search serves the shape (option topk_screen):
  *         one 4-byte flag is read back, the call waits for `stream` (never
- *         for the device) before it finishes or re-runs unscreened;
+ *         for the device) before it finishes or re-runs unscreened -- unless
+ *         flag ANYLOC_TOPK_NO_WAIT is set: then the device decides and the
+ *         call returns as soon as its work is enqueued;
  *       anyloc_vit_attach_h2 (no stream argument, construction time) waits
  *         for the whole DEVICE, quantises the patch weights on the null
  *         stream and waits for that.
@@ -431,7 +433,8 @@ int anyloc_kmeans_update(const float* sums, const float* counts, const float* ce
  *   (HBM-bound); otherwise scores are fp32-MFMA GEMM panels (MFMA-bound).
  *   Streams: where the screened search runs (option topk_screen: by default >= 256 queries x >= 16 384 rows x >= 4096
  *   columns on the fp16 panels) the call synchronises with `stream` once -- it waits for its 4-byte overflow flag
- *   (see anyloc_topk_search_index_rows); every other shape returns without waiting. */
+ *   (see anyloc_topk_search_index_rows); every other shape returns without waiting, and so does every shape with
+ *   ANYLOC_TOPK_NO_WAIT (below). */
 #define ANYLOC_TOPK_NORMALIZE_DB 1u
 size_t anyloc_topk_workspace_bytes(int64_t nq, int64_t ndb, int64_t dim, int64_t k);
 int anyloc_topk(const float* queries, int64_t nq, const float* db, int64_t ndb,
@@ -453,7 +456,7 @@ size_t anyloc_topk_index_bytes(int64_t ndb, int64_t dim);
 int anyloc_topk_index_build(const float* db, int64_t ndb, int64_t dim, void* index, size_t index_bytes, void* stream);
 size_t anyloc_topk_index_workspace_bytes(int64_t nq, int64_t ndb, int64_t dim, int64_t k);
 /* Streams: with ANYLOC_TOPK_RESCORE_PLANES on a screened shape the call waits for `stream` once (the overflow flag of the
- * screened search, below); otherwise it returns without waiting. */
+ * screened search, below) unless ANYLOC_TOPK_NO_WAIT is set too; otherwise it returns without waiting. */
 int anyloc_topk_search_index(const float* queries, int64_t nq, const void* index, int64_t ndb, int64_t dim, int64_t k,
                              int metric, unsigned flags, int64_t index_base, float* dist, int64_t* idx, void* workspace,
                              size_t workspace_bytes, void* stream);
@@ -468,7 +471,8 @@ int anyloc_topk_search_index(const float* queries, int64_t nq, const void* index
  * Lists: the rows of the exact search; distances within 1e-6 of it (more accurate, not bit-identical).  db == NULL: as
  * anyloc_topk_search_index.
  * Streams: that read-back makes a screened call synchronise with `stream` (hipStreamSynchronize, on every screened call):
- * the host waits for everything enqueued on `stream` before the call, other streams are not waited for. */
+ * the host waits for everything enqueued on `stream` before the call, other streams are not waited for.  ANYLOC_TOPK_NO_WAIT
+ * (below) takes the read-back and the wait away. */
 int anyloc_topk_search_index_rows(const float* queries, int64_t nq, const float* db, const void* index, int64_t ndb, int64_t dim,
                                   int64_t k, int metric, unsigned flags, int64_t index_base, float* dist, int64_t* idx,
                                   void* workspace, size_t workspace_bytes, void* stream);
@@ -483,6 +487,20 @@ int anyloc_topk_search_index_rows(const float* queries, int64_t nq, const float*
  *   unscreened search of the same call beyond it, workspace of anyloc_topk_index_workspace_bytes).  anyloc_topk (no index)
  *   rejects the flag with ANYLOC_ERR_INVALID_ARG. */
 #define ANYLOC_TOPK_RESCORE_PLANES 2u
+/* The screened search WITHOUT its wait (additive to ABI 10; an older library answers the flag with ANYLOC_ERR_INVALID_ARG,
+ * "unknown flags").
+ *   flags: ANYLOC_TOPK_NO_WAIT -- all three searches, alone or with the two flags above.  The call makes no blocking runtime call
+ *   and returns as soon as its work is enqueued on `stream`; what the host decides from the read-back is decided on the device,
+ *   per QUERY.  The screened search marks every query that had more than 512 rows inside its bound in some column range.  Up to
+ *   64 marked queries are gathered into a batch of their own, searched unscreened over the whole database, and their lists
+ *   replace the ones the screened search left for them; every other query keeps its screened list, bit for bit what a call
+ *   without those queries gives it.  More than 64: the unscreened search for every query, bit for bit what the waiting call
+ *   does then.  The host cannot know which, so it enqueues both behind gates (device words): a launch whose gate is closed
+ *   returns at entry, and a call without overflow pays for those empty launches -- a few percent.  Lists of marked
+ *   queries are those of the unscreened search of the entry point; nothing else about the results changes, and a call whose
+ *   queries do not overflow returns the bits of the waiting call.  Workspace: the same size functions (they cover the side
+ *   batch for every screening shape).  On a shape that does not screen the flag changes nothing: that call never waited. */
+#define ANYLOC_TOPK_NO_WAIT 4u
 /* An index built piece by piece -- `index.add(chunk)` called repeatedly (utilities.py:441-442 / :446-447), for a database whose
  * fp32 rows never exist in one place (1 M x 49 152 rows are 196.6 GB; rows + index do not fit one device).
  * anyloc_topk_index_panel: rows per panel of the index for `dim` columns (0 where the fp16 panels do not serve `dim`).
