@@ -60,6 +60,19 @@ class H3PlanDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in H3_PLAN_FIELDS] + [("grid", C.c_int64)]
 
 
+GEMM_PLAN_PART_FIELDS = ("tile", "tile_rows", "tile_cols", "bk", "kfull", "rowsq", "abl", "reserved")
+
+
+class GemmPlanPart(C.Structure):
+    """anyloc_gemm_plan_part: one launch of a planned fp32 GEMM call"""
+    _fields_ = [(n, C.c_int64) for n in ("row0", "rows", "grid")] + [(n, C.c_int32) for n in GEMM_PLAN_PART_FIELDS]
+
+
+class GemmPlanDesc(C.Structure):
+    """anyloc_gemm_plan_desc: the answer of the host-only anyloc_gemm_plan_describe"""
+    _fields_ = [("parts", C.c_int32), ("reserved", C.c_int32), ("part", GemmPlanPart * 2)]
+
+
 # name -> (restype, argtypes); also the list the symbol-export test checks
 SIGNATURES = {
     "anyloc_version": (C.c_int, []),
@@ -88,6 +101,7 @@ SIGNATURES = {
     "anyloc_h3_plan_describe": (C.c_int, [c_i64, c_i64, c_i64, C.c_char_p, C.c_int32, C.c_uint32, C.POINTER(H3PlanDesc)]),
     "anyloc_gemm_nt": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_f32p, c_i64,
                                  c_i64, c_i64, c_i64, C.c_void_p]),
+    "anyloc_gemm_plan_describe": (C.c_int, [c_i64, c_i64, c_i64, C.c_char_p, C.c_int32, C.POINTER(GemmPlanDesc)]),
     "anyloc_layernorm": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i64, C.c_float, C.c_void_p]),
     "anyloc_attention": (C.c_int, [c_f32p, c_f32p, c_i64, c_i64, c_i64, c_i64, C.c_void_p]),
     "anyloc_attention_h3_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),

@@ -52,8 +52,21 @@ struct ProfScope {
 bool profiling_enabled();
 
 // ---- tuning options (anyloc_set_option / anyloc_get_option; include/anyloc_hip.h lists the names) ------------------
-// Process-wide integers read by the host-side dispatch code; never read from the environment on a call path: the one
-// environment variable, ANYLOC_OPTIONS="name=value,...", is parsed once when the first option is looked up.
+// Process-wide integers; never read from the environment on a call path: the one environment variable,
+// ANYLOC_OPTIONS="name=value,...", is parsed once when the first option is looked up.
+// Who reads what: an option is read by ONE plan function -- a function that decides how a call runs before its first HIP call --
+// and by no template and no function that launches:
+//   gemm_f32_plan (gemm_f32.hip)               gemm_f32_cfg
+//   x6_plan (gemm_x6.hip)                      x6_cfg
+//   h3_plan and its helpers (gemm_h3s.hip)     h3_cfg, h3_group_m (h3_group_m(): also gemm_screen's), h3_tiny_max, h3_deep_max, h3_deep2_max,
+//                                              h3_epi_lds, h3_fast_silu, h3_mfma16, h3s_*, h3s_ln_lead, h3_ln_lead
+//   ln_h2_plan (gemm_h3.hip)                   ln_rows_per_wave, ln_small_rows, ln_waves, ln_direct_rows
+//   attn_f32_plan / attn_plan (attention.hip)  attn_cfg, attn_x6 / attn_h3_qg, attn_h3_ks, attn_h3_ragged_xcd
+//   fused_plan (vlad_fused.hip)                vlad_fused_v, kmeans_fused_v, vlad_gather_v
+//   the plan helpers of vlad.hip               vlad_parts, vlad_two_pass, kmeans_max_chunks
+//   topk_plan (topk.hip)                       topk_h3, topk_screen, topk_fewq_x6, topk_fewq_qdma
+//   vit_forward_launches' decision block       h3_fuse, x6_fuse, h3_min_rows, x6_min_rows, h3_patch
+//   (h3_swiglu_t is read by the Python host when it builds the weight images)
 enum Option {
   OPT_GEMM_F32_CFG,      // gemm_f32.hip tile configuration (micro-benchmarks); 0 = default
   OPT_X6_CFG,            // gemm_x6.hip tile configuration; 0 = default
@@ -307,9 +320,10 @@ struct H3Problem {
   const float* gamma;                       // EPI_LS_RESID
   const float* resid;                       // EPI_LS_RESID, leading dim ldc
   int accumulate;                           // EPI_STORE: C += A W^T (a long contraction cut into K chunks, one launch each)
-  int fast_silu;                            // EPI_SWIGLU_H2: SiLU on v_exp_f32 / v_rcp_f32 (set by gemm_h3 from option h3_fast_silu)
-  int epi_lds;                              // EPI_LS_RESID: transposed 16-byte epilogue through LDS (set by gemm_h3)
-  int group_m;                              // tile-rows per XCD scheduling group (set by gemm_h3)
+  // the next three are the plan's (H3Plan): the launcher copies them here, whatever the caller left in them
+  int fast_silu;                            // EPI_SWIGLU_H2 / _T / _T_H2: SiLU on v_exp_f32 / v_rcp_f32
+  int epi_lds;                              // EPI_LS_RESID: transposed 16-byte epilogue through LDS
+  int group_m;                              // tile-rows per XCD scheduling group
   // split-K (small-M plans, gemm_h3s.hip): ksplit > 1 cuts the contraction into ksplit ranges of kper k-blocks, one
   // workgroup each; partial accumulators meet in sk_part, the last arrival of a tile (sk_tickets, zero between launches)
   // sums them in split order and runs the epilogue.  Both buffers: h3_split_workspace().
@@ -392,7 +406,13 @@ struct H3Plan {
   int lead;              // LayerNorm lead role (H3Problem::ln_x): 0 = none, 1 = small-M, 2 = batched
   int tiles_m, tiles_n;
   unsigned grid;
+  // what the kernel reads from its argument and the options decide: gemm_h3 copies them into H3Problem's fields of the same names
+  int group_m;           // tile-rows per XCD scheduling group (option h3_group_m)
+  int epi_lds;           // EPI_LS_RESID: 16-byte accesses through LDS (option h3_epi_lds, and C / resid aligned for them)
+  int fast_silu;         // the SwiGLU epilogues that quantise or transpose (option h3_fast_silu)
 };
+// option h3_group_m as every kernel that orders its tiles by XCD groups takes it (gemm_h3_kernel, gemm_h3m_kernel, gemm_screen_kernel)
+int h3_group_m();
 // ln_in_front: the caller has a LayerNorm whose output is this GEMM's operand image and asks whether the launch can carry it
 // as its lead role (plan.lead != 0: set H3Problem::ln_x ...; 0: the caller launches layernorm_h2 itself)
 H3Plan h3_plan(const H3Problem& p, int epilogue, bool ln_in_front);

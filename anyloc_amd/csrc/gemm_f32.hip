@@ -31,6 +31,7 @@
 //     private 4 MiB L2) + grouped ordering so co-resident blocks of one XCD
 //     share A row-panels and W column-panels.
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "common.hpp"
@@ -369,44 +370,28 @@ int launch_cfg(const GemmProblem& p, hipStream_t stream) {
   return launch_status("gemm_nt_kernel");
 }
 
-// tile configuration of the wide (ViT / retrieval) GEMMs; option gemm_f32_cfg selects an
-// alternative at run time (micro-benchmarks only)
-int gemm_cfg() { return (int)option(OPT_GEMM_F32_CFG); }
-
-template <int EPI, bool KFULL>
-int launch_wide(const GemmProblem& p, hipStream_t stream) {
-  switch (gemm_cfg()) {
-    case 1:  // 256x128, 4 waves of 128x64, one block per CU
-      return launch_cfg<256, 128, 2, 2, 32, 1, EPI, false, KFULL>(p, stream);
-    case 2:  // 256x128, 8 waves of 64x64, one block per CU
-      return launch_cfg<256, 128, 4, 2, 32, 2, EPI, false, KFULL>(p, stream);
-    case 3:  // 128x128, BK=16, three blocks per CU
-      return launch_cfg<128, 128, 2, 2, 16, 3, EPI, false, KFULL>(p, stream);
-    case 4:  // 256x256, 8 waves of 128x64 (swiglu-compatible), one block per CU
-      return launch_cfg<256, 256, 2, 4, 16, 2, EPI, false, KFULL>(p, stream);
-    // 5..8: timing-only ablations of the default tile (plain-store epilogue only; results are wrong)
-    case 5:
-    case 6:
-    case 7:
-    case 8:
-      if constexpr (EPI == EPI_STORE && KFULL) {
-        const int c = gemm_cfg();
-        if (c == 5) return launch_cfg<128, 128, 2, 2, 32, 2, EPI, false, KFULL, 1>(p, stream);
-        if (c == 6) return launch_cfg<128, 128, 2, 2, 32, 2, EPI, false, KFULL, 2>(p, stream);
-        if (c == 7) return launch_cfg<128, 128, 2, 2, 32, 2, EPI, false, KFULL, 3>(p, stream);
-        return launch_cfg<128, 128, 2, 2, 32, 2, EPI, false, KFULL, 4>(p, stream);
-      }
-      return launch_cfg<128, 128, 2, 2, 32, 2, EPI, false, KFULL>(p, stream);
-    case 20:  // default tile, LDS-DMA staging
-      if constexpr (KFULL) return launch_cfg<128, 128, 2, 2, 32, 2, EPI, false, KFULL, 64>(p, stream);
-      return launch_cfg<128, 128, 2, 2, 32, 2, EPI, false, KFULL>(p, stream);
-    case 10:  // default tile, loads issued two slabs ahead
-      return launch_cfg<128, 128, 2, 2, 32, 2, EPI, false, KFULL, 8>(p, stream);
-    case 11:  // 256x256 tile (8 waves of 128x64), loads two slabs ahead
-      return launch_cfg<256, 256, 2, 4, 16, 2, EPI, false, KFULL, 8>(p, stream);
-    default:  // 128x128, 4 waves of 64x64, two blocks per CU
-      return launch_cfg<128, 128, 2, 2, 32, 2, EPI, false, KFULL>(p, stream);
-  }
+// ---- host side: the tile shapes a plan (GemmF32Plan) can name ----
+struct F32Tile { int bm, bn, wm, wn, bk, occ; };
+constexpr F32Tile kF32Tile[] = {
+    {128, 128, 2, 2, 32, 2},   // 0: 4 waves of 64x64, two blocks per CU (default)
+    {256, 128, 2, 2, 32, 1},   // 1: 4 waves of 128x64, one block per CU
+    {256, 128, 4, 2, 32, 2},   // 2: 8 waves of 64x64, one block per CU
+    {128, 128, 2, 2, 16, 3},   // 3: BK=16, three blocks per CU
+    {256, 256, 2, 4, 16, 2},   // 4: 8 waves of 128x64 (swiglu-compatible), one block per CU
+    {64, 128, 2, 2, 32, 2},    // 5: 4 waves of 32x64: the 64-row part of a row split
+    {128, 32, 4, 1, 32, 2},    // 6: N <= 32
+    {128, 64, 4, 1, 32, 2},    // 7: gemm_nt_splitk
+};
+constexpr int F32_TILE_HALF = 5, F32_TILE_NARROW = 6, F32_TILE_SPLITK = 7;
+// The kernels that exist: a plan that names anything else is an error at launch.  The 64-row part has no EPI_PATCH kernel: that
+// epilogue derives the output row from the row inside the launch, so a launch cannot start at a row other than 0.
+constexpr bool f32_compiled(int epi, int tile, bool rowsq, bool kfull, int abl) {
+  if (tile == F32_TILE_NARROW) return epi == EPI_STORE && !kfull && abl == 0;
+  if (tile == F32_TILE_SPLITK) return epi == EPI_STORE && rowsq && kfull && abl == 0;
+  if (rowsq) return epi == EPI_STORE && tile == 0 && !kfull && abl == 0;
+  if (tile == F32_TILE_HALF) return epi != EPI_PATCH && kfull && abl == 0;
+  if (tile == 0) return abl == 0 || abl == 8 || (kfull && (abl == 64 || (epi == EPI_STORE && (abl == 32 || (abl >= 1 && abl <= 4)))));
+  return abl == 0 || (tile == 4 && abl == 8);
 }
 
 // Row split of a GEMM into a 128-row-tile part [0, m1) and a 64-row-tile part [m1, M).
@@ -439,24 +424,77 @@ int64_t plan_row_split(int64_t M, int64_t N) {
   return best < 0.96 * rounds_cost(tm * tn, 1.0) ? best_m1 : M;
 }
 
-template <int EPI>
-int launch_wide_k(const GemmProblem& p, hipStream_t stream) {
-  if (gemm_cfg() != 0 || p.K % 32 != 0 || EPI == EPI_PATCH)
-    return (p.K % 32 == 0) ? launch_wide<EPI, true>(p, stream) : launch_wide<EPI, false>(p, stream);
+// How one call runs: one launch, or two that cut the rows.  gemm_f32_plan is the one place that decides it, from the problem,
+// the epilogue and option gemm_f32_cfg (micro-benchmarks only; 0 = default), without a HIP call.
+struct GemmF32Part {
+  int64_t row0, rows;    // rows [row0, row0 + rows) of A, C and resid
+  int tile;              // id in kF32Tile
+  bool kfull, rowsq;
+  int abl;
+};
+struct GemmF32Plan {
+  int nparts;
+  GemmF32Part part[2];
+};
+
+GemmF32Plan gemm_f32_plan(const GemmProblem& p, int epilogue) {
+  const int cfg = (int)option(OPT_GEMM_F32_CFG);
+  const bool k32 = p.K % 32 == 0, rowsq = p.rowsq != nullptr;
+  auto whole = [&](int tile, bool kfull, bool rs, int abl) { return GemmF32Plan{1, {{0, p.M, tile, kfull, rs, abl}, {}}}; };
+  if (epilogue == EPI_STORE) {
+    if (p.N <= 32) return whole(F32_TILE_NARROW, false, rowsq, 0);
+    if (rowsq) return whole(0, false, true, 0);
+    if (p.K >= 8192 && k32 && cfg == 0) return whole(0, true, false, 32);      // long contraction: chunked summation
+  }
+  // no row split under a cfg, with a K tail, for the patch epilogue -- nor for the narrow / row-sum calls that only a plain store has
+  // kernels for (no caller asks them of another epilogue)
+  if (cfg != 0 || !k32 || epilogue == EPI_PATCH || p.N <= 32 || rowsq) {
+    switch (cfg) {
+      case 1: case 2: case 3: case 4: return whole(cfg, k32, false, 0);
+      // 5..8: timing-only ablations of the default tile (plain-store epilogue only; results are wrong)
+      case 5: case 6: case 7: case 8: return whole(0, k32, false, epilogue == EPI_STORE && k32 ? cfg - 4 : 0);
+      case 20: return whole(0, k32, false, k32 ? 64 : 0);                       // default tile, LDS-DMA staging
+      case 10: return whole(0, k32, false, 8);                                  // default tile, loads issued two slabs ahead
+      case 11: return whole(4, k32, false, 8);                                  // 256x256 tile, loads two slabs ahead
+      default: return whole(0, k32, false, 0);
+    }
+  }
   const int64_t m1 = plan_row_split(p.M, p.N);
-  if (m1 > 0) {
-    GemmProblem a = p;
-    a.M = m1;
-    ANYLOC_TRY((launch_cfg<128, 128, 2, 2, 32, 2, EPI, false, true>(a, stream)));
-  }
-  if (m1 < p.M) {
-    GemmProblem b = p;                      // rows [m1, M) on 64x128 tiles (2x2 waves of 32x64)
-    b.M = p.M - m1;
-    b.A = p.A + m1 * p.lda;
-    b.C = p.C + m1 * p.ldc;
-    if (p.resid) b.resid = p.resid + m1 * p.ldc;
-    ANYLOC_TRY((launch_cfg<64, 128, 2, 2, 32, 2, EPI, false, true>(b, stream)));
-  }
+  if (m1 == p.M) return whole(0, true, false, 0);
+  if (m1 == 0) return whole(F32_TILE_HALF, true, false, 0);
+  return GemmF32Plan{2, {{0, m1, 0, true, false, 0}, {m1, p.M - m1, F32_TILE_HALF, true, false, 0}}};
+}
+
+// the one dispatch onto launch_cfg: the kernel a part names, on the part's rows
+template <int EPI>
+int launch_part(const GemmProblem& p, const GemmF32Part& k, hipStream_t stream) {
+  GemmProblem q = p;
+  q.M = k.rows;
+  q.A += k.row0 * p.lda;
+  q.C += k.row0 * p.ldc;
+  if (p.resid) q.resid += k.row0 * p.ldc;
+  return with_constant<0, 1, 2, 3, 4, 5, 6, 7>(k.tile, [&](auto id) {
+    return with_constant<0, 1>((int)k.rowsq, [&](auto rs) {
+      return with_constant<0, 1>((int)k.kfull, [&](auto kf) {
+        return with_constant<0, 1, 2, 3, 4, 8, 32, 64>(k.abl, [&](auto ab) -> int {
+          constexpr F32Tile T = kF32Tile[decltype(id)::value];
+          constexpr bool ROWSQ = decltype(rs)::value != 0, KFULL = decltype(kf)::value != 0;
+          if constexpr (f32_compiled(EPI, decltype(id)::value, ROWSQ, KFULL, decltype(ab)::value)) {
+            return launch_cfg<T.bm, T.bn, T.wm, T.wn, T.bk, T.occ, EPI, ROWSQ, KFULL, decltype(ab)::value>(q, stream);
+          } else {
+            set_error("gemm_nt: no kernel for epilogue %d on tile %d (rowsq %d, kfull %d, abl %d)", EPI, k.tile, k.rowsq, k.kfull, k.abl);
+            return ANYLOC_ERR_INVALID_ARG;
+          }
+        });
+      });
+    });
+  });
+}
+
+int run_plan(const GemmProblem& p, int epilogue, const GemmF32Plan& pl, hipStream_t stream) {
+  for (int i = 0; i < pl.nparts; ++i)
+    ANYLOC_TRY((with_constant<EPI_STORE, EPI_GELU, EPI_LS_RESID, EPI_SWIGLU, EPI_PATCH>(
+        epilogue, [&](auto e) { return launch_part<decltype(e)::value>(p, pl.part[i], stream); })));
   return ANYLOC_OK;
 }
 
@@ -469,7 +507,7 @@ int gemm_nt_splitk(const GemmProblem& p, hipStream_t stream) {
   ANYLOC_CHECK_ARG(p.lda % 4 == 0 && p.ldw % 4 == 0 && (reinterpret_cast<uintptr_t>(p.A) & 15) == 0 &&
                        (reinterpret_cast<uintptr_t>(p.W) & 15) == 0,
                    "gemm_nt_splitk: operands must be 16-byte aligned with row strides that are multiples of 4");
-  return launch_cfg<128, 64, 4, 1, 32, 2, EPI_STORE, true, true>(p, stream);
+  return run_plan(p, EPI_STORE, GemmF32Plan{1, {{0, p.M, F32_TILE_SPLITK, true, true, 0}, {}}}, stream);
 }
 
 int gemm_nt(const GemmProblem& p, int epilogue, hipStream_t stream) {
@@ -482,35 +520,42 @@ int gemm_nt(const GemmProblem& p, int epilogue, hipStream_t stream) {
   ANYLOC_CHECK_ARG((reinterpret_cast<uintptr_t>(p.A) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.W) & 15) == 0,
                    "gemm_nt: operands must be 16-byte aligned");
   ANYLOC_CHECK_ARG((p.M + 127) / 128 * ((p.N + 31) / 32) < (1ll << 31), "gemm_nt: grid too large");
-  const bool narrow = p.N <= 32;
-  switch (epilogue) {
-    case EPI_STORE:
-      if (narrow) {
-        return p.rowsq ? launch_cfg<128, 32, 4, 1, 32, 2, EPI_STORE, true, false>(p, stream)
-                       : launch_cfg<128, 32, 4, 1, 32, 2, EPI_STORE, false, false>(p, stream);
-      }
-      if (p.rowsq) return launch_cfg<128, 128, 2, 2, 32, 2, EPI_STORE, true, false>(p, stream);
-      if (p.K >= 8192 && p.K % 32 == 0 && gemm_cfg() == 0)      // long contraction: chunked summation
-        return launch_cfg<128, 128, 2, 2, 32, 2, EPI_STORE, false, true, 32>(p, stream);
-      return launch_wide_k<EPI_STORE>(p, stream);
-    case EPI_GELU:
-      return launch_wide_k<EPI_GELU>(p, stream);
-    case EPI_LS_RESID:
-      ANYLOC_CHECK_ARG(p.gamma && p.resid, "gemm_nt: LS_RESID needs gamma and resid");
-      return launch_wide_k<EPI_LS_RESID>(p, stream);
-    case EPI_SWIGLU:
-      ANYLOC_CHECK_ARG(p.N % 64 == 0, "gemm_nt: SWIGLU needs N %% 64 == 0");
-      return launch_wide_k<EPI_SWIGLU>(p, stream);
-    case EPI_PATCH:
-      ANYLOC_CHECK_ARG(p.pos && p.patches > 0, "gemm_nt: PATCH needs pos and patches");
-      return launch_wide_k<EPI_PATCH>(p, stream);
-    default:
-      set_error("gemm_nt: unknown epilogue %d", epilogue);
-      return ANYLOC_ERR_INVALID_ARG;
-  }
+  ANYLOC_CHECK_ARG(epilogue >= EPI_STORE && epilogue <= EPI_PATCH, "gemm_nt: unknown epilogue %d", epilogue);
+  ANYLOC_CHECK_ARG(epilogue != EPI_LS_RESID || (p.gamma && p.resid), "gemm_nt: LS_RESID needs gamma and resid");
+  ANYLOC_CHECK_ARG(epilogue != EPI_SWIGLU || p.N % 64 == 0, "gemm_nt: SWIGLU needs N %% 64 == 0");
+  ANYLOC_CHECK_ARG(epilogue != EPI_PATCH || (p.pos && p.patches > 0), "gemm_nt: PATCH needs pos and patches");
+  return run_plan(p, epilogue, gemm_f32_plan(p, epilogue), stream);
 }
 
 }  // namespace anyloc
+
+// host-only: the fields of a GemmProblem that gemm_f32_plan reads, gemm_f32_plan, and the plan with its tiles' shapes -- nothing else
+extern "C" int anyloc_gemm_plan_describe(int64_t M, int64_t N, int64_t K, const char* epilogue, int32_t rowsq,
+                                         anyloc_gemm_plan_desc* out) {
+  using namespace anyloc;
+  static const char* const names[] = {"store", "gelu", "ls_resid", "swiglu", "patch"};
+  static_assert(EPI_STORE == 0 && EPI_GELU == 1 && EPI_LS_RESID == 2 && EPI_SWIGLU == 3 && EPI_PATCH == 4, "names[] is indexed by the epilogue");
+  ANYLOC_CHECK_ARG(out && epilogue, "gemm_plan_describe: null pointer");
+  ANYLOC_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 4 == 0, "gemm_plan_describe: bad shape %lld x %lld x %lld", (long long)M, (long long)N,
+                   (long long)K);
+  int epi = -1;
+  for (int i = 0; i < 5; ++i)
+    if (std::strcmp(epilogue, names[i]) == 0) epi = i;
+  ANYLOC_CHECK_ARG(epi >= 0, "gemm_plan_describe: unknown epilogue \"%s\"", epilogue);
+  static float rowsq_at_hand;                // gemm_f32_plan asks whether the row sums are wanted, never where they go
+  GemmProblem p{};
+  p.M = M; p.N = N; p.K = K;
+  if (rowsq) p.rowsq = &rowsq_at_hand;
+  const GemmF32Plan pl = gemm_f32_plan(p, epi);
+  *out = anyloc_gemm_plan_desc{};
+  out->parts = pl.nparts;
+  for (int i = 0; i < pl.nparts; ++i) {
+    const GemmF32Part& k = pl.part[i];
+    const F32Tile t = kF32Tile[k.tile];
+    out->part[i] = {k.row0, k.rows, cdiv(k.rows, t.bm) * cdiv(N, t.bn), k.tile, t.bm, t.bn, t.bk, k.kfull, k.rowsq, k.abl, 0};
+  }
+  return ANYLOC_OK;
+}
 
 extern "C" int anyloc_gemm_nt(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* C,
                               int64_t ldc, int64_t M, int64_t N, int64_t K, void* stream) {

@@ -433,48 +433,68 @@ int split_h2(const float* x, int64_t ldx, int64_t rows, int64_t K, void* h2, flo
   return launch_status("split_h2_kernel");
 }
 
+namespace {
+// How one LayerNorm runs; ln_h2_plan is the one place that decides it, from the shape and the four ln_* options, without a HIP call.
+struct LnH2Plan {
+  bool direct;           // layernorm_h2_direct_kernel | layernorm_h2_kernel
+  int nv, rpw, nw;       // float4 per lane and row; rows per wave, waves per block (tiled kernel)
+  unsigned grid, block;
+  const char* what;      // the kernel's name for launch_status
+};
+LnH2Plan ln_h2_plan(int64_t rows, int dim) {
+  LnH2Plan pl{};
+  pl.nv = (dim / 4 + 63) / 64;
+  // Option ln_rows_per_wave (0 = the rules below) forces 1, 2 or 4 rows per wave of the tiled kernel at every size (A/B; same
+  // per-row arithmetic, same bits)
+  const int64_t forced = option(OPT_LN_ROWS_PER_WAVE);
+  pl.direct = forced == 0 && rows < option(OPT_LN_DIRECT_ROWS);
+  if (pl.direct) {
+    // a few hundred rows: one single-wave workgroup per row, image written straight from registers
+    pl.rpw = pl.nw = 1;
+    pl.what = "layernorm_h2_direct_kernel";
+  } else {
+    // few rows (option ln_small_rows, default 4096 = seven 322 x 322 images): one row per wave, four per block; otherwise two
+    // rows per wave (48 instead of 96 data registers: more waves in flight; B=61: 6.48 -> 5.65 ms per step, four rows per wave
+    // was the round-2 kernel, one row per wave at this size 11.4 ms -- profiles/r03_ab_attn_kbatch_ln_rpw.log)
+    pl.rpw = (forced == 1 || forced == 2 || forced == 4) ? (int)forced : (rows < option(OPT_LN_SMALL_ROWS) ? 1 : 2);
+    // two rows per wave: EIGHT waves per block (option ln_waves = 8, default) -- 16 rows per block, i.e. 512-byte runs per store
+    // instruction instead of the 256-byte runs of four waves, at the register count of two rows per wave (B = 61: 5.65 -> 5.55 ms
+    // per step; four rows per wave on four waves: 6.4, one row per wave: 11.1, sixteen waves = 32 rows per block: 6.2 -- a bare
+    // copy in this pattern takes 80 us per call against LayerNorm's 87-89: tools/micro/ln_store_pattern.hip)
+    pl.nw = (pl.rpw == 2 && option(OPT_LN_WAVES) == 8) ? 8 : 4;
+    pl.what = "layernorm_h2_kernel";
+  }
+  pl.grid = (unsigned)cdiv(rows, pl.nw * pl.rpw);
+  pl.block = 64u * pl.nw;
+  return pl;
+}
+}  // namespace
+
 int layernorm_h2(const float* x, const float* w, const float* b, int64_t rows, int dim, float eps, void* h2,
                  float* inv_scale, hipStream_t stream, const float* bound, float* bound_inv) {
   ANYLOC_CHECK_ARG(dim % 16 == 0 && dim <= 2048, "layernorm_h2: dim %d (needs a multiple of 16, at most 2048)", dim);
   ProfScope prof("layernorm_h2", stream, 8.0 * rows * dim, 8.0 * rows * dim);
   unsigned char* out = static_cast<unsigned char*>(h2);
-  const int nv = (dim / 4 + 63) / 64;
   f32x4 b4;                                                  // bound: HOST array of 4 floats (or null)
   for (int i = 0; i < 4; ++i) b4[i] = bound ? bound[i] : 0.0f;
-  // few rows (option ln_small_rows, default 4096 = seven 322 x 322 images): one row per wave, four per block; otherwise two
-  // rows per wave (48 instead of 96 data registers: more waves in flight; B=61: 6.48 -> 5.65 ms per step, four rows per wave
-  // was the round-2 kernel, one row per wave at this size 11.4 ms -- profiles/r03_ab_attn_kbatch_ln_rpw.log).  Option
-  // ln_rows_per_wave (0 = that rule) forces 1, 2 or 4 at every size (A/B; same per-row arithmetic, same bits)
-  const int64_t forced = option(OPT_LN_ROWS_PER_WAVE);
-  if (forced == 0 && rows < option(OPT_LN_DIRECT_ROWS)) {
-    // a few hundred rows: one single-wave workgroup per row, image written straight from registers
-    const dim3 grid((unsigned)rows);
-    with_constant<1, 2, 3, 4, 6, 8>(nv, [&](auto c) {
-      hipLaunchKernelGGL((layernorm_h2_direct_kernel<decltype(c)::value>), grid, dim3(64), 0, stream, x, w, b, dim, rows, eps, out,
+  const LnH2Plan pl = ln_h2_plan(rows, dim);
+  with_constant<1, 2, 3, 4, 6, 8>(pl.nv, [&](auto c) {
+    constexpr int NV = decltype(c)::value;
+    if (pl.direct) {
+      hipLaunchKernelGGL((layernorm_h2_direct_kernel<NV>), dim3(pl.grid), dim3(pl.block), 0, stream, x, w, b, dim, rows, eps, out,
                          inv_scale, rows, b4, bound ? bound_inv : nullptr);
+      return;
+    }
+    with_constant<1, 2, 4>(pl.rpw, [&](auto r) {
+      with_constant<4, 8>(pl.nw, [&](auto n) {
+        constexpr int RPW = decltype(r)::value, NW = decltype(n)::value;
+        if constexpr (NW == 4 || RPW == 2)                   // (eight waves: at two rows per wave only)
+          hipLaunchKernelGGL((layernorm_h2_kernel<NV, RPW, NW>), dim3(pl.grid), dim3(pl.block), 0, stream, x, w, b, dim, rows, eps, out,
+                             inv_scale, rows, b4, bound ? bound_inv : nullptr);
+      });
     });
-    return launch_status("layernorm_h2_direct_kernel");
-  }
-  const int rpw = (forced == 1 || forced == 2 || forced == 4) ? (int)forced : (rows < option(OPT_LN_SMALL_ROWS) ? 1 : 2);
-  // two rows per wave: EIGHT waves per block (option ln_waves = 8, default) -- 16 rows per block, i.e. 512-byte runs per store
-  // instruction instead of the 256-byte runs of four waves, at the register count of two rows per wave (B = 61: 5.65 -> 5.55 ms
-  // per step; four rows per wave on four waves: 6.4, one row per wave: 11.1, sixteen waves = 32 rows per block: 6.2 -- a bare
-  // copy in this pattern takes 80 us per call against LayerNorm's 87-89: tools/micro/ln_store_pattern.hip)
-  const int nw = (rpw == 2 && option(OPT_LN_WAVES) == 8) ? 8 : 4;
-  const dim3 grid((unsigned)((rows + nw * rpw - 1) / (nw * rpw)));
-  with_constant<1, 2, 3, 4, 6, 8>(nv, [&](auto c) {
-    auto launch = [&](auto r, auto n) {
-      constexpr int NV = decltype(c)::value, RPW = decltype(r)::value, NW = decltype(n)::value;
-      hipLaunchKernelGGL((layernorm_h2_kernel<NV, RPW, NW>), grid, dim3(64 * NW), 0, stream, x, w, b, dim, rows, eps, out, inv_scale,
-                         rows, b4, bound ? bound_inv : nullptr);
-    };
-    using std::integral_constant;
-    if (rpw == 1) launch(integral_constant<int, 1>{}, integral_constant<int, 4>{});
-    else if (rpw == 2 && nw == 8) launch(integral_constant<int, 2>{}, integral_constant<int, 8>{});
-    else if (rpw == 2) launch(integral_constant<int, 2>{}, integral_constant<int, 4>{});
-    else launch(integral_constant<int, 4>{}, integral_constant<int, 4>{});
   });
-  return launch_status("layernorm_h2_kernel");
+  return launch_status(pl.what);
 }
 
 // ---- LayerNorm lead role inside a batched launch (gemm_h3_kernel<..., LNL = 2>; tile_order.hpp: LeadPlan) ----
@@ -563,9 +583,7 @@ int gemm_h3(const H3Problem& p_in, int epilogue, hipStream_t stream, const H3Pla
                    "gemm_h3: LayerNorm lead role asked for a launch that cannot carry it (h3_plan: lead)");
   const int64_t K = 16ll * p.K16;
   ProfScope prof(p.tag ? p.tag : "gemm_h3", stream, 2.0 * p.M * p.N * K, 4.0 * (p.M + p.N) * K + 4.0 * p.M * p.N);
-  // tile-rows per scheduling group (co-resident workgroups of an XCD share A / W panels through its L2): option
-  // h3_group_m, default 8
-  p.group_m = (int)std::max<int64_t>(1, option(OPT_H3_GROUP_M));
+  p.group_m = pl.group_m; p.epi_lds = pl.epi_lds; p.fast_silu = pl.fast_silu;       // what the kernel reads of the plan
   if (pl.mfma16) {
     const int rc = gemm_h3m(p, epilogue, stream);
     if (rc != ANYLOC_ERR_UNSUPPORTED) return rc;
@@ -578,14 +596,9 @@ int gemm_h3(const H3Problem& p_in, int epilogue, hipStream_t stream, const H3Pla
     case EPI_PATCH:
       ANYLOC_CHECK_ARG(p.pos && p.patches > 0 && p.M % p.patches == 0, "gemm_h3: PATCH needs pos and M = batch * patches");
       return launch_planned<EPI_PATCH>(p, pl, stream);
-    case EPI_LS_RESID: {
+    case EPI_LS_RESID:
       ANYLOC_CHECK_ARG(p.gamma && p.resid, "gemm_h3: LS_RESID needs gamma and resid");
-      H3Problem q = p;
-      // option h3_epi_lds = 0: the dword read-modify-write epilogue (also the fallback for unaligned C)
-      q.epi_lds = option(OPT_H3_EPI_LDS) != 0 && p.N % 4 == 0 && p.ldc % 4 == 0 &&
-                  (reinterpret_cast<uintptr_t>(p.C) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.resid) & 15) == 0;
-      return launch_planned<EPI_LS_RESID>(q, pl, stream);
-    }
+      return launch_planned<EPI_LS_RESID>(p, pl, stream);
     case EPI_SWIGLU:
       ANYLOC_CHECK_ARG(p.N % 64 == 0, "gemm_h3: SWIGLU needs N %% 64 == 0");
       return launch_planned<EPI_SWIGLU>(p, pl, stream);
@@ -606,7 +619,6 @@ int gemm_h3(const H3Problem& p_in, int epilogue, hipStream_t stream, const H3Pla
       return launch_planned<EPI_GELU_H2>(p, pl, stream);
     case EPI_SWIGLU_H2:
       ANYLOC_CHECK_ARG(p.C2 && p.c_inv && p.RC >= p.M && p.N % 128 == 0, "gemm_h3: SWIGLU_H2 needs an output image, c_inv and N %% 128 == 0");
-      p.fast_silu = option(OPT_H3_FAST_SILU) != 0;
       return launch_planned<EPI_SWIGLU_H2>(p, pl, stream);
     case EPI_SWIGLU_T:
     case EPI_SWIGLU_T_H2:
@@ -617,7 +629,6 @@ int gemm_h3(const H3Problem& p_in, int epilogue, hipStream_t stream, const H3Pla
         ANYLOC_CHECK_ARG(p.C2 && p.c_inv && p.RC >= p.M, "gemm_h3: SWIGLU_T_H2 needs an output image and c_inv");
       else
         ANYLOC_CHECK_ARG(p.C && p.ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0, "gemm_h3: SWIGLU_T needs an aligned fp32 output");
-      p.fast_silu = option(OPT_H3_FAST_SILU) != 0;
       return epilogue == EPI_SWIGLU_T ? launch_planned<EPI_SWIGLU_T>(p, pl, stream) : launch_planned<EPI_SWIGLU_T_H2>(p, pl, stream);
     default: set_error("gemm_h3: unsupported epilogue %d", epilogue); return ANYLOC_ERR_INVALID_ARG;
   }

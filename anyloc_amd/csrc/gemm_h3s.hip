@@ -92,10 +92,18 @@ int launch_small(const H3Problem& p, const H3Plan& pl, hipStream_t stream) {
 
 }  // namespace
 
+// tile-rows per scheduling group (co-resident workgroups of an XCD share A / W panels through its L2): option h3_group_m, default 8
+int h3_group_m() { return (int)std::max<int64_t>(1, option(OPT_H3_GROUP_M)); }
+
 H3Plan h3_plan(const H3Problem& p, int epilogue, bool ln_in_front) {
   epilogue = plan_epilogue(epilogue);
   H3Plan pl{};
   pl.kb = 1; pl.ksplit = 1; pl.kper = p.K16;
+  pl.group_m = h3_group_m();
+  // option h3_epi_lds = 0: the dword read-modify-write epilogue (also the fallback for unaligned C)
+  pl.epi_lds = epilogue == EPI_LS_RESID && option(OPT_H3_EPI_LDS) != 0 && p.N % 4 == 0 && p.ldc % 4 == 0 &&
+               (reinterpret_cast<uintptr_t>(p.C) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.resid) & 15) == 0;
+  pl.fast_silu = (epilogue == EPI_SWIGLU_H2 || epilogue == EPI_SWIGLU_T || epilogue == EPI_SWIGLU_T_H2) && option(OPT_H3_FAST_SILU) != 0;
   // option h3_cfg (micro-benchmarks): 0 = 128x256 tile, 3-deep ring (default; the small-M plans when there are few tiles);
   // 1 - 5: kH3Tile, at every size
   const int cfg = (int)option(OPT_H3_CFG);
@@ -148,7 +156,7 @@ H3Plan h3_plan(const H3Problem& p, int epilogue, bool ln_in_front) {
     pl.grid += (unsigned)((cdiv(p.M, t.nw()) + 7) / 8 * 8);
   } else if (pl.route == H3_ROUTE_BATCHED && cfg == 0 && option(OPT_H3_LN_LEAD) != 0 && batched_lead_compiled(epilogue) &&
              16 * (int64_t)p.K16 <= 1536 && p.ksplit <= 1 &&
-             h3_lead_plan_check(pl.tiles_m, pl.tiles_n, (int)std::max<int64_t>(1, option(OPT_H3_GROUP_M)), p.M, &lead_grid)) {
+             h3_lead_plan_check(pl.tiles_m, pl.tiles_n, pl.group_m, p.M, &lead_grid)) {
     pl.lead = 2;
     pl.grid = lead_grid;
   }

@@ -211,39 +211,77 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void gemm_x6_kernel(X6Problem p,
   }
 }
 
-template <int MI, int NI, int WM, int WN, int STAGES, int OCC, int EPI, int SCHED = 0, bool OUT3 = false>
-int launch_x6(const X6Problem& p, hipStream_t stream) {
+// ---- host side: the tile shapes a plan (X6Plan) can name ----
+struct X6Tile { int mi, ni, wm, wn, stages, occ; };
+constexpr X6Tile kX6Tile[] = {
+    {2, 4, 2, 2, 2, 2},      // 0: 128x256, 4 waves, 2-deep ring, two blocks per CU (default)
+    {2, 2, 2, 2, 3, 2},      // 1: 128x128, 3-deep
+    {4, 2, 2, 2, 3, 1},      // 2: 256x128, 3-deep, one block per CU
+    {4, 2, 2, 2, 2, 2},      // 3: 256x128, 2-deep
+    {4, 2, 2, 4, 2, 1},      // 4: 256x256, 8 waves, one block per CU
+    {2, 4, 4, 2, 2, 1},      // 5: the same, the waves stacked along M
+};
+// the kernels that exist.  sched (the refill schedule): 0 = refills issued in one burst, 1 = interleaved with the MFMAs, 2 = A/B
+constexpr bool x6_compiled(int epi, int tile, int sched, bool out3) {
+  if (out3) return (epi == EPI_GELU || epi == EPI_SWIGLU) && sched == 1 && tile <= 1;
+  return sched == 0 ? tile <= 3 : sched == 1 ? tile != 2 : tile == 0;
+}
+
+// How one GEMM runs; x6_plan is the one place that decides it, from the problem and option x6_cfg, without a HIP call.
+struct X6Plan {
+  int tile, sched;       // id in kX6Tile, refill schedule
+  bool out3;             // the result leaves as a plane image (X6Problem::C3)
+  int tiles_m, tiles_n;
+};
+X6Plan x6_plan(const X6Problem& p, int epilogue) {
+  // option x6_cfg (micro-benchmarks) -> (tile, sched); 0 = default.  A plane-image output has the default's two kernels only
+  static constexpr int kCfg[10][2] = {{0, 1}, {1, 0}, {2, 0}, {3, 0}, {0, 0}, {1, 1}, {3, 1}, {4, 1}, {5, 1}, {0, 2}};
+  X6Plan pl{};
+  pl.out3 = p.C3 != nullptr && (epilogue == EPI_GELU || epilogue == EPI_SWIGLU);
+  const int64_t cfg = pl.out3 ? 0 : option(OPT_X6_CFG);
+  if (cfg >= 1 && cfg <= 9) {
+    pl.tile = kCfg[cfg][0];
+    pl.sched = kCfg[cfg][1];
+  } else {
+    // few tiles (small batches): 128x128 tiles double the number of workgroups
+    pl.tile = cdiv(p.M, 128) * cdiv(p.N, 256) < 512 ? 1 : 0;
+    pl.sched = 1;
+  }
+  const X6Tile t = kX6Tile[pl.tile];
+  pl.tiles_m = (int)cdiv(p.M, 32 * t.mi * t.wm);
+  pl.tiles_n = (int)cdiv(p.N, 32 * t.ni * t.wn);
+  return pl;
+}
+
+template <int MI, int NI, int WM, int WN, int STAGES, int OCC, int EPI, int SCHED, bool OUT3>
+int launch_x6(const X6Problem& p, const X6Plan& pl, hipStream_t stream) {
   using Cfg = X6Cfg<MI, NI, WM, WN, STAGES>;
-  const int tiles_m = (int)((p.M + Cfg::BM - 1) / Cfg::BM), tiles_n = (int)((p.N + Cfg::BN - 1) / Cfg::BN);
   static DynLds dyn_lds_once;
   ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(&gemm_x6_kernel<MI, NI, WM, WN, STAGES, OCC, EPI, SCHED, OUT3>), (int)(Cfg::LDS)));
-  hipLaunchKernelGGL((gemm_x6_kernel<MI, NI, WM, WN, STAGES, OCC, EPI, SCHED, OUT3>), dim3((unsigned)(tiles_m * tiles_n)), dim3(64 * WM * WN),
-                     Cfg::LDS, stream, p, tiles_m, tiles_n);
+  hipLaunchKernelGGL((gemm_x6_kernel<MI, NI, WM, WN, STAGES, OCC, EPI, SCHED, OUT3>), dim3((unsigned)(pl.tiles_m * pl.tiles_n)),
+                     dim3(64 * WM * WN), Cfg::LDS, stream, p, pl.tiles_m, pl.tiles_n);
   return launch_status("gemm_x6_kernel");
 }
 
-template <int EPI>
-int dispatch_x6(const X6Problem& p, hipStream_t stream) {
-  // few tiles (small batches): 128x128 tiles double the number of workgroups
-  const bool small = ((p.M + 127) / 128) * ((p.N + 255) / 256) < 512;
-  if constexpr (EPI == EPI_GELU || EPI == EPI_SWIGLU)
-    if (p.C3) return small ? launch_x6<2, 2, 2, 2, 3, 2, EPI, 1, true>(p, stream)
-                           : launch_x6<2, 4, 2, 2, 2, 2, EPI, 1, true>(p, stream);
-  // option x6_cfg (micro-benchmarks): 0 = 128x256 tile, 4 waves, 2-deep ring, two blocks per CU (default);
-  //   1 = 128x128 3-deep; 2 = 256x128 3-deep (1 block/CU); 3 = 256x128 2-deep; 7 / 8 = 256x256 with 8 waves
-  switch ((int)option(OPT_X6_CFG)) {
-    case 1: return launch_x6<2, 2, 2, 2, 3, 2, EPI>(p, stream);
-    case 2: return launch_x6<4, 2, 2, 2, 3, 1, EPI>(p, stream);
-    case 3: return launch_x6<4, 2, 2, 2, 2, 2, EPI>(p, stream);
-    case 4: return launch_x6<2, 4, 2, 2, 2, 2, EPI, 0>(p, stream);   // default tile, refills issued in one burst
-    case 5: return launch_x6<2, 2, 2, 2, 3, 2, EPI, 1>(p, stream);
-    case 6: return launch_x6<4, 2, 2, 2, 2, 2, EPI, 1>(p, stream);
-    case 7: return launch_x6<4, 2, 2, 4, 2, 1, EPI, 1>(p, stream);   // 256x256 tile, 8 waves, one block per CU
-    case 8: return launch_x6<2, 4, 4, 2, 2, 1, EPI, 1>(p, stream);
-    case 9: return launch_x6<2, 4, 2, 2, 2, 2, EPI, 2>(p, stream);
-    default:                                                         // 128x256, refills interleaved with the MFMAs
-      return small ? launch_x6<2, 2, 2, 2, 3, 2, EPI, 1>(p, stream) : launch_x6<2, 4, 2, 2, 2, 2, EPI, 1>(p, stream);
-  }
+// the one dispatch onto launch_x6
+int run_x6(const X6Problem& p, int epilogue, const X6Plan& pl, hipStream_t stream) {
+  return with_constant<EPI_STORE, EPI_GELU, EPI_LS_RESID, EPI_SWIGLU>(epilogue, [&](auto e) {
+    return with_constant<0, 1, 2, 3, 4, 5>(pl.tile, [&](auto id) {
+      return with_constant<0, 1, 2>(pl.sched, [&](auto sc) {
+        return with_constant<0, 1>((int)pl.out3, [&](auto o3) -> int {
+          constexpr int EPI = decltype(e)::value, SCHED = decltype(sc)::value;
+          constexpr X6Tile T = kX6Tile[decltype(id)::value];
+          constexpr bool OUT3 = decltype(o3)::value != 0;
+          if constexpr (x6_compiled(EPI, decltype(id)::value, SCHED, OUT3)) {
+            return launch_x6<T.mi, T.ni, T.wm, T.wn, T.stages, T.occ, EPI, SCHED, OUT3>(p, pl, stream);
+          } else {
+            set_error("gemm_x6: no kernel for epilogue %d on tile %d (sched %d, out3 %d)", EPI, pl.tile, pl.sched, (int)pl.out3);
+            return ANYLOC_ERR_INVALID_ARG;
+          }
+        });
+      });
+    });
+  });
 }
 
 // ---- fp32 row-major -> x3 planes ------------------------------------------------------------------------
@@ -376,15 +414,9 @@ int layernorm_x3(const float* x, const float* w, const float* b, int64_t rows, i
   const dim3 grid((unsigned)((rows + 15) / 16));
   unsigned char* out = static_cast<unsigned char*>(x3);
   const int nv = (dim / 4 + 63) / 64;
-  switch (nv) {
-    case 1: hipLaunchKernelGGL(layernorm_x3_kernel<1>, grid, dim3(256), 0, stream, x, w, b, dim, rows, eps, out, rows); break;
-    case 2: hipLaunchKernelGGL(layernorm_x3_kernel<2>, grid, dim3(256), 0, stream, x, w, b, dim, rows, eps, out, rows); break;
-    case 3: hipLaunchKernelGGL(layernorm_x3_kernel<3>, grid, dim3(256), 0, stream, x, w, b, dim, rows, eps, out, rows); break;
-    case 4: hipLaunchKernelGGL(layernorm_x3_kernel<4>, grid, dim3(256), 0, stream, x, w, b, dim, rows, eps, out, rows); break;
-    case 5: hipLaunchKernelGGL(layernorm_x3_kernel<5>, grid, dim3(256), 0, stream, x, w, b, dim, rows, eps, out, rows); break;
-    case 6: hipLaunchKernelGGL(layernorm_x3_kernel<6>, grid, dim3(256), 0, stream, x, w, b, dim, rows, eps, out, rows); break;
-    default: hipLaunchKernelGGL(layernorm_x3_kernel<8>, grid, dim3(256), 0, stream, x, w, b, dim, rows, eps, out, rows); break;
-  }
+  with_constant<1, 2, 3, 4, 5, 6, 8>(nv, [&](auto c) {
+    hipLaunchKernelGGL(layernorm_x3_kernel<decltype(c)::value>, grid, dim3(256), 0, stream, x, w, b, dim, rows, eps, out, rows);
+  });
   return launch_status("layernorm_x3_kernel");
 }
 
@@ -411,17 +443,10 @@ int gemm_x6(const X6Problem& p, int epilogue, hipStream_t stream) {
                    "gemm_x6: operand image exceeds the 2 GiB buffer-addressing range");
   const int64_t K = 16ll * p.K16;
   ProfScope prof(p.tag ? p.tag : "gemm_x6", stream, 2.0 * p.M * p.N * K, 6.0 * (p.M + p.N) * K + 4.0 * p.M * p.N);
-  switch (epilogue) {
-    case EPI_STORE: return dispatch_x6<EPI_STORE>(p, stream);
-    case EPI_GELU: return dispatch_x6<EPI_GELU>(p, stream);
-    case EPI_LS_RESID:
-      ANYLOC_CHECK_ARG(p.gamma && p.resid, "gemm_x6: LS_RESID needs gamma and resid");
-      return dispatch_x6<EPI_LS_RESID>(p, stream);
-    case EPI_SWIGLU:
-      ANYLOC_CHECK_ARG(p.N % 64 == 0, "gemm_x6: SWIGLU needs N %% 64 == 0");
-      return dispatch_x6<EPI_SWIGLU>(p, stream);
-    default: set_error("gemm_x6: unsupported epilogue %d", epilogue); return ANYLOC_ERR_INVALID_ARG;
-  }
+  ANYLOC_CHECK_ARG(epilogue >= EPI_STORE && epilogue <= EPI_SWIGLU, "gemm_x6: unsupported epilogue %d", epilogue);
+  ANYLOC_CHECK_ARG(epilogue != EPI_LS_RESID || (p.gamma && p.resid), "gemm_x6: LS_RESID needs gamma and resid");
+  ANYLOC_CHECK_ARG(epilogue != EPI_SWIGLU || p.N % 64 == 0, "gemm_x6: SWIGLU needs N %% 64 == 0");
+  return run_x6(p, epilogue, x6_plan(p, epilogue), stream);
 }
 
 }  // namespace anyloc

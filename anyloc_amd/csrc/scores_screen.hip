@@ -530,7 +530,7 @@ int gemm_screen(const H3Problem& p_in, hipStream_t stream) {
   ANYLOC_CHECK_ARG((size_t)p.K16 * 2 * (size_t)p.RA * 32 < (1ull << 31) && (size_t)p.K16 * 2 * (size_t)p.RW * 32 < (1ull << 31),
                    "gemm_screen: operand image exceeds the 2 GiB buffer-addressing range");
   ProfScope prof(p.tag ? p.tag : "gemm_screen", stream, 2.0 * p.M * p.N * 16.0 * p.K16, 2.0 * (p.M + p.N) * 16.0 * p.K16 + 4.0 * p.M * p.N);
-  p.group_m = (int)std::max<int64_t>(1, option(OPT_H3_GROUP_M));
+  p.group_m = h3_group_m();
   const int tiles_m = (int)((p.M + SC_BM - 1) / SC_BM), tiles_n = (int)((p.N + SC_BN - 1) / SC_BN);
   static DynLds dyn_lds_once;
   ANYLOC_TRY(ensure_dyn_lds(dyn_lds_once, reinterpret_cast<const void*>(&gemm_screen_kernel), SC_LDS));

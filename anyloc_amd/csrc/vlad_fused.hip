@@ -1120,24 +1120,9 @@ int launch_units(FusedKernel kern, DynLds& dyn, int block, size_t lds, const cha
   return launch_status(what);
 }
 
-template <int NV, int SW, bool KMEANS, int GV = 0>
+template <int NV, int SW, bool KMEANS, int GV>
 int launch_fused3(const FusedArgs& a, int64_t units, hipStream_t stream) {
   constexpr int D = NV * 128;
-  if constexpr (NV == 12 && SW == 8 && !KMEANS && GV == 0) {
-    switch ((int)option(OPT_VLAD_GATHER_V)) {                 // hazard study (tools/stress_vlad.py): see fused3_kernel
-      case 1: return launch_fused3<NV, SW, KMEANS, 1>(a, units, stream);
-      case 2: return launch_fused3<NV, SW, KMEANS, 2>(a, units, stream);
-      case 3: return launch_fused3<NV, SW, KMEANS, 3>(a, units, stream);
-      case 4: return launch_fused3<NV, SW, KMEANS, 4>(a, units, stream);
-      case 5: return launch_fused3<NV, SW, KMEANS, 5>(a, units, stream);
-      case 7: return launch_fused3<NV, SW, KMEANS, 7>(a, units, stream);
-      case 8: return launch_fused3<NV, SW, KMEANS, 8>(a, units, stream);
-      case 9: return launch_fused3<NV, SW, KMEANS, 9>(a, units, stream);
-      case 10: return launch_fused3<NV, SW, KMEANS, 10>(a, units, stream);
-      case 11: return launch_fused3<NV, SW, KMEANS, 11>(a, units, stream);
-      default: break;
-    }
-  }
   static DynLds dyn_lds_once;
   return launch_units(fused3_kernel<NV, SW, KMEANS, GV>, dyn_lds_once, 64 * SW,
                       sizeof(float) * (TT * (D + 4) + SW * TT * 32 + SW * TT + TT + TT + TT + SW * 32 + 4 + TT * 32),
@@ -1154,17 +1139,26 @@ int launch_fused(const FusedArgs& a, int64_t units, hipStream_t stream) {
                       units, stream);
 }
 
-// options kmeans_fused_v / vlad_fused_v (A/B, tests): 0 (default) = fused3_kernel -- 8 waves where D / 128 is even, 4 waves
+// Which kernel a call runs; fused_plan is the one place that decides it, from the width, the mode and the options, without a HIP
+// call.  Options kmeans_fused_v / vlad_fused_v (A/B, tests): 0 (default) = fused3_kernel -- 8 waves where D / 128 is even, 4 waves
 // otherwise -- at every parts count (round 4: with the CW-wide hand-off 0.135 vs 0.154 ms at 61 images x 4 parts);
-// 1 = vlad_fused_kernel (both modes), 3 = fused3 with 4 waves, 4 = fused3 with 8
-template <int NV>
-int launch_version(const FusedArgs& a, int64_t units, bool kmeans, hipStream_t stream) {
+// 1 = vlad_fused_kernel (both modes), 3 = fused3 with 4 waves, 4 = fused3 with 8.  Option vlad_gather_v: the gather variants of
+// the hazard study (tools/stress_vlad.py; see fused3_kernel), compiled for VLAD at D = 1536 on 8 waves only
+struct FusedPlan {
+  bool fused3;           // fused3_kernel | vlad_fused_kernel
+  int sw, gv;            // fused3_kernel: waves, gather variant
+};
+constexpr bool fused3_compiled(int nv, int sw, bool kmeans, int gv) {
+  return (sw == 4 || nv % 2 == 0) && (gv == 0 || (nv == 12 && sw == 8 && !kmeans));
+}
+FusedPlan fused_plan(int D, bool kmeans) {
   const int ver = (int)option(kmeans ? OPT_KMEANS_FUSED_V : OPT_VLAD_FUSED_V);
-  if (ver != 0 && ver < 3) return kmeans ? launch_fused<NV, true>(a, units, stream) : launch_fused<NV, false>(a, units, stream);
-  if constexpr (NV % 2 == 0) {
-    if (ver != 3) return kmeans ? launch_fused3<NV, 8, true>(a, units, stream) : launch_fused3<NV, 8, false>(a, units, stream);
-  }
-  return kmeans ? launch_fused3<NV, 4, true>(a, units, stream) : launch_fused3<NV, 4, false>(a, units, stream);
+  FusedPlan pl{};
+  pl.fused3 = ver == 0 || ver >= 3;
+  pl.sw = (D / 128) % 2 == 0 && ver != 3 ? 8 : 4;
+  const int64_t gv = pl.fused3 && fused3_compiled(D / 128, pl.sw, kmeans, 1) ? option(OPT_VLAD_GATHER_V) : 0;
+  pl.gv = (gv >= 1 && gv <= 11 && gv != 6) ? (int)gv : 0;
+  return pl;
 }
 
 }  // namespace
@@ -1176,15 +1170,28 @@ bool fused_supported(int64_t D, int64_t K) {
 int vlad_fused(const FusedArgs& a, int64_t units, bool kmeans, hipStream_t stream) {
   if (units <= 0) return ANYLOC_OK;
   ANYLOC_CHECK_ARG(units < (1ll << 31), "vlad_fused: too many units");
-  switch (a.D) {
-    case 384: return launch_version<3>(a, units, kmeans, stream);
-    case 768: return launch_version<6>(a, units, kmeans, stream);
-    case 1024: return launch_version<8>(a, units, kmeans, stream);
-    case 1536: return launch_version<12>(a, units, kmeans, stream);
-    default:
-      set_error("vlad_fused: unsupported D=%d", a.D);
-      return ANYLOC_ERR_UNSUPPORTED;
+  if (!fused_supported(a.D, 1)) {
+    set_error("vlad_fused: unsupported D=%d", a.D);
+    return ANYLOC_ERR_UNSUPPORTED;
   }
+  const FusedPlan pl = fused_plan(a.D, kmeans);
+  return with_constant<3, 6, 8, 12>(a.D / 128, [&](auto nv) {
+    return with_constant<0, 1>((int)kmeans, [&](auto km) {
+      constexpr int NV = decltype(nv)::value;
+      constexpr bool KMEANS = decltype(km)::value != 0;
+      if (!pl.fused3) return launch_fused<NV, KMEANS>(a, units, stream);
+      return with_constant<4, 8>(pl.sw, [&](auto sw) {
+        return with_constant<0, 1, 2, 3, 4, 5, 7, 8, 9, 10, 11>(pl.gv, [&](auto gv) -> int {
+          if constexpr (fused3_compiled(NV, decltype(sw)::value, KMEANS, decltype(gv)::value)) {
+            return launch_fused3<NV, decltype(sw)::value, KMEANS, decltype(gv)::value>(a, units, stream);
+          } else {
+            set_error("vlad_fused: no kernel for D=%d on %d waves (gather variant %d)", a.D, pl.sw, pl.gv);
+            return ANYLOC_ERR_INVALID_ARG;
+          }
+        });
+      });
+    });
+  });
 }
 
 }  // namespace anyloc

@@ -302,6 +302,28 @@ int anyloc_gemm_nt_f64(const double* A, int64_t a_rs, int64_t a_cs,
 int anyloc_gemm_nt(const float* A, int64_t lda, const float* W, int64_t ldw,
                    const float* bias, float* C, int64_t ldc,
                    int64_t M, int64_t N, int64_t K, void* stream);
+/* Additive to ABI 10 (diagnostic, host only -- no device is touched): how ONE call of the fp32 MFMA GEMM would run.  The library's
+ * plan function (csrc/gemm_f32.hip: gemm_f32_plan) decides from the shape, the epilogue and option gemm_f32_cfg whether the call
+ * is one launch or two that cut the rows (a part on 128-row tiles, the rest on 64-row tiles), and which compiled kernel each part
+ * runs; this call builds the problem fields that function reads, calls it, and returns its answer with the tile's shape.
+ *   M, N, K    C [M, N] = A [M, K] W [N, K]^T, K a multiple of 4
+ *   epilogue   "store" "gelu" "ls_resid" "swiglu" "patch"
+ *   rowsq      != 0: the call also asks for the row sums of squares of A
+ *   out (host) parts = 1 or 2; part[i]: rows [row0, row0 + rows) on tile_rows x tile_cols tiles with K slabs of bk; kfull = the
+ *              kernel without a K-tail predicate (K % bk == 0); rowsq = the kernel that also sums the rows' squares; abl = the
+ *              kernel variant (0 plain, 8 loads two slabs ahead, 32 chunked summation, 64 LDS-DMA staging, 1 - 4 timing-only
+ *              ablations); grid = workgroups of the part's launch
+ * Returns ANYLOC_ERR_INVALID_ARG for an unknown epilogue name, a null pointer, sizes that are not positive and K % 4 != 0. */
+typedef struct anyloc_gemm_plan_part {
+  int64_t row0, rows, grid;
+  int32_t tile, tile_rows, tile_cols, bk, kfull, rowsq, abl, reserved;      /* tile = id of the compiled shape (csrc/gemm_f32.hip: kF32Tile) */
+} anyloc_gemm_plan_part;
+typedef struct anyloc_gemm_plan_desc {
+  int32_t parts, reserved;
+  anyloc_gemm_plan_part part[2];
+} anyloc_gemm_plan_desc;
+int anyloc_gemm_plan_describe(int64_t M, int64_t N, int64_t K, const char* epilogue, int32_t rowsq,
+                              anyloc_gemm_plan_desc* out /*host*/);
 
 /* Building blocks of the ViT forward, exposed for unit tests:
  * LayerNorm over the last dim (eps as given; DINOv2 uses 1e-6) and multi-head

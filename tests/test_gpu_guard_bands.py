@@ -1125,7 +1125,7 @@ EXEMPT = {
     # profiling (host buffers only)
     "anyloc_profile_enable", "anyloc_profile_filter", "anyloc_profile_reset", "anyloc_profile_dump",
     # host-only plan and size calls: no device is touched
-    "anyloc_h3_lead_plan_check", "anyloc_h3_plan_describe", "anyloc_topk_path", "anyloc_topk_index_panel",
+    "anyloc_h3_lead_plan_check", "anyloc_h3_plan_describe", "anyloc_gemm_plan_describe", "anyloc_topk_path", "anyloc_topk_index_panel",
     "anyloc_vlad_auto_parts", "anyloc_x3_bytes", "anyloc_h2_bytes", "anyloc_topk_index_bytes",
     # construction and per-handle switches: they store pointers or host state (anyloc_vit_attach_h2 writes memory the
     # library allocated itself)
