@@ -64,7 +64,7 @@ bool profiling_enabled();
 //   attn_f32_plan / attn_plan (attention.hip)  attn_cfg, attn_x6 / attn_h3_qg, attn_h3_ks, attn_h3_ragged_xcd
 //   fused_plan (vlad_fused.hip)                vlad_fused_v, kmeans_fused_v, vlad_gather_v
 //   the plan helpers of vlad.hip               vlad_parts, vlad_two_pass, kmeans_max_chunks
-//   topk_plan (topk.hip)                       topk_h3, topk_screen, topk_fewq_x6, topk_fewq_qdma
+//   topk_plan (topk.hip)                       topk_h3, topk_screen, topk_rescore_cols, topk_fewq_x6, topk_fewq_qdma
 //   vit_forward_launches' decision block       h3_fuse, x6_fuse, h3_min_rows, x6_min_rows, h3_patch
 //   (h3_swiglu_t is read by the Python host when it builds the weight images)
 enum Option {
@@ -114,6 +114,8 @@ enum Option {
   OPT_VLAD_GATHER_V,     // one-pass VLAD kernel at D = 1536: variants of the register-indexed gather kept for the hazard study (0 = shipped)
   OPT_TOPK_SCREEN,       // many-query retrieval: score panels on the leading fp16 planes + exact re-scoring of the rows inside the bound (scores_screen.hip): -1 = where it pays, 0 = never, 1 = wherever possible
   OPT_ATTN_H3_RAGGED_XCD, // ragged attention_h3: 1 = (image, head) units dealt round-robin over the XCDs, 0 = the uniform kernel's contiguous ranges
+  OPT_TOPK_RESCORE_COLS, // screened retrieval: columns per slice of the re-scoring kernels: 0 = 49 152 (rows up to that width in one slice, on the
+                         // single-slice kernels), or a multiple of 4096 up to 49 152, which sends every width through the sliced kernels (tests)
   OPT_COUNT
 };
 int64_t option(Option o);
@@ -440,14 +442,18 @@ int screen_compact(const float* scores, int64_t ld, int64_t ncols, int64_t nq, i
 constexpr int SCREEN_SIDE_Q = 64;
 constexpr int SCREEN_PLAN_INTS = 4 + SCREEN_SIDE_Q;
 int screen_overflow_plan(const int* over_q, int64_t nq, int side_cap, int* plan, hipStream_t stream);
+// re-scoring: `slice` = 0: the whole row in one slice, the query in registers (dim <= SCREEN_RESCORE_COLS); otherwise the columns
+// per slice of the sliced kernels, a multiple of 4096 up to SCREEN_RESCORE_COLS (any dim; cmax <= SCREEN_CMAX)
+constexpr int SCREEN_CMAX = 512;          // candidates per query and column range; more: the call re-runs unscreened
+constexpr int64_t SCREEN_RESCORE_COLS = 2048 * 24;
 bool screen_rescore_supported(int64_t dim);
-int screen_rescore(const float* queries, const float* db, int64_t dim, int64_t nq, int cmax, const int* cand, const int* count,
-                   int metric, const float* qn, const float* dn, const float* dnorm, float* cand_v, hipStream_t stream);
+int screen_rescore(const float* queries, const float* db, int64_t dim, int64_t slice, int64_t nq, int cmax, const int* cand,
+                   const int* count, int metric, const float* qn, const float* dn, const float* dnorm, float* cand_v, hipStream_t stream);
 // the same from the two planes of a prepared index (img + p * slot: the image of panel p; dinv: the 2^-e of ALL rows; the
 // candidates are columns of the range that starts at database row s0; dn / dnorm already point at that range)
 int screen_rescore_planes(const float* queries, const unsigned char* img, size_t slot, int64_t panel, int64_t ndb, int64_t s0,
-                          const float* dinv, int64_t dim, int64_t nq, int cmax, const int* cand, const int* count, int metric,
-                          const float* qn, const float* dn, const float* dnorm, float* cand_v, hipStream_t stream);
+                          const float* dinv, int64_t dim, int64_t slice, int64_t nq, int cmax, const int* cand, const int* count,
+                          int metric, const float* qn, const float* dn, const float* dnorm, float* cand_v, hipStream_t stream);
 int screen_select(const int* cand, const float* cand_v, const int* count, int cmax, int64_t col_base, int64_t nq, int k, float* run_v,
                   int64_t* run_i, int first, hipStream_t stream);
 

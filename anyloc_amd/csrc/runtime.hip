@@ -52,6 +52,7 @@ const OptDef kOptDefs[OPT_COUNT] = {
     {"h3s_cfg", -1}, {"h3s_ksplit", 0}, {"h3s_kb", 0}, {"h3s_stages", 0}, {"h3s_mask", 31}, {"h3s_enable", 1}, {"h3_patch", 1}, {"topk_fewq_qdma", 1},
     {"h3s_w12_tall", 1},      {"attn_h3_qg", 1},     {"attn_h3_ks", 0},
     {"h3s_ln_lead", 0},       {"h3_ln_lead", 0},       {"vlad_gather_v", 0},    {"topk_screen", -1},     {"attn_h3_ragged_xcd", 1},
+    {"topk_rescore_cols", 0},
 };
 std::mutex g_opt_mu;
 int64_t g_opt[OPT_COUNT];
@@ -61,6 +62,12 @@ int find_option(const char* name, size_t len) {
   for (int i = 0; i < OPT_COUNT; ++i)
     if (strlen(kOptDefs[i].name) == len && strncmp(kOptDefs[i].name, name, len) == 0) return i;
   return -1;
+}
+
+// the values an option refuses (anyloc_set_option: ANYLOC_ERR_ARG; ANYLOC_OPTIONS: reported and ignored); most take any integer
+bool option_value_ok(int id, int64_t v) {
+  if (id == OPT_TOPK_RESCORE_COLS) return v >= 0 && v % 4096 == 0 && v <= SCREEN_RESCORE_COLS;
+  return true;
 }
 
 // defaults, then ANYLOC_OPTIONS="name=value,name=value" (the library's only environment variable; unknown names and
@@ -75,7 +82,7 @@ void init_options() {
     const size_t len = end ? (size_t)(end - e) : strlen(e);
     const char* eq = static_cast<const char*>(memchr(e, '=', len));
     const int id = eq ? find_option(e, (size_t)(eq - e)) : -1;
-    if (id >= 0) g_opt[id] = strtoll(eq + 1, nullptr, 0);
+    if (id >= 0 && option_value_ok(id, strtoll(eq + 1, nullptr, 0))) g_opt[id] = strtoll(eq + 1, nullptr, 0);
     else if (len) fprintf(stderr, "[anyloc] ANYLOC_OPTIONS: ignoring '%.*s'\n", (int)len, e);
     e = end ? end + 1 : nullptr;
   }
@@ -129,6 +136,7 @@ int anyloc_set_option(const char* name, int64_t value) {
   init_options();
   const int id = find_option(name, strlen(name));
   ANYLOC_CHECK_ARG(id >= 0, "set_option: unknown option '%s'", name);
+  ANYLOC_CHECK_ARG(option_value_ok(id, value), "set_option: %s = %lld is not a value of this option", name, (long long)value);
   g_opt[id] = value;
   return ANYLOC_OK;
 }

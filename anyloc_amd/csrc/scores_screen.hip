@@ -21,7 +21,8 @@
 // Kernels: gemm_screen_kernel (256 x 256 tiles, 8 waves, v_mfma_f32_16x16x32_f16, leading planes only, 4-deep DMA ring of
 // 32-k stages), screen_compact_kernel (threshold filter of a query's screened row -> candidate columns),
 // screen_rescore_kernel (one workgroup per query: the query in registers, four candidate rows per step, float64 sums),
-// screen_rescore_planes_kernel (the same from the two fp16 planes of a prepared index: no fp32 rows needed),
+// screen_rescore_planes_kernel (the same from the two fp16 planes of a prepared index: no fp32 rows needed), the _sliced_ variants
+// of both (rows wider than the registers hold: the query in column slices, per-candidate float64 totals in LDS),
 // screen_select_kernel (candidates + running list -> new running list, rank by counting 64-bit keys).
 #include "common.hpp"
 #include "tile_order.hpp"
@@ -278,6 +279,69 @@ __global__ __launch_bounds__(512) void screen_rescore_kernel(const float* __rest
   }
 }
 
+// The same for rows of ANY width: the columns are cut into slices of `slice` <= 2048 NJ columns (a multiple of 4096; the last one
+// may be short).  Per slice the query slice is loaded into the registers and the candidate loop above runs over that slice's columns
+// of every candidate row -- four rows per step, float64, the same wave / LDS tree -- and the step's four totals are added to the
+// candidates' float64 accumulators in LDS (SCREEN_CMAX doubles: 4 KiB).  Slices are added in ascending column order: deterministic,
+// and for a row of one slice 0 + total, the bits of the kernel above.  Every byte of a candidate row is still read exactly once.
+template <int NJ>
+__global__ __launch_bounds__(512) void screen_rescore_sliced_kernel(const float* __restrict__ queries, const float* __restrict__ db,
+                                                                    int64_t dim, int64_t slice, int cmax, const int* __restrict__ cand,
+                                                                    const int* __restrict__ count, int metric, const float* __restrict__ qn,
+                                                                    const float* __restrict__ dn, const float* __restrict__ dnorm,
+                                                                    float* __restrict__ cand_v) {
+  __shared__ double red[8][RS_G];
+  __shared__ double tot_s[SCREEN_CMAX];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t q = blockIdx.x;
+  const int n = min(count[q], cmax);
+  for (int i = tid; i < n; i += 512) tot_s[i] = 0.0;     // (first touched again after the barrier of a step)
+  for (int64_t col0 = 0; col0 < dim; col0 += slice) {
+    const int n4 = (int)(min(slice, dim - col0) >> 2);
+    f32x4 qv[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int idx = tid + 512 * j;
+      qv[j] = idx < n4 ? reinterpret_cast<const f32x4*>(queries + q * dim + col0)[idx] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    for (int i0 = 0; i0 < n; i0 += RS_G) {
+      const f32x4* dr[RS_G];
+#pragma unroll
+      for (int g = 0; g < RS_G; ++g)                       // (a short last group re-reads its last row; the copy is not added)
+        dr[g] = reinterpret_cast<const f32x4*>(db + (int64_t)cand[q * cmax + min(i0 + g, n - 1)] * dim + col0);
+      double s[RS_G];
+#pragma unroll
+      for (int g = 0; g < RS_G; ++g) s[g] = 0.0;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int idx = tid + 512 * j;
+        if (idx < n4) {
+          f32x4 d[RS_G];
+#pragma unroll
+          for (int g = 0; g < RS_G; ++g) d[g] = dr[g][idx];
+#pragma unroll
+          for (int g = 0; g < RS_G; ++g)
+            s[g] += ((double)qv[j][0] * (double)d[g][0] + (double)qv[j][1] * (double)d[g][1]) +
+                    ((double)qv[j][2] * (double)d[g][2] + (double)qv[j][3] * (double)d[g][3]);
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < RS_G; ++g) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s[g] += __shfl_xor(s[g], off, 64);
+        if (lane == 0) red[wave][g] = s[g];
+      }
+      __syncthreads();
+      if (tid < RS_G && i0 + tid < n)
+        tot_s[i0 + tid] += ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid])) + ((red[4][tid] + red[5][tid]) + (red[6][tid] + red[7][tid]));
+      __syncthreads();
+    }
+  }
+  const float qq = metric ? qn[q] : 0.f;
+  for (int i = tid; i < n; i += 512)                       // (n > 0: the last step ended with a barrier)
+    cand_v[q * cmax + i] = screen_value((float)tot_s[i], cand[q * cmax + i], metric, qq, dn, dnorm);
+}
+
 // ------------------------------------------------------------------------------------------ re-score from the index
 // The same re-scoring WITHOUT the fp32 rows (ANYLOC_TOPK_RESCORE_PLANES): a candidate row is read from the two fp16 planes of
 // the prepared index (topk.hip: index_view), whose sum (hi + lo) 2^-e IS the database the index holds -- every element within
@@ -378,6 +442,102 @@ __global__ __launch_bounds__(512) void screen_rescore_planes_kernel(const float*
       cand_v[q * cmax + i0 + tid] = screen_value((float)(tot * (double)dinv[s0 + c]), c, metric, qq, dn, dnorm);
     }
     __syncthreads();
+  }
+}
+
+// The same for rows of ANY width (dim % 16 == 0), sliced as screen_rescore_sliced_kernel: a slice of `slice` <= 4096 NU columns (a
+// multiple of 4096: whole k-blocks, 512 units per j) starts at k-block col0 / 16 of every candidate row's image, (col0 / 16) 2 R_p 32
+// bytes into it -- still a 32-bit offset: the whole image stays inside 2 GiB.  The totals of the slices meet in
+// the LDS accumulators in ascending column order; the row's 2^-e goes on the whole sum.  The fence on the query registers stays
+// inside the slice loop: it is what keeps the float64 conversions of the query slice out of the candidate loop's registers.
+template <int NU>
+__global__ __launch_bounds__(512) void screen_rescore_planes_sliced_kernel(const float* __restrict__ queries, const unsigned char* __restrict__ img,
+                                                                           size_t slot, int64_t panel, int64_t ndb, int64_t s0,
+                                                                           const float* __restrict__ dinv, int64_t dim, int64_t slice, int cmax,
+                                                                           const int* __restrict__ cand, const int* __restrict__ count, int metric,
+                                                                           const float* __restrict__ qn, const float* __restrict__ dn,
+                                                                           const float* __restrict__ dnorm, float* __restrict__ cand_v) {
+  __shared__ double red[8][RS_G];
+  __shared__ double tot_s[SCREEN_CMAX];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t q = blockIdx.x;
+  const int n = min(count[q], cmax);
+  for (int i = tid; i < n; i += 512) tot_s[i] = 0.0;     // (first touched again after the barrier of a step)
+  const int ncol = (int)dim, nslice = (int)slice;
+  for (int col0 = 0; col0 < ncol; col0 += nslice) {
+    const int n8 = min(nslice, ncol - col0) >> 3;
+    f32x4 qa[NU], qb[NU];
+#pragma unroll
+    for (int j = 0; j < NU; ++j) {
+      const int u = tid + 512 * j;
+      const f32x4* qr = reinterpret_cast<const f32x4*>(queries + q * dim + col0);
+      qa[j] = u < n8 ? qr[2 * u] : f32x4{0.f, 0.f, 0.f, 0.f};
+      qb[j] = u < n8 ? qr[2 * u + 1] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    for (int i0 = 0; i0 < n; i0 += RS_G) {
+      const unsigned char* dr[RS_G];
+      unsigned plane[RS_G], off0[RS_G];                    // bytes of one plane of the row's image: R_p * 32
+#pragma unroll
+      for (int g = 0; g < RS_G; ++g) {
+        const int64_t r = s0 + cand[q * cmax + min(i0 + g, n - 1)];   // (a short last group re-reads its last row; the copy is not added)
+        const int64_t p = r / panel, lr = r - p * panel;
+        plane[g] = (unsigned)(min(panel, ndb - p * panel) * 32);
+        dr[g] = img + (size_t)p * slot + lr * 32;
+        off0[g] = (unsigned)(((tid & 1) ^ (int)((lr >> 3) & 1)) << 4) + (unsigned)((col0 >> 4) + (tid >> 1)) * 2u * plane[g];
+      }
+      double s[RS_G];
+#pragma unroll
+      for (int g = 0; g < RS_G; ++g) s[g] = 0.0;
+      sc_f16x8 hi[RS_G], lo[RS_G], hi_n[RS_G], lo_n[RS_G];
+      auto load = [&](int j, sc_f16x8 (&h)[RS_G], sc_f16x8 (&l)[RS_G]) {
+        if (tid + 512 * j < n8) {
+#pragma unroll
+          for (int g = 0; g < RS_G; ++g) {
+            const unsigned o = off0[g] + (unsigned)(512 * j) * plane[g];     // k-block (tid >> 1) + 256 j of the slice
+            h[g] = *reinterpret_cast<const sc_f16x8*>(dr[g] + o);
+            l[g] = *reinterpret_cast<const sc_f16x8*>(dr[g] + (o + plane[g]));
+          }
+        }
+      };
+      load(0, hi, lo);
+#pragma unroll
+      for (int j = 0; j < NU; ++j) asm volatile("" : "+v"(qa[j]), "+v"(qb[j]));
+#pragma unroll
+      for (int j = 0; j < NU; ++j) {
+        if (j + 1 < NU) load(j + 1, hi_n, lo_n);
+        asm volatile("" ::: "memory");
+        if (tid + 512 * j < n8) {
+#pragma unroll
+          for (int g = 0; g < RS_G; ++g) {
+            double v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (double)(float)hi[g][e] + (double)(float)lo[g][e];
+            s[g] += (((double)qa[j][0] * v[0] + (double)qa[j][1] * v[1]) + ((double)qa[j][2] * v[2] + (double)qa[j][3] * v[3])) +
+                    (((double)qb[j][0] * v[4] + (double)qb[j][1] * v[5]) + ((double)qb[j][2] * v[6] + (double)qb[j][3] * v[7]));
+          }
+        }
+#pragma unroll
+        for (int g = 0; g < RS_G; ++g) {
+          hi[g] = hi_n[g];
+          lo[g] = lo_n[g];
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < RS_G; ++g) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s[g] += __shfl_xor(s[g], off, 64);
+        if (lane == 0) red[wave][g] = s[g];
+      }
+      __syncthreads();
+      if (tid < RS_G && i0 + tid < n)
+        tot_s[i0 + tid] += ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid])) + ((red[4][tid] + red[5][tid]) + (red[6][tid] + red[7][tid]));
+      __syncthreads();
+    }
+  }
+  const float qq = metric ? qn[q] : 0.f;
+  for (int i = tid; i < n; i += 512) {                     // (n > 0: the last step ended with a barrier)
+    const int c = cand[q * cmax + i];
+    cand_v[q * cmax + i] = screen_value((float)(tot_s[i] * (double)dinv[s0 + c]), c, metric, qq, dn, dnorm);
   }
 }
 
@@ -571,42 +731,70 @@ int screen_overflow_plan(const int* over_q, int64_t nq, int side_cap, int* plan,
   return launch_status("screen_overflow_plan_kernel");
 }
 
-bool screen_rescore_supported(int64_t dim) { return dim % 4 == 0 && dim <= 2048 * 24; }
+bool screen_rescore_supported(int64_t dim) { return dim >= 4 && dim % 4 == 0; }
 
-int screen_rescore(const float* queries, const float* db, int64_t dim, int64_t nq, int cmax, const int* cand, const int* count,
-                   int metric, const float* qn, const float* dn, const float* dnorm, float* cand_v, hipStream_t stream) {
-  ANYLOC_CHECK_ARG(screen_rescore_supported(dim), "screen_rescore: dim %lld not served", (long long)dim);
+// a slice of the sliced kernels: columns per slice, a multiple of 4096 the largest register footprint holds
+constexpr int64_t SCREEN_RESCORE_PLANES_COLS = 4096 * 8;   // the widest slice of screen_rescore_planes_sliced_kernel
+static bool rescore_slice_ok(int64_t slice) { return slice > 0 && slice % 4096 == 0 && slice <= SCREEN_RESCORE_COLS; }
+
+int screen_rescore(const float* queries, const float* db, int64_t dim, int64_t slice, int64_t nq, int cmax, const int* cand,
+                   const int* count, int metric, const float* qn, const float* dn, const float* dnorm, float* cand_v, hipStream_t stream) {
+  ANYLOC_CHECK_ARG(screen_rescore_supported(dim) && (slice ? rescore_slice_ok(slice) && cmax <= SCREEN_CMAX : dim <= SCREEN_RESCORE_COLS),
+                   "screen_rescore: dim %lld in slices of %lld not served", (long long)dim, (long long)slice);
   ProfScope prof("topk_screen_rescore", stream, 0.0, 0.0);
-  const int nj = (int)((dim / 4 + 511) / 512);
+  const int nj = (int)(((slice ? slice : dim) / 4 + 511) / 512);
 #define ANYLOC_RESCORE(NJ)                                                                                                      \
   hipLaunchKernelGGL((screen_rescore_kernel<NJ>), dim3((unsigned)nq), dim3(512), 0, stream, queries, db, dim, cmax, cand, count, \
                      metric, qn, dn, dnorm, cand_v)
-  if (nj <= 1) ANYLOC_RESCORE(1);
+#define ANYLOC_RESCORE_SLICED(NJ)                                                                                                 \
+  hipLaunchKernelGGL((screen_rescore_sliced_kernel<NJ>), dim3((unsigned)nq), dim3(512), 0, stream, queries, db, dim, slice, cmax, \
+                     cand, count, metric, qn, dn, dnorm, cand_v)
+  if (slice) {
+    if (nj <= 2) ANYLOC_RESCORE_SLICED(2);
+    else if (nj <= 4) ANYLOC_RESCORE_SLICED(4);
+    else if (nj <= 8) ANYLOC_RESCORE_SLICED(8);
+    else if (nj <= 16) ANYLOC_RESCORE_SLICED(16);
+    else ANYLOC_RESCORE_SLICED(24);
+  } else if (nj <= 1) ANYLOC_RESCORE(1);
   else if (nj <= 2) ANYLOC_RESCORE(2);
   else if (nj <= 4) ANYLOC_RESCORE(4);
   else if (nj <= 8) ANYLOC_RESCORE(8);
   else if (nj <= 16) ANYLOC_RESCORE(16);
   else ANYLOC_RESCORE(24);
 #undef ANYLOC_RESCORE
+#undef ANYLOC_RESCORE_SLICED
   return launch_status("screen_rescore_kernel");
 }
 
 int screen_rescore_planes(const float* queries, const unsigned char* img, size_t slot, int64_t panel, int64_t ndb, int64_t s0,
-                          const float* dinv, int64_t dim, int64_t nq, int cmax, const int* cand, const int* count, int metric,
-                          const float* qn, const float* dn, const float* dnorm, float* cand_v, hipStream_t stream) {
-  ANYLOC_CHECK_ARG(dim % 16 == 0 && screen_rescore_supported(dim), "screen_rescore_planes: dim %lld not served", (long long)dim);
+                          const float* dinv, int64_t dim, int64_t slice, int64_t nq, int cmax, const int* cand, const int* count,
+                          int metric, const float* qn, const float* dn, const float* dnorm, float* cand_v, hipStream_t stream) {
+  ANYLOC_CHECK_ARG(dim >= 16 && dim % 16 == 0 && (slice ? rescore_slice_ok(slice) && cmax <= SCREEN_CMAX : dim <= SCREEN_RESCORE_COLS),
+                   "screen_rescore_planes: dim %lld in slices of %lld not served", (long long)dim, (long long)slice);
   ANYLOC_CHECK_ARG(img && dinv && panel > 0 && s0 >= 0 && s0 < ndb, "screen_rescore_planes: bad index");
   ProfScope prof("topk_screen_rescore_planes", stream, 0.0, 0.0);
-  const int nu = (int)((dim / 8 + 511) / 512);
+  // (NU = 12 of the single-slice kernel leaves two VGPRs of the 256 a 512-thread workgroup has: with the slice loop's state it
+  // spills.  The sliced kernel stops at NU = 8, 237 VGPRs and no scratch: its slices are at most 32 768 columns.)
+  slice = std::min(slice, SCREEN_RESCORE_PLANES_COLS);
+  const int nu = (int)(((slice ? slice : dim) / 8 + 511) / 512);
 #define ANYLOC_RESCORE_PLANES(NU)                                                                                                \
   hipLaunchKernelGGL((screen_rescore_planes_kernel<NU>), dim3((unsigned)nq), dim3(512), 0, stream, queries, img, slot, panel, ndb, s0, \
                      dinv, dim, cmax, cand, count, metric, qn, dn, dnorm, cand_v)
-  if (nu <= 1) ANYLOC_RESCORE_PLANES(1);
+#define ANYLOC_RESCORE_PLANES_SLICED(NU)                                                                                          \
+  hipLaunchKernelGGL((screen_rescore_planes_sliced_kernel<NU>), dim3((unsigned)nq), dim3(512), 0, stream, queries, img, slot, panel, ndb, \
+                     s0, dinv, dim, slice, cmax, cand, count, metric, qn, dn, dnorm, cand_v)
+  if (slice) {
+    if (nu <= 1) ANYLOC_RESCORE_PLANES_SLICED(1);
+    else if (nu <= 2) ANYLOC_RESCORE_PLANES_SLICED(2);
+    else if (nu <= 4) ANYLOC_RESCORE_PLANES_SLICED(4);
+    else ANYLOC_RESCORE_PLANES_SLICED(8);
+  } else if (nu <= 1) ANYLOC_RESCORE_PLANES(1);
   else if (nu <= 2) ANYLOC_RESCORE_PLANES(2);
   else if (nu <= 4) ANYLOC_RESCORE_PLANES(4);
   else if (nu <= 8) ANYLOC_RESCORE_PLANES(8);
   else ANYLOC_RESCORE_PLANES(12);
 #undef ANYLOC_RESCORE_PLANES
+#undef ANYLOC_RESCORE_PLANES_SLICED
   return launch_status("screen_rescore_planes_kernel");
 }
 

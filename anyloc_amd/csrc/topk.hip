@@ -310,9 +310,9 @@ constexpr int64_t SCORE_KC16 = 512;       // k-blocks of 16 per accumulated chun
 constexpr int64_t SCREEN_KC16 = 1536;     // ... leading-plane scores (the accumulation term of the screening bound)
 
 // Screened search (scores_screen.hip)
-constexpr int SCREEN_CMAX = 512;          // candidates per query and column range; more: the call re-runs unscreened
+// (SCREEN_CMAX, candidates per query and column range, and SCREEN_RESCORE_COLS, the widest re-scoring slice: common.hpp)
 constexpr int SCREEN_KMAX = 128;
-constexpr int64_t SCREEN_COLS = 131072;   // database columns per range (a multiple of the panel)
+constexpr int64_t SCREEN_COLS = 131072;   // database columns per range, at most (a range is a whole number of panels)
 constexpr size_t SCREEN_SBUF_MAX = 12ull << 30;
 
 enum { PATH_F32 = 0, PATH_FEWQ = 1, PATH_H3 = 2 };   // the values anyloc_topk_path answers
@@ -322,15 +322,22 @@ struct TopkPlan {
   int path;
   int64_t panel, q_chunk;          // database rows per score panel; fp16 panels: queries per operand image
   int64_t sc_cols;                 // database columns per screened range; 0: no screened search for this shape
+  int64_t rs_cols;                 // ... columns per slice of its re-scoring kernels; 0: the whole row in one, on the single-slice kernels
   int fewq;                        // few-query arithmetic: 2 = two fp16 planes, 1 = three bf16 planes, 0 = fp32 MFMA
   bool qdma;                       // ... on fp16 planes: the queries are pre-split once per call
 };
 // Option topk_h3: -1 (default) = where it pays (>= 256 queries, dim >= 1024, >= 2048 rows), 0 = never, 1 = wherever the shape
 // allows (tests).  Option topk_screen: 0 = never, 1 = wherever the shape allows, -1 (default) = where it pays (>= 256 queries
-// against >= 16 384 rows of >= 4096 columns); it serves the fp16 panels' shapes with k <= 128, rows the re-scoring kernel holds
-// in registers, and a score buffer of at most 12 GiB (fewer columns per range for more queries).
+// against >= 16 384 rows of 4096 .. 49 152 columns -- wider rows screen under 1 only: their panels are short, 3 840 rows at 131 072
+// columns, the 256 x 256 tiles of gemm_screen then fill a quarter of the chip and 1 000 x 20 000 x 131 072 took 28.1 ms screened
+// against 24.7 ms, profiles/wide_screen_timing.md); it serves the fp16 panels' shapes with k <= 128 and a score buffer of at most 12 GiB
+// (fewer columns per range for more queries).  A range is a whole number of panels -- the indexed db_panel serves whole panels,
+// and from 65 536 columns on the panel (h3_rows_limit) no longer divides SCREEN_COLS.  Option topk_rescore_cols: the columns per
+// slice of the re-scoring kernels, 0 (default) = SCREEN_RESCORE_COLS, where narrower rows keep the single-slice kernels; a set value
+// (a multiple of 4096) sends every width through the sliced ones.  It changes no size.
 TopkPlan topk_plan(int64_t nq, int64_t ndb, int64_t dim, int64_t k, bool indexed) {
   const int64_t h3_mode = option(OPT_TOPK_H3), screen_mode = option(OPT_TOPK_SCREEN), limit = h3_rows_limit(dim);
+  const int64_t rescore_cols = option(OPT_TOPK_RESCORE_COLS);
   TopkPlan p{nq, ndb, dim, k, indexed};
   p.fewq = (int)option(OPT_TOPK_FEWQ_X6);
   p.qdma = option(OPT_TOPK_FEWQ_QDMA) != 0;
@@ -340,10 +347,11 @@ TopkPlan topk_plan(int64_t nq, int64_t ndb, int64_t dim, int64_t k, bool indexed
   p.panel = h3 ? std::min(H3_PANEL, limit) : PANEL;
   p.q_chunk = std::max<int64_t>(1, h3 ? std::min(nq, limit) : nq);
   if (h3 && screen_mode != 0 && k >= 1 && k <= SCREEN_KMAX && screen_rescore_supported(dim) && nq > 0 && ndb > 0 &&
-      (screen_mode > 0 || (nq >= 256 && ndb >= 16384 && dim >= 4096))) {
+      (screen_mode > 0 || (nq >= 256 && ndb >= 16384 && dim >= 4096 && dim <= SCREEN_RESCORE_COLS))) {
     const int64_t fit = (int64_t)(SCREEN_SBUF_MAX / 4) / nq / p.panel * p.panel;
-    const int64_t cols = std::min(std::min(SCREEN_COLS, cdiv(ndb, p.panel) * p.panel), fit);
+    const int64_t cols = std::min(std::min(SCREEN_COLS / p.panel * p.panel, cdiv(ndb, p.panel) * p.panel), fit);
     p.sc_cols = cols >= p.panel ? cols : 0;
+    p.rs_cols = rescore_cols > 0 ? std::min(rescore_cols, SCREEN_RESCORE_COLS) : dim > SCREEN_RESCORE_COLS ? SCREEN_RESCORE_COLS : 0;
   }
   return p;
 }
@@ -624,11 +632,11 @@ int screened_search(const TopkCall& c) {
     ANYLOC_TRY(screen_compact(w.sbuf, sn, sn, nq, (int)c.p.k, c.metric, w.qn, w.dn + s0, dnorm_s, w.scr_v, w.margin, SCREEN_CMAX, w.cand,
                               w.count, w.overflow, c.no_wait ? w.over_q : nullptr, c.stream));
     if (c.rescore_planes)
-      ANYLOC_TRY(screen_rescore_planes(c.queries, c.iv.img, c.iv.slot, c.iv.panel, ndb, s0, c.iv.dinv, dim, nq, SCREEN_CMAX, w.cand, w.count,
-                                       c.metric, w.qn, w.dn + s0, dnorm_s, w.cand_v, c.stream));
+      ANYLOC_TRY(screen_rescore_planes(c.queries, c.iv.img, c.iv.slot, c.iv.panel, ndb, s0, c.iv.dinv, dim, c.p.rs_cols, nq, SCREEN_CMAX, w.cand,
+                                       w.count, c.metric, w.qn, w.dn + s0, dnorm_s, w.cand_v, c.stream));
     else
-      ANYLOC_TRY(screen_rescore(c.queries, c.db + s0 * dim, dim, nq, SCREEN_CMAX, w.cand, w.count, c.metric, w.qn, w.dn + s0, dnorm_s,
-                                w.cand_v, c.stream));
+      ANYLOC_TRY(screen_rescore(c.queries, c.db + s0 * dim, dim, c.p.rs_cols, nq, SCREEN_CMAX, w.cand, w.count, c.metric, w.qn, w.dn + s0,
+                                dnorm_s, w.cand_v, c.stream));
     ANYLOC_TRY(screen_select(w.cand, w.cand_v, w.count, SCREEN_CMAX, c.index_base + s0, nq, (int)c.p.k, c.dist,
                              reinterpret_cast<int64_t*>(c.idx), s0 == 0, c.stream));
   }

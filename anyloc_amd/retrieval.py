@@ -50,7 +50,9 @@ class FlatIndex:
     (default): the fp32 rows, so an index without them searches unscreened.  "planes": the two planes of the index
     (ANYLOC_TOPK_RESCORE_PLANES) -- insists on the planes, and with ``keep_fp32=False`` the index is ONE copy of the database
     (4 bytes per element, as faiss keeps after ``index.add``) that still searches screened; its lists are the float64-exact
-    ones over the 22-bit rows the planes hold (every element within 2^-23 of its row's maximum)."""
+    ones over the 22-bit rows the planes hold (every element within 2^-23 of its row's maximum).  Either way the screened
+    search serves every width the planes serve; rows above 49 152 columns run it under option ``topk_screen = 1`` only
+    (measured slower than the three-product panels at 1 000 queries: DESIGN 4.4)."""
 
     def __init__(self, db, method="cosine", norm_descs=True, planes="auto", keep_fp32=True, rescore="rows"):
         if method not in ("cosine", "l2"):

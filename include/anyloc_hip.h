@@ -114,8 +114,14 @@ const char* anyloc_last_error(void);
  *   vlad_parts (0 = auto) vlad_two_pass (0) vlad_fused_v (0) kmeans_fused_v (0)
  *                                     which VLAD / k-means kernel serves a call
  *   topk_screen (-1)                  many queries against long rows: the screened search described at anyloc_topk_search_index_rows,
- *                                     -1 = where it pays (>= 256 queries, >= 16 384 rows, dim >= 4096), 1 = wherever the shape allows,
- *                                     0 = never (every panel on the three-product scores)
+ *                                     -1 = where it pays (>= 256 queries, >= 16 384 rows, 4096 <= dim <= 49 152), 1 = wherever the shape
+ *                                     allows (every width the fp16 panels serve; rows above 49 152 columns measured slower screened at
+ *                                     1 000 queries, profiles/wide_screen_timing.md: they screen under 1 only), 0 = never (every panel on
+ *                                     the three-product scores)
+ *   topk_rescore_cols (0)             columns per slice of the screened search's re-scoring kernels: 0 = 49 152 (narrower rows in one
+ *                                     slice, on the single-slice kernels), or a multiple of 4096 up to 49 152, which sends every width
+ *                                     through the sliced kernels (tests); other values are ANYLOC_ERR_INVALID_ARG.  It changes no
+ *                                     workspace size
  *   h3_ln_lead (0)                    batched calls (>= 64 tile rows of 128 tokens): 1 = LayerNorm 1 / 2 run as LEAD workgroups of 16 rows
  *                                     interleaved with the tiles of the qkv / fc1 (w12) GEMM's own launch (per XCD: the lead work of the next
  *                                     tile-row group sits among the tiles of the current one; write-through stores, one ticket per tile row);
@@ -453,8 +459,8 @@ int anyloc_kmeans_update(const float* sums, const float* counts, const float* ce
  *   scores instead of materialising a normalised copy of the database (queries are taken as given).
  *   With <= 64 queries of >= 4096 dimensions the database is streamed once by a split-K launch
  *   (HBM-bound); otherwise scores are fp32-MFMA GEMM panels (MFMA-bound).
- *   Streams: where the screened search runs (option topk_screen: by default >= 256 queries x >= 16 384 rows x >= 4096
- *   columns on the fp16 panels) the call synchronises with `stream` once -- it waits for its 4-byte overflow flag
+ *   Streams: where the screened search runs (option topk_screen: by default >= 256 queries x >= 16 384 rows x 4096 ..
+ *   49 152 columns on the fp16 panels; with topk_screen = 1 every shape of the fp16 panels with k <= 128) the call synchronises with `stream` once -- it waits for its 4-byte overflow flag
  *   (see anyloc_topk_search_index_rows); every other shape returns without waiting, and so does every shape with
  *   ANYLOC_TOPK_NO_WAIT (below). */
 #define ANYLOC_TOPK_NORMALIZE_DB 1u
@@ -488,7 +494,8 @@ int anyloc_topk_search_index(const float* queries, int64_t nq, const void* index
  * |s - s~| <= eps |q| |d|, the k-th best screened value of a query minus twice its bound is a threshold no row of the true list can
  * fall below, and the few tens of rows above it are re-scored from the fp32 rows with float64 sums and ranked (value, then lower
  * index).  One bound per query: its norm and measured residual x the largest row norm the compared value sees (1 with
- * ANYLOC_TOPK_NORMALIZE_DB, the largest raw row norm without it: rows of very different raw norms make it loose).  k <= 128, dim <= 49 152; a query
+ * ANYLOC_TOPK_NORMALIZE_DB, the largest raw row norm without it: rows of very different raw norms make it loose).  k <= 128; every dim the fp16 panels serve -- rows
+ * above 49 152 columns are re-scored in column slices (option topk_rescore_cols) and screen under topk_screen = 1 only; a query
  * with more than 512 rows inside its bound makes the call run the unscreened search instead (one 4-byte read-back per call decides).
  * Lists: the rows of the exact search; distances within 1e-6 of it (more accurate, not bit-identical).  db == NULL: as
  * anyloc_topk_search_index.
@@ -505,7 +512,8 @@ int anyloc_topk_search_index_rows(const float* queries, int64_t nq, const float*
  *   screened search are re-scored from the two fp16 planes of the index: (hi + lo) 2^-e, the 22-bit rows the index holds and the
  *   unscreened indexed search scores (every element within 2^-23 of its row's maximum: a normalised score moves by < 1e-8),
  *   in float64.  `db` is then not needed and not read, so a prepared index costs 4 bytes per element and keeps the screened
- *   speed; the lists are the float64-exact lists over those rows.  Everything else as above (bound, 512-candidate cap and the
+ *   speed; the lists are the float64-exact lists over those rows (any dim of the index: rows above 49 152 columns in
+ *   slices of at most 32 768).  Everything else as above (bound, 512-candidate cap and the
  *   unscreened search of the same call beyond it, workspace of anyloc_topk_index_workspace_bytes).  anyloc_topk (no index)
  *   rejects the flag with ANYLOC_ERR_INVALID_ARG. */
 #define ANYLOC_TOPK_RESCORE_PLANES 2u

@@ -1,0 +1,241 @@
+"""Screened retrieval on rows wider than 49 152 columns (``pytest -m gpu``; ``screen_rescore_sliced_kernel`` and
+``screen_rescore_planes_sliced_kernel`` of csrc/scores_screen.hip, option ``topk_rescore_cols``): the re-scoring kernels take
+the query in column slices and add the slices' float64 totals in LDS, so the screened search serves every width the fp16 panels
+serve.  Data recipe and float64 checker are those of tests/test_gpu_screen.py, restated here: planted neighbours at graded
+distances, a float64 flat search (computed in row blocks), distances within 3e-6 (inner product) / 1e-5 (L2) of it, a differing
+index only where the two float64 scores are closer than that bar -- and at most 0.1 % of a case's list entries may differ at
+all (a float64 search against itself gives 0; under fp32 rounding far less than one entry per case is expected).  Every case
+asserts from the profile that the leading-plane GEMM ran and the exact one did not: no silent fallback.
+
+The multi-slice path is reached at small shapes with ``topk_rescore_cols = 4096`` (8 208 columns: two slices and a 16-column
+third) and by every shape above 49 152 columns under the default slice.  What no test here reaches: TWO column ranges at
+> 65 535 columns -- more than 130 000 rows of >= 256 KiB each do not fit a seconds-long test; the sizes of that path are pinned
+by tests/test_topk_wide_screen_cpu.py and it was run once by tools/time_wide_screen.py (profiles/wide_screen_timing.md)."""
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+BAR = {"ip": 3e-6, "l2": 1e-5}                             # (the bars of tests/test_gpu_screen.py)
+SCREEN = dict(topk_screen=1, topk_h3=1)
+
+
+def _exact64(qu, db, metric):
+    """float64 score matrix of a flat search over F.normalize(db) on the device (larger = better), in blocks of 512 rows."""
+    q = qu.double()
+    out = torch.empty(qu.shape[0], db.shape[0], dtype=torch.float64, device=qu.device)
+    for r0 in range(0, db.shape[0], 512):
+        d = torch.nn.functional.normalize(db[r0:r0 + 512].double())
+        s = q @ d.t()
+        if metric == "l2":
+            s = -((q * q).sum(1, keepdim=True) + (d * d).sum(1)[None, :] - 2.0 * s)
+        out[:, r0:r0 + 512] = s
+    return out
+
+
+def _check(d, i, s, k, metric, tag):
+    """Lists (d, i) against the float64 score matrix ``s`` (ties -> lower index): padding, distances within the bar, a differing
+    index only at a float64 near-tie, and at most 0.1 % of the entries.  -> differing entries."""
+    kk = min(k, s.shape[1])
+    o = torch.sort(s, dim=1, descending=True, stable=True)
+    assert bool((i[:, kk:] == -1).all()), tag
+    got64 = torch.gather(s, 1, i[:, :kk])
+    val = -d[:, :kk].double() if metric == "l2" else d[:, :kk].double()
+    err = float((val - got64).abs().max())
+    mism = i[:, :kk] != o.indices[:, :kk]
+    differing = int(mism.sum())
+    print(f"{tag}: max |distance - float64| {err:.2e} (bar {BAR[metric]:.0e}); {differing} of {mism.numel()} entries differ")
+    assert err <= BAR[metric], (tag, err)
+    if differing:                                         # only float64 near-ties may swap
+        assert float((got64[mism] - o.values[:, :kk][mism]).abs().max()) <= BAR[metric], tag
+    assert differing <= 0.001 * mism.numel(), (tag, differing, mism.numel())
+    return differing
+
+
+def _data(nq, ndb, dim, seed, planted=True):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    db = torch.randn(ndb, dim, generator=g, device=DEV) * (0.3 + 2.0 * torch.rand(ndb, 1, generator=g, device=DEV))
+    qu = torch.nn.functional.normalize(torch.randn(nq, dim, generator=g, device=DEV))
+    if planted and ndb >= 64:
+        # every query has a handful of true neighbours at graded distances, some closer to each other than the screening bound
+        for j in range(6):
+            rows = torch.randint(0, ndb, (nq,), generator=g, device=DEV)
+            noise = torch.nn.functional.normalize(torch.randn(nq, dim, generator=g, device=DEV))
+            db[rows] = (qu + (0.02 + 0.0004 * j) * noise) * (0.5 + j)
+    return qu, db
+
+
+_CASE = {}
+
+
+def _case(nq, ndb, dim, metric):
+    """(queries, rows, float64 scores) of a shape, made once and shared by the tests that follow each other on it (one shape is
+    kept: the widest holds 2.1 GB of rows)."""
+    key = (nq, ndb, dim, metric)
+    if key not in _CASE:
+        _CASE.clear()
+        qu, db = _data(nq, ndb, dim, nq + ndb + dim)
+        _CASE[key] = (qu, db, _exact64(qu, db, metric))
+    return _CASE[key]
+
+
+def _as_flat_index_scores_them(qu, db, s, metric):
+    """FlatIndex.search normalises its queries (ops.l2norm_rows, which may move the last bit of a unit row): the queries it
+    scores and their float64 scores"""
+    from anyloc_amd import ops
+    q = ops.l2norm_rows(qu)
+    return q, (s if torch.equal(q, qu) else _exact64(q, db, metric))
+
+
+def _profiled(fn):
+    from anyloc_amd import ops
+    ops.profile_enable(True); ops.profile_reset()
+    out = fn()
+    torch.cuda.synchronize()
+    prof = ops.profile_dump()
+    ops.profile_enable(False)
+    return out, prof
+
+
+def _screened(prof, rescore="topk_screen_rescore"):
+    """the leading-plane GEMM ran, the exact one did not, and the candidates were re-scored by the kernel named"""
+    other = {"topk_screen_rescore": "topk_screen_rescore_planes", "topk_screen_rescore_planes": "topk_screen_rescore"}[rescore]
+    return "topk_screen_gemm" in prof and "topk_scores_gemm" not in prof and rescore in prof and other not in prof
+
+
+def _three_searches(qu, db, k, metric):
+    """the one-shot call, FlatIndex with its rows, FlatIndex without them -> [(tag, (d, i), profile)] under the options in force"""
+    from anyloc_amd import ops, retrieval
+    method = "cosine" if metric == "ip" else "l2"
+    kept = retrieval.FlatIndex(db, method, True, planes=True)
+    bare = retrieval.FlatIndex(db, method, True, keep_fp32=False, rescore="planes")
+    assert kept.has_planes and kept.db is not None and bare.db is None
+    out = []
+    for tag, fn, rescore in (("one-shot", lambda: ops.topk(qu, db, k, metric, normalize_db=True), "topk_screen_rescore"),
+                             ("rows kept", lambda: kept.search(qu, k), "topk_screen_rescore"),
+                             ("rows free", lambda: bare.search(qu, k), "topk_screen_rescore_planes")):
+        res, prof = _profiled(fn)
+        assert _screened(prof, rescore), (tag, sorted(prof))
+        out.append((tag, res))
+    return out
+
+
+@pytest.mark.parametrize("nq,ndb,dim,k,metric", [(130, 9000, 8208, 20, "ip"),      # two slices and a 16-column third; two panels
+                                                  (130, 9000, 8192, 10, "l2"),      # exactly two slices
+                                                  (70, 300, 12304, 20, "ip")])      # fewer rows than a panel; four slices, the last 16 columns
+def test_slices_of_4096_columns_give_the_lists_of_one_slice(nq, ndb, dim, k, metric):
+    """``topk_rescore_cols = 4096`` sends narrow rows through the sliced kernels: against float64, and against the same call on
+    the single-slice kernels (option 0) -- identical lists, distances within the bar (the float64 totals of the slices are added
+    in another order than one pass adds them: the last bit of the fp32 value may differ)."""
+    from anyloc_amd import ops
+    qu, db, s = _case(nq, ndb, dim, metric)
+    s_index = _as_flat_index_scores_them(qu, db, s, metric)[1]
+    with ops.options(topk_rescore_cols=4096, **SCREEN):
+        assert ops.get_option("topk_rescore_cols") == 4096
+        sliced = _three_searches(qu, db, k, metric)
+    assert ops.get_option("topk_rescore_cols") == 0
+    with ops.options(**SCREEN):
+        whole = _three_searches(qu, db, k, metric)
+    for (tag, (d, i)), (_, (d1, i1)) in zip(sliced, whole):
+        ref = s if tag == "one-shot" else s_index
+        _check(d, i, ref, k, metric, f"{tag}, slices of 4096, {nq}x{ndb}x{dim} {metric}")
+        _check(d1, i1, ref, k, metric, f"{tag}, one slice, {nq}x{ndb}x{dim} {metric}")
+        assert torch.equal(i, i1), tag
+        assert float((d - d1).abs().max()) <= BAR[metric], (tag, float((d - d1).abs().max()))
+
+
+WIDE = [(130, 4000, 131072, 20, "ip"),                     # a full 3 840-row panel and a ragged one; three slices
+        (130, 4000, 131072, 20, "l2"),
+        (70, 3000, 65536, 5, "ip"),                        # one ragged 7 936-row panel; two slices, the second 16 384 columns
+        (100, 2700, 196608, 20, "ip"),                     # a 2 560-row panel and a ragged one; exactly four slices
+        (100, 4000, 81920, 20, "ip")]                      # one ragged 6 400-row panel
+
+
+@pytest.mark.parametrize("nq,ndb,dim,k,metric", WIDE)
+def test_wide_rows_screened_give_the_exact_lists(nq, ndb, dim, k, metric):
+    """Default slice (49 152 columns), topk_screen = 1: against float64 and against the unscreened panels; a second call gives
+    the same bits; ``index_base`` shifts the indices and nothing else."""
+    from anyloc_amd import ops
+    qu, db, s = _case(nq, ndb, dim, metric)
+    with ops.options(**SCREEN):
+        (d, i), prof = _profiled(lambda: ops.topk(qu, db, k, metric, normalize_db=True))
+        assert _screened(prof), sorted(prof)
+        d_again, i_again = ops.topk(qu, db, k, metric, normalize_db=True)
+        assert torch.equal(d, d_again) and torch.equal(i, i_again)
+        d_b, i_b = ops.topk(qu, db, k, metric, normalize_db=True, index_base=5000)
+        assert torch.equal(torch.where(i_b >= 0, i_b - 5000, i_b), i) and torch.equal(d_b, d)
+    with ops.options(topk_screen=0, topk_h3=1):
+        (d0, i0), prof0 = _profiled(lambda: ops.topk(qu, db, k, metric, normalize_db=True))
+    assert "topk_scores_gemm" in prof0 and "topk_screen_gemm" not in prof0, sorted(prof0)
+    n = _check(d, i, s, k, metric, f"screened {nq}x{ndb}x{dim} {metric}")
+    n0 = _check(d0, i0, s, k, metric, f"unscreened {nq}x{ndb}x{dim} {metric}")
+    assert float((d - d0).abs().max()) <= BAR[metric]
+    assert int((i != i0).sum()) <= n + n0                  # a differing pair differs from the float64 list on one side at least
+
+
+def test_wide_rows_screened_on_an_index_without_its_rows():
+    """(130, 4000, 131 072) through ``FlatIndex(rescore="planes", keep_fp32=False)``: the planes variant, in four slices of 32 768
+    columns, against float64 and against the one-shot call on the rows."""
+    from anyloc_amd import ops, retrieval
+    nq, ndb, dim, k = WIDE[0][:4]
+    qu, db, s = _case(nq, ndb, dim, "ip")
+    q, s = _as_flat_index_scores_them(qu, db, s, "ip")
+    with ops.options(**SCREEN):
+        bare = retrieval.FlatIndex(db, "cosine", True, keep_fp32=False, rescore="planes")
+        assert bare.db is None
+        (d, i), prof = _profiled(lambda: bare.search(qu, k))
+        assert _screened(prof, "topk_screen_rescore_planes"), sorted(prof)
+        d_again, i_again = bare.search(qu, k)
+        assert torch.equal(d, d_again) and torch.equal(i, i_again)
+        d1, i1 = ops.topk(q, db, k, "ip", normalize_db=True)
+    n = _check(d, i, s, k, "ip", "rows free, 131 072 columns")
+    n1 = _check(d1, i1, s, k, "ip", "one-shot, 131 072 columns")
+    assert float((d - d1).abs().max()) <= BAR["ip"] and int((i != i1).sum()) <= n + n1
+
+
+def test_wide_rows_without_the_wait():
+    """ANYLOC_TOPK_NO_WAIT at 131 072 columns with one all-zero query (every row ties inside its bound: more than 512
+    candidates): its list is the unscreened call's, from the side batch of 64 x 131 072 floats; every other query keeps the
+    bits the screened search gives it in a call without the zero query."""
+    from anyloc_amd import ops
+    nq, ndb, dim, k = WIDE[0][:4]
+    clean, db, s = _case(nq, ndb, dim, "ip")
+    qu = clean.clone()
+    qu[7] = 0.0
+    with ops.options(**SCREEN):
+        d, i = ops.topk(qu, db, k, "ip", normalize_db=True, no_wait=True)
+        (d_w, i_w), prof = _profiled(lambda: ops.topk(qu, db, k, "ip", normalize_db=True))
+        assert "topk_screen_gemm" in prof and "topk_scores_gemm" in prof, sorted(prof)     # the waiting call falls back for everyone
+        (d_c, i_c), prof_c = _profiled(lambda: ops.topk(clean, db, k, "ip", normalize_db=True))
+        assert _screened(prof_c), sorted(prof_c)
+    with ops.options(topk_screen=0, topk_h3=1):
+        d0, i0 = ops.topk(qu, db, k, "ip", normalize_db=True)
+    assert torch.equal(i[7], i0[7]) and torch.equal(d[7], d0[7])
+    assert torch.equal(i[7], torch.arange(k, device=DEV)) and bool((d[7] == 0).all())       # every row ties at 0: lower index first
+    keep = torch.ones(nq, dtype=torch.bool, device=DEV)
+    keep[7] = False
+    assert torch.equal(d[keep], d_c[keep]) and torch.equal(i[keep], i_c[keep])
+    s_z = s.clone()
+    s_z[7] = 0.0
+    _check(d, i, s_z, k, "ip", "no wait, one zero query")
+
+
+def test_narrow_rows_under_default_options_are_unchanged():
+    """(300, 20 000, 4096) screens by default, on the single-slice kernels as before: the same checks; and the slice option is
+    back at 0 once its context has exited."""
+    from anyloc_amd import ops
+    nq, ndb, dim, k = 300, 20000, 4096, 20
+    with ops.options(topk_rescore_cols=4096):
+        assert ops.get_option("topk_rescore_cols") == 4096
+    assert ops.get_option("topk_rescore_cols") == 0
+    qu, db, s = _case(nq, ndb, dim, "ip")
+    (d, i), prof = _profiled(lambda: ops.topk(qu, db, k, "ip", normalize_db=True))
+    assert _screened(prof), sorted(prof)
+    d_again, i_again = ops.topk(qu, db, k, "ip", normalize_db=True)
+    assert torch.equal(d, d_again) and torch.equal(i, i_again)
+    with ops.options(topk_screen=0):
+        d0, i0 = ops.topk(qu, db, k, "ip", normalize_db=True)
+    n = _check(d, i, s, k, "ip", "narrow rows, defaults")
+    n0 = _check(d0, i0, s, k, "ip", "narrow rows, unscreened")
+    assert float((d - d0).abs().max()) <= BAR["ip"] and int((i != i0).sum()) <= n + n0
+    _CASE.clear()
