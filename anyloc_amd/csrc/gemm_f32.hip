@@ -385,7 +385,11 @@ constexpr F32Tile kF32Tile[] = {
 constexpr int F32_TILE_HALF = 5, F32_TILE_NARROW = 6, F32_TILE_SPLITK = 7;
 // The kernels that exist: a plan that names anything else is an error at launch.  The 64-row part has no EPI_PATCH kernel: that
 // epilogue derives the output row from the row inside the launch, so a launch cannot start at a row other than 0.
+// The GELU / LayerScale-residual / SwiGLU epilogues have no kernel with a K tail: only the ViT forward asks for them, with
+// K = dim or K = ffn_hidden, both multiples of 64 (anyloc_vit_create), so gemm_nt and anyloc_gemm_plan_describe refuse a tail.
+constexpr bool f32_epilogue_needs_k32(int epi) { return epi == EPI_GELU || epi == EPI_LS_RESID || epi == EPI_SWIGLU; }
 constexpr bool f32_compiled(int epi, int tile, bool rowsq, bool kfull, int abl) {
+  if (f32_epilogue_needs_k32(epi) && !kfull) return false;
   if (tile == F32_TILE_NARROW) return epi == EPI_STORE && !kfull && abl == 0;
   if (tile == F32_TILE_SPLITK) return epi == EPI_STORE && rowsq && kfull && abl == 0;
   if (rowsq) return epi == EPI_STORE && tile == 0 && !kfull && abl == 0;
@@ -521,6 +525,8 @@ int gemm_nt(const GemmProblem& p, int epilogue, hipStream_t stream) {
                    "gemm_nt: operands must be 16-byte aligned");
   ANYLOC_CHECK_ARG((p.M + 127) / 128 * ((p.N + 31) / 32) < (1ll << 31), "gemm_nt: grid too large");
   ANYLOC_CHECK_ARG(epilogue >= EPI_STORE && epilogue <= EPI_PATCH, "gemm_nt: unknown epilogue %d", epilogue);
+  ANYLOC_CHECK_ARG(!f32_epilogue_needs_k32(epilogue) || p.K % 32 == 0, "gemm_nt: epilogue %d needs K %% 32 == 0 (K=%lld)", epilogue,
+                   (long long)p.K);
   ANYLOC_CHECK_ARG(epilogue != EPI_LS_RESID || (p.gamma && p.resid), "gemm_nt: LS_RESID needs gamma and resid");
   ANYLOC_CHECK_ARG(epilogue != EPI_SWIGLU || p.N % 64 == 0, "gemm_nt: SWIGLU needs N %% 64 == 0");
   ANYLOC_CHECK_ARG(epilogue != EPI_PATCH || (p.pos && p.patches > 0), "gemm_nt: PATCH needs pos and patches");
@@ -542,6 +548,8 @@ extern "C" int anyloc_gemm_plan_describe(int64_t M, int64_t N, int64_t K, const 
   for (int i = 0; i < 5; ++i)
     if (std::strcmp(epilogue, names[i]) == 0) epi = i;
   ANYLOC_CHECK_ARG(epi >= 0, "gemm_plan_describe: unknown epilogue \"%s\"", epilogue);
+  ANYLOC_CHECK_ARG(!f32_epilogue_needs_k32(epi) || K % 32 == 0, "gemm_plan_describe: epilogue \"%s\" needs K %% 32 == 0 (K=%lld)", epilogue,
+                   (long long)K);
   static float rowsq_at_hand;                // gemm_f32_plan asks whether the row sums are wanted, never where they go
   GemmProblem p{};
   p.M = M; p.N = N; p.K = K;

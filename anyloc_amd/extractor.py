@@ -147,14 +147,16 @@ def ragged_offsets(sizes, use_cls, patch=PATCH, registers=0):
 class HipDinoV2:
     """Device-resident DINOv2 weights + the C handle of the HIP forward."""
 
-    def __init__(self, name, state_dict, device, max_layer=None, gemm=None):
+    def __init__(self, name, state_dict, device, max_layer=None, gemm=None, patch_k_pad=None):
         # the weight images are quantised by HIP launches and the library allocates the patch-embedding image itself: all of
         # it on the MODEL's device, whatever the current one is
         with _on_device(device):
-            self._build(name, state_dict, device, max_layer, gemm)
+            self._build(name, state_dict, device, max_layer, gemm, patch_k_pad)
 
-    def _build(self, name, state_dict, device, max_layer, gemm):
-        """``gemm``: "x6" runs the block GEMMs as six bf16 MFMA products of exact three-way bf16 splits
+    def _build(self, name, state_dict, device, max_layer, gemm, patch_k_pad=None):
+        """``patch_k_pad``: row length of the patch-embedding weights handed to the library (anyloc_vit_config.patch_k_pad), a
+        multiple of 4 that is at least 3 * patch * patch (the default); the extra columns are zeros.
+        ``gemm``: "x6" runs the block GEMMs as six bf16 MFMA products of exact three-way bf16 splits
         (csrc/gemm_x6.hip); "h3" as three fp16 MFMA products of row-scaled two-term fp16 splits (csrc/gemm_h3.hip);
         both have fp32-level accuracy; "f32" keeps them on the fp32 MFMA kernel.  Env ANYLOC_GEMM sets the default."""
         self.gemm = gemm or os.environ.get("ANYLOC_GEMM", DEFAULT_GEMM)
@@ -183,7 +185,11 @@ class HipDinoV2:
             return t
         self.pos_embed_host = None if self.rope else state_dict["pos_embed"].detach().to("cpu", torch.float32)
         self._pos_cache = {}
-        patch_w = keep(state_dict["patch_embed.proj.weight"].reshape(dim, 3 * P * P))
+        self.patch_k_pad = 3 * P * P if patch_k_pad is None else int(patch_k_pad)
+        if self.patch_k_pad < 3 * P * P or self.patch_k_pad % 4:
+            raise ValueError(f"patch_k_pad must be a multiple of 4 and at least {3 * P * P}, got {patch_k_pad!r}")
+        patch_w = keep(torch.nn.functional.pad(state_dict["patch_embed.proj.weight"].reshape(dim, 3 * P * P),
+                                               (0, self.patch_k_pad - 3 * P * P)))
         patch_b = keep(state_dict["patch_embed.proj.bias"])
         cls = keep(state_dict["cls_token"].reshape(dim))
         if self.n_reg and "register_tokens" not in state_dict:
@@ -254,7 +260,7 @@ class HipDinoV2:
                              float(w12d[hidden:].norm(dim=1).max()), float(b12d[hidden:].abs().max())]
                 for j in range(4):
                     h2[i].fc1_bound[j] = bound[j] * (1.0 + 1e-6)
-        cfg = _lib.VitConfig(dim, depth, heads, self.ffn_kind, hidden, P, 3 * P * P)
+        cfg = _lib.VitConfig(dim, depth, heads, self.ffn_kind, hidden, P, self.patch_k_pad)
         self._handle = C.c_void_p()
         lib = _lib.load()
         _lib.check(lib.anyloc_vit_create(C.byref(self._handle), C.byref(cfg), _lib.ptr(patch_w),

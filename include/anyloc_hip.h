@@ -319,7 +319,9 @@ int anyloc_gemm_nt(const float* A, int64_t lda, const float* W, int64_t ldw,
  *              kernel without a K-tail predicate (K % bk == 0); rowsq = the kernel that also sums the rows' squares; abl = the
  *              kernel variant (0 plain, 8 loads two slabs ahead, 32 chunked summation, 64 LDS-DMA staging, 1 - 4 timing-only
  *              ablations); grid = workgroups of the part's launch
- * Returns ANYLOC_ERR_INVALID_ARG for an unknown epilogue name, a null pointer, sizes that are not positive and K % 4 != 0. */
+ * Returns ANYLOC_ERR_INVALID_ARG for an unknown epilogue name, a null pointer, sizes that are not positive, K % 4 != 0, and for
+ * "gelu" / "ls_resid" / "swiglu" with K % 32 != 0: those epilogues have no kernel with a K tail (the ViT forward, their only
+ * caller, contracts over dim or ffn_hidden, multiples of 64). */
 typedef struct anyloc_gemm_plan_part {
   int64_t row0, rows, grid;
   int32_t tile, tile_rows, tile_cols, bk, kfull, rowsq, abl, reserved;      /* tile = id of the compiled shape (csrc/gemm_f32.hip: kF32Tile) */

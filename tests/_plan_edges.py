@@ -57,6 +57,57 @@ def describe(lib, M, N, K, epilogue, kind, flags):
     return {f: int(getattr(d, f)) for f in _lib.H3_PLAN_FIELDS + ("grid",)}
 
 
+# the forced small-M plans of tests/test_gpu_vit.py::test_small_m_plans_agree_with_the_plain_kernels: (h3s_cfg, h3s_kb, h3s_ksplit,
+# h3s_stages) -- every tile of kSmallTile x five (k-blocks per stage, split-K factor, ring depth) triples
+FORCED_PLANS = [(c, kb, ks, st) for c in range(8) for kb, ks, st in ((1, 1, 3), (2, 3, 6), (4, 2, 3), (1, 8, 6), (2, 5, 3))]
+
+
+# the forced plans the plan function refuses, on every GEMM alike: the four widest tiles (128 x 128, 64 x 256 twice, 192 x 128) hold
+# neither a 6-deep ring of two k-blocks per stage nor a 3-deep ring of four in the CU's 160 KiB of LDS, and fall back to the
+# 3-deep ring / two k-blocks per stage -- what (2, 5, 3) forces anyway
+REFUSED_PLANS = {(c, kb, ks, st) for c in (4, 5, 6, 7) for kb, ks, st in ((2, 3, 6), (4, 2, 3))}
+
+
+H3_SPLIT_PART_BYTES, H3_SPLIT_TICKETS = 48 << 20, 4096       # csrc/common.hpp: the split-K workspace of one launch
+
+
+def forced_ksplit(K, kb, ks, tiles, tile_elems):
+    """the split-K factor h3_plan makes of a forced one (csrc/gemm_h3s.hip): no more splits than k-blocks or than the workspace
+    holds partial tiles for, k-blocks per split a multiple of the forced k-blocks per stage, no empty split"""
+    k16 = K // 16
+    ks = min(ks, k16)
+    while ks > 1 and (ks * tiles * tile_elems * 4 > H3_SPLIT_PART_BYTES or tiles > H3_SPLIT_TICKETS):
+        ks -= 1
+    if ks <= 1:
+        return 1
+    kper = -(-(-(-k16 // ks)) // kb) * kb
+    return max(1, -(-k16 // kper))
+
+
+def forced_plan_is_served(lib, rows, gemms, forced):
+    """Under the options of ``forced`` = (cfg, kb, ksplit, stages), already in force: how would the library run each of ``gemms``
+    ({label: (N, K, epilogue, kind, flags)}, each with the split-K workspace at hand) at ``rows`` rows?  Every GEMM on the small-M
+    route, the forced tile and the split-K factor forced_ksplit restates; then either the forced k-blocks per stage and ring depth
+    -> True (launch it), or, for every GEMM alike, fewer k-blocks / the 3-deep ring because the tile's ring would not fit the
+    LDS -- the plan refuses the combination and names another entry of FORCED_PLANS -> False (asserted here, not to be
+    launched again).  Which combinations are refused is pinned: exactly REFUSED_PLANS."""
+    cfg, kb, ks, st = forced
+    plans = {label: describe(lib, rows, *g) for label, g in gemms.items()}
+    assert all(p["route"] == 0 and p["tile"] == cfg for p in plans.values()), (forced, plans)
+    for label, (N, K, _, _, flags) in gemms.items():
+        assert flags & WS and not flags & ACC, label
+        p = plans[label]
+        assert p["ksplit"] == forced_ksplit(K, kb, ks, p["tiles_m"] * p["tiles_n"], p["tile_rows"] * p["tile_cols"]), (forced, label, p)
+    took = {(p["kb"], p["stages"]) for p in plans.values()}
+    assert len(took) == 1, (forced, took)                  # what a tile's ring can hold does not depend on the GEMM
+    served = took == {(kb, st)}
+    assert served == (forced not in REFUSED_PLANS), (forced, took)
+    if not served:
+        (kb1, st1), = took
+        assert kb1 <= kb and st1 <= st and (kb1, st1) in {(k, s) for c, k, _, s in FORCED_PLANS if c == cfg}, (forced, took)
+    return served
+
+
 def decision(plan):
     return tuple(plan[f] for f in DECISION)
 

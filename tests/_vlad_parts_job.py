@@ -21,7 +21,8 @@ def l2rel(a, b):
 
 def main():
     worst = 0.0
-    for K, D, N, n_img in ((32, 1536, 529, 5), (8, 384, 256, 3), (17, 768, 100, 7)):
+    # (D = 1024: the only width whose exact-score kernel and 4-wave screening kernel no other VLAD test launches)
+    for K, D, N, n_img in ((32, 1536, 529, 5), (8, 384, 256, 3), (17, 768, 100, 7), (12, 1024, 150, 4)):
         centers = 0.7 * synth.clustered_tokens(1, K, D, n_modes=K, seed=K)[0]
         first = None
         for rep in range(4):

@@ -15,6 +15,9 @@ from anyloc_amd import _lib
 
 ERR_INVALID_ARG = -1
 EPILOGUES = ("store", "gelu", "ls_resid", "swiglu", "patch")
+# the epilogues that have kernels with a K tail (K % 32 != 0); "gelu" / "ls_resid" / "swiglu" are refused there: the ViT forward,
+# their only caller, contracts over dim or ffn_hidden, multiples of 64 (csrc/gemm_f32.hip: f32_epilogue_needs_k32)
+K_TAIL_EPILOGUES = ("store", "patch")
 SWEEP_M = np.concatenate([np.arange(1, 6001), np.arange(21000, 22001), np.arange(32000, 33001), np.arange(65000, 66001)])
 SWEEP_N = (1, 32, 33, 128, 257, 384, 1152, 1536, 4608, 8192)
 SWEEP_K = (4, 32, 36, 64, 8192, 8196)
@@ -30,9 +33,9 @@ COMPILED = {(NARROW, 0, 0, 0): ("store",), (NARROW, 0, 1, 0): ("store",),
             (0, 1, 0, 1): ("store",), (0, 1, 0, 2): ("store",), (0, 1, 0, 3): ("store",), (0, 1, 0, 4): ("store",),
             (0, 1, 0, 64): EPILOGUES,
             (HALF, 1, 0, 0): ("store", "gelu", "ls_resid", "swiglu"),   # the 64-row part: no patch epilogue
-            (4, 0, 0, 8): EPILOGUES, (4, 1, 0, 8): EPILOGUES}
-COMPILED.update({(t, kf, 0, 0): EPILOGUES for t in (0, 1, 2, 3, 4) for kf in (0, 1)})
-COMPILED.update({(0, kf, 0, 8): EPILOGUES for kf in (0, 1)})
+            (4, 0, 0, 8): K_TAIL_EPILOGUES, (4, 1, 0, 8): EPILOGUES}
+COMPILED.update({(t, kf, 0, 0): EPILOGUES if kf else K_TAIL_EPILOGUES for t in (0, 1, 2, 3, 4) for kf in (0, 1)})
+COMPILED.update({(0, kf, 0, 8): EPILOGUES if kf else K_TAIL_EPILOGUES for kf in (0, 1)})
 # option gemm_f32_cfg -> (tile, ABL) of a wide call (N > 32, no row sums); ABL of 5 and 20 where the kernel exists, else 0
 CFG_TILE = {1: (1, 0), 2: (2, 0), 3: (3, 0), 4: (4, 0), 5: (0, 1), 10: (0, 8), 11: (4, 8), 20: (0, 64)}
 
@@ -108,6 +111,13 @@ def describe(lib, M, N, K, epilogue, rowsq=0):
 
 
 _SWEEP = {}
+
+
+def refused(lib, M, N, K, epilogue, rowsq=0):
+    """the library refuses to plan this call, and says which epilogue needs what"""
+    d = _lib.GemmPlanDesc()
+    st = lib.anyloc_gemm_plan_describe(M, N, K, epilogue.encode(), rowsq, C.byref(d))
+    return st == ERR_INVALID_ARG and b"needs K % 32 == 0" in lib.anyloc_last_error()
 
 
 def sweep(lib, N, K, epilogue, rowsq):
@@ -196,6 +206,9 @@ def test_every_plan_covers_its_rows_on_compiled_kernels(lib, model_m1, options):
         _set(lib, options)
         for N, K, epi, rowsq in itertools.product(SWEEP_N, SWEEP_K, EPILOGUES, (0, 1)):
             case = (N, K, epi, rowsq, options)
+            if K % 32 != 0 and epi not in K_TAIL_EPILOGUES:        # no kernel with a K tail: refused at every M, under every option
+                assert all(refused(lib, int(m), N, K, epi, rowsq) for m in SWEEP_M[::61]), case
+                continue
             p = sweep(lib, N, K, epi, rowsq)
             if check(p, SWEEP_M, N, K, epi, rowsq, cfg, case):
                 got = m1_of(p, SWEEP_M)
@@ -212,7 +225,8 @@ def test_pinned_cuts(lib):
             p = describe(lib, M, N, 64, epi)
             assert int(m1_of(p[None], np.array([M]))[0]) == m1, (M, N, epi, p)
             assert p["parts"] == (2 if 0 < m1 < M else 1), (M, N, epi, p)
-        assert describe(lib, M, N, 64, "patch")["parts"] == 1 and describe(lib, M, N, 36, "gelu")["parts"] == 1
+        assert describe(lib, M, N, 64, "patch")["parts"] == 1 and describe(lib, M, N, 36, "patch")["parts"] == 1
+        assert refused(lib, M, N, 36, "gelu")
 
 
 def test_describe_rejects_what_it_cannot_answer(lib):
@@ -228,3 +242,4 @@ def test_describe_rejects_what_it_cannot_answer(lib):
     assert b"gemm_plan_describe" in lib.anyloc_last_error()
     for name in EPILOGUES:
         assert lib.anyloc_gemm_plan_describe(1025, 8192, 32, name.encode(), 1, C.byref(d)) == 0, name
+        assert refused(lib, 1025, 8192, 36, name) == (name not in K_TAIL_EPILOGUES), name

@@ -192,6 +192,93 @@ def test_every_qkv_route_rotates(B):
     c.check(got, imgs, [(1, "token")], False, f"plan {QKV_PLANS[B]} B={B} M={201 * B}")
 
 
+def _v3_gemms():
+    """the block GEMMs of dinov3_vits16 as the fused forward launches them (the rotating qkv epilogue has the plans of
+    "qkv_planes": csrc/common.hpp plan_epilogue)"""
+    import _plan_edges as pe
+    return pe, _lib_handle(), pe.block_gemms("dinov3_vits16")
+
+
+def _lib_handle():
+    from anyloc_amd import _lib
+    return _lib.load()
+
+
+def _token_forward(c, imgs, what, check=True):
+    """layer-1 tokens of the 2-block model on the h3 kernels, without the FFN re-run that would hide which kernels produced
+    them; held to the restatement under the bars of test_every_qkv_route_rotates"""
+    m = c.model("h3")
+    prev, m.ffn_check = m.ffn_check, False
+    try:
+        got = m.forward_taps(imgs.to(DEV), [(1, "token")]).clone()
+    finally:
+        m.ffn_check = prev
+    if check:
+        c.check(got, imgs, [(1, "token")], False, what)
+    return got
+
+
+@pytest.mark.parametrize("B", [1, 3])
+def test_every_small_m_plan_rotates(B):
+    """The rotating qkv epilogue on every small-M kernel (tile x k-blocks per stage x ring depth), where
+    test_every_qkv_route_rotates meets the table's choices only: the forced plans of
+    tests/test_gpu_vit.py::test_small_m_plans_agree_with_the_plain_kernels on one and three 224 x 224 images (201 and 603
+    rows), each held to the restatement under this file's bars and bit-identical on a second run; a combination the plan
+    refuses is asserted as a refusal and not launched."""
+    from anyloc_amd import ops
+    pe, lib, gemms = _v3_gemms()
+    c = _case("s2")
+    imgs = _images((224, 224), B, 5)
+    launched = 0
+    for forced in pe.FORCED_PLANS:
+        cfg, kb, ks, st = forced
+        with ops.options(h3s_cfg=cfg, h3s_kb=kb, h3s_ksplit=ks, h3s_stages=st):
+            if not pe.forced_plan_is_served(lib, 201 * B, gemms, forced):
+                continue
+            got = _token_forward(c, imgs, f"forced plan {forced} B={B}")
+            assert torch.equal(got, _token_forward(c, imgs, "", check=False)), (forced, "not reproducible")
+        launched += 1
+    assert launched == len(pe.FORCED_PLANS) - len(pe.REFUSED_PLANS) == 32
+
+
+@pytest.mark.parametrize("cfg", [1, 2, 3, 4, 5])
+def test_every_batched_tile_rotates(cfg):
+    """Option h3_cfg = 1 ... 5 sends every GEMM to kH3Tile[cfg] at every size: the rotating qkv epilogue on those five tiles (three
+    224 x 224 images, 603 rows: a partial last tile of 128 and of 256 rows), held to the restatement."""
+    from anyloc_amd import ops
+    pe, lib, gemms = _v3_gemms()
+    c = _case("s2")
+    imgs = _images((224, 224), 3, 5)
+    with ops.options(h3_cfg=cfg):
+        d = pe.describe(lib, 603, *gemms["qkv"])
+        assert (d["route"], d["tile"], d["lead"]) == (H3_ROUTE_BATCHED, cfg, 0), d
+        _token_forward(c, imgs, f"h3_cfg {cfg}")
+
+
+@pytest.mark.parametrize("B", [1, 65])
+def test_layernorm_lead_role_in_front_of_the_rotating_epilogue(B):
+    """LayerNorm 1 as the lead role of the qkv GEMM's own launch with the rotating epilogue: one image (option h3s_ln_lead, on the
+    one plan the small-M role is compiled for -- 128 x 128 tiles, 6-deep ring, forced on the qkv GEMM alone, since ViT-S's
+    narrow qkv is not given that plan by the table) and 65 images (option h3_ln_lead, the batched role).  The library's plan
+    must name the role; the tokens must be the bits of the separate launches -- the bar of
+    tests/test_gpu_round6.py::test_layernorm_lead_role_gives_the_bits_of_the_separate_launch -- and meet the restatement."""
+    from anyloc_amd import ops
+    pe, lib, gemms = _v3_gemms()
+    c = _case("s2")
+    imgs = _images((224, 224), B, 5)
+    plan = dict(h3s_mask=1, h3s_cfg=4, h3s_kb=1, h3s_ksplit=1, h3s_stages=6) if B == 1 else {}
+    lead = "h3s_ln_lead" if B == 1 else "h3_ln_lead"
+    with ops.options(**plan):
+        with ops.options(**{lead: 0}):
+            assert pe.describe(lib, 201 * B, *gemms["qkv"])["lead"] == 0
+            want = _token_forward(c, imgs, f"separate LayerNorm B={B}")
+        with ops.options(**{lead: 1}):
+            d = pe.describe(lib, 201 * B, *gemms["qkv"])
+            assert d["lead"] == (1 if B == 1 else 2), d
+            for rep in range(5):
+                assert torch.equal(_token_forward(c, imgs, "", check=False), want), (B, rep, "the lead-role forward differs")
+
+
 # ---------------------------------------------------------------- 3. taps are pre-rotation, later layers see the rotation ----
 
 @pytest.mark.parametrize("mode", MODES)
@@ -302,13 +389,16 @@ def test_rope_rows_alone(ragged):
 
 # ---------------------------------------------------------------- 6. the new block shape ----
 
-@pytest.mark.parametrize("mode", ["h3", "f32"])
+@pytest.mark.parametrize("mode", ["h3", "f32", "x6"])
 def test_vith16plus_block_shape(mode):
-    """D = 1280, 20 heads, gated mlp with hidden 5120: 2 blocks, B = 2 at 64 x 96."""
+    """D = 1280, 20 heads, gated mlp with hidden 5120: 2 blocks, B = 2 at 64 x 96 (x6: the only width with five float4 per lane in
+    layernorm_x3_kernel)."""
+    from anyloc_amd import ops
     c = _case("hplus")
     m = c.model(mode)
     imgs = _images((64, 96), 2, 7)
-    got = m.forward_taps(imgs.to(DEV), [(1, "token")])
+    with ops.options(**({"x6_min_rows": 0} if mode == "x6" else {})):       # (few rows would run the fp32 kernels under "x6")
+        got = m.forward_taps(imgs.to(DEV), [(1, "token")])
     assert got.shape == (2, 24, 1280)
     c.check(got, imgs, [(1, "token")], False, f"vith16plus {mode}")
 

@@ -208,6 +208,71 @@ def test_small_m_plans_agree_with_the_plain_kernels(batch):
         weights.unregister_state_dict(name)
 
 
+def _forced_plans_agree(name, depth, layer, hw, batch, seed, gemms, rows, **build_options):
+    """The table's plan and every plan of _plan_edges.FORCED_PLANS on ``batch`` images of ``hw`` x ``hw`` pixels through a
+    ``depth``-block ``name`` (built under ``build_options``): within 2e-6 of the round-3 kernels (h3s_enable = 0) and
+    bit-identical on a second run -- the bar of test_small_m_plans_agree_with_the_plain_kernels.  Before a forced plan is launched
+    the library is asked how it would run each GEMM of ``gemms`` at ``rows`` token rows (_plan_edges.forced_plan_is_served): a
+    combination the plan refuses is asserted as a refusal and not launched.  -> plans launched."""
+    import _plan_edges as pe
+    import utilities
+    from anyloc_amd import _lib, ops
+    lib = _lib.load()
+    weights.register_state_dict(name, synth.synthetic_state_dict(name, seed, device=DEV, depth=depth))
+    try:
+        with ops.options(**build_options):
+            ext = utilities.DinoV2ExtractFeatures(name, layer, "value", device=DEV)
+        ext.dino_model.ffn_check = False
+        if "h3_swiglu_t" in build_options:                                        # the option was read: the handle got that layout
+            assert ext.dino_model.fc1_layout == build_options["h3_swiglu_t"]
+        img = torch.randn(batch, 3, hw, hw, generator=torch.Generator().manual_seed(seed + batch)).to(DEV)
+        with ops.options(h3s_enable=0):
+            want = ext(img).clone()
+        got = ext(img).clone()
+        assert got.shape[0] == batch and got.shape[1] == rows // batch - 1 and torch.isfinite(got).all()
+        assert float((got - want).abs().max()) <= 2e-6
+        assert torch.equal(got, ext(img))
+        for g in gemms.values():
+            assert pe.describe(lib, rows, *g)["route"] == 0, g                    # the small-M plan table serves every GEMM
+        launched = 0
+        for cfg, kb, ks, st in pe.FORCED_PLANS:
+            with ops.options(h3s_cfg=cfg, h3s_kb=kb, h3s_ksplit=ks, h3s_stages=st):
+                if not pe.forced_plan_is_served(lib, rows, gemms, (cfg, kb, ks, st)):
+                    continue
+                a = ext(img).clone()
+                b = ext(img)
+            assert float((a - want).abs().max()) <= 2e-6, (cfg, kb, ks, st, float((a - want).abs().max()))
+            assert torch.equal(a, b), (cfg, kb, ks, st, "not reproducible")
+            launched += 1
+        return launched
+    finally:
+        weights.unregister_state_dict(name)
+
+
+@pytest.mark.parametrize("batch", [1, 2])
+def test_small_m_plans_agree_on_a_gelu_model(batch):
+    """The small-M plans under the GELU epilogue (ViT-S/B/L; test_small_m_plans_agree_with_the_plain_kernels is a SwiGLU ViT-g):
+    dinov2_vitb14, 2 blocks, layer 1 'value', one and two 224 x 224 images = 257 token rows each -- one live row in the last
+    64-row tile.  qkv, proj, fc1 (GELU + quantise), fc2 and the facet GEMM go through the table's plan and every forced one."""
+    import _plan_edges as pe
+    launched = _forced_plans_agree("dinov2_vitb14", 2, 1, 224, batch, 20, pe.block_gemms("dinov2_vitb14"), 257 * batch)
+    assert launched == len(pe.FORCED_PLANS) - len(pe.REFUSED_PLANS) == 32
+
+
+@pytest.mark.parametrize("batch", [1, 2])
+def test_small_m_plans_agree_on_the_interleaved_swiglu_layout(batch):
+    """The same on a 3-block ViT-g built under h3_swiglu_t = 0: its w12 GEMM runs the LDS-transposing SWIGLU_H2 epilogue of the
+    32 / 32 gate / value interleave, where test_small_m_plans_agree_with_the_plain_kernels runs SWIGLU_T_H2 (322 x 322: 530 rows
+    per image)."""
+    import _plan_edges as pe
+    gemms = dict(pe.block_gemms("dinov2_vitg14"))
+    N, K, epi, kind, flags = gemms["fc1"]
+    assert epi == "swiglu_t_h2"
+    gemms["fc1"] = (N, K, "swiglu_h2", kind, flags)
+    launched = _forced_plans_agree("dinov2_vitg14", 3, 2, 322, batch, 30, gemms, 530 * batch, h3_swiglu_t=0)
+    assert launched == len(pe.FORCED_PLANS) - len(pe.REFUSED_PLANS) == 32
+
+
 def test_split_k_hand_off_under_load():
     """The split-K hand-off of gemm_h3_kernel.hpp (write-through sc1 slab stores, every wave drained, ONE relaxed agent-scope
     ticket, the last arrival reads the slabs back with sc1 loads in split order) under load: a 3-block ViT-g forward at one

@@ -8,8 +8,9 @@ all (a float64 search against itself gives 0; under fp32 rounding far less than 
 asserts from the profile that the leading-plane GEMM ran and the exact one did not: no silent fallback.
 
 The multi-slice path is reached at small shapes with ``topk_rescore_cols = 4096`` (8 208 columns: two slices and a 16-column
-third) and by every shape above 49 152 columns under the default slice.  What no test here reaches: TWO column ranges at
-> 65 535 columns -- more than 130 000 rows of >= 256 KiB each do not fit a seconds-long test; the sizes of that path are pinned
+third) and by every shape above 49 152 columns under the default slice; ``topk_rescore_cols`` = 8 192 ... 45 056 reaches the
+remaining instantiations of the two sliced kernels (test_every_slice_width_gives_the_lists_of_one_slice).  What no test here
+reaches: TWO column ranges at > 65 535 columns -- more than 130 000 rows of >= 256 KiB each do not fit a seconds-long test; the sizes of that path are pinned
 by tests/test_topk_wide_screen_cpu.py and it was run once by tools/time_wide_screen.py (profiles/wide_screen_timing.md)."""
 import pytest
 import torch
@@ -140,6 +141,73 @@ def test_slices_of_4096_columns_give_the_lists_of_one_slice(nq, ndb, dim, k, met
         ref = s if tag == "one-shot" else s_index
         _check(d, i, ref, k, metric, f"{tag}, slices of 4096, {nq}x{ndb}x{dim} {metric}")
         _check(d1, i1, ref, k, metric, f"{tag}, one slice, {nq}x{ndb}x{dim} {metric}")
+        assert torch.equal(i, i1), tag
+        assert float((d - d1).abs().max()) <= BAR[metric], (tag, float((d - d1).abs().max()))
+
+
+def _graded(nq, ndb, dim, seed):
+    """(queries, rows) drawn with a CPU generator whose float64 cosines are PRESCRIBED: row r is Q^+ t_r plus a unit vector
+    orthogonal to every query, so that q_i . d_r = t_r[i] -- per query a permutation of a ladder of ndb values, the best eight
+    4e-5 apart (true neighbours closer to each other than the screening bound), the rest 6e-4 apart, all in [-0.09, 0.09] (the
+    70 prescribed cosines of a row then take a quarter of its unit length).  No two scores of a query are closer than 4e-5
+    (8e-5 under L2): 13 x / 8 x the bar, so no float64 near-tie can excuse a differing entry -- _no_near_ties asserts it on the
+    fp32 data.  Rows are then scaled by 0.3 ... 2.3 as in _data (the search normalises them)."""
+    g = torch.Generator().manual_seed(seed)
+    q = torch.nn.functional.normalize(torch.randn(nq, dim, generator=g, dtype=torch.float64))
+    ladder = 0.09 - torch.cat([4e-5 * torch.arange(8, dtype=torch.float64), 4e-5 * 8 + 6e-4 * torch.arange(ndb - 8, dtype=torch.float64)])
+    t = torch.stack([ladder[torch.randperm(ndb, generator=g)] for _ in range(nq)])         # [nq, ndb]: t[i, r] = q_i . d_r
+    gram = q @ q.t()
+    in_span = torch.linalg.solve(gram, t).t() @ q                                          # [ndb, dim]: Q^+ t_r
+    n = torch.randn(ndb, dim, generator=g, dtype=torch.float64)
+    n = torch.nn.functional.normalize(n - torch.linalg.solve(gram, q @ n.t()).t() @ q)    # unit, orthogonal to every query
+    left = 1.0 - (in_span * in_span).sum(1, keepdim=True)
+    assert float(left.min()) > 0.5
+    d = (in_span + left.sqrt() * n) * (0.3 + 2.0 * torch.rand(ndb, 1, generator=g, dtype=torch.float64))
+    return q.float().to(DEV), d.float().to(DEV)
+
+
+def _no_near_ties(s, k, metric):
+    """the best k + 1 float64 scores of every query lie further apart than four bars -> the smallest gap"""
+    top = torch.sort(s, dim=1, descending=True).values[:, :k + 1]
+    gap = float((top[:, :-1] - top[:, 1:]).min())
+    assert gap > 4 * BAR[metric], gap
+    return gap
+
+
+# option value -> the instantiations it selects: NJ of screen_rescore_sliced_kernel (2 048 columns per register group; 12 288 is
+# six groups in the <8> kernel, 20 480 ten in the <16>, 45 056 twenty-two in the <24>) and NU of
+# screen_rescore_planes_sliced_kernel (4 096 columns per group, slices capped at 32 768)
+SLICE_WIDTHS = {8192: (4, 2), 12288: (8, 4), 16384: (8, 4), 20480: (16, 8), 32768: (16, 8), 45056: (24, 8)}
+SLICED = [(cols, cols + 16, "ip") for cols in SLICE_WIDTHS] + [(cols, 2 * cols, "l2") for cols in (8192, 16384)]
+
+
+@pytest.mark.parametrize("cols,dim,metric", SLICED)
+def test_every_slice_width_gives_the_lists_of_one_slice(cols, dim, metric):
+    """``topk_rescore_cols`` from 8 192 to 45 056: every instantiation of the two sliced re-scoring kernels that the 4 096-column
+    and default slices of the tests above leave out (SLICE_WIDTHS), on 70 queries x 300 rows: one full slice and a 16-column one
+    (inner product), exactly two slices (L2).  One-shot, rows kept and rows free, each against float64 under the bars of
+    test_slices_of_4096_columns_give_the_lists_of_one_slice and against the same call on the single-slice kernels (option 0):
+    identical index lists, distances within the bar.  The data (_graded) has no float64 near-tie, so _check's allowance for
+    differing entries is not drawn on: not one entry may differ."""
+    from anyloc_amd import ops
+    nq, ndb, k = 70, 300, 20
+    nj, nu = SLICE_WIDTHS[cols]
+    assert (cols // 4 + 511) // 512 in range(nj // 2 + 1, nj + 1) and (min(cols, 32768) // 8 + 511) // 512 in range(nu // 2 + 1, nu + 1)
+    _CASE.clear()
+    qu, db = _graded(nq, ndb, dim, 1000 + cols // 4096 + (0 if metric == "ip" else 50))
+    s = _exact64(qu, db, metric)
+    s_index = _as_flat_index_scores_them(qu, db, s, metric)[1]
+    print(f"smallest gap among the best {k + 1}: {_no_near_ties(s, k, metric):.2e}, as the index scores them {_no_near_ties(s_index, k, metric):.2e}")
+    with ops.options(topk_rescore_cols=cols, **SCREEN):
+        assert ops.get_option("topk_rescore_cols") == cols
+        sliced = _three_searches(qu, db, k, metric)
+    assert ops.get_option("topk_rescore_cols") == 0
+    with ops.options(**SCREEN):
+        whole = _three_searches(qu, db, k, metric)
+    for (tag, (d, i)), (_, (d1, i1)) in zip(sliced, whole):
+        ref = s if tag == "one-shot" else s_index
+        assert _check(d, i, ref, k, metric, f"{tag}, slices of {cols}, {nq}x{ndb}x{dim} {metric}") == 0
+        assert _check(d1, i1, ref, k, metric, f"{tag}, one slice, {nq}x{ndb}x{dim} {metric}") == 0
         assert torch.equal(i, i1), tag
         assert float((d - d1).abs().max()) <= BAR[metric], (tag, float((d - d1).abs().max()))
 
