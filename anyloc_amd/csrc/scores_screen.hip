@@ -218,42 +218,94 @@ __global__ __launch_bounds__(PLAN_NT) void screen_overflow_plan_kernel(const int
 }
 
 // ---------------------------------------------------------------------------------------------------------- re-score
-// One workgroup of 512 threads per query: the query row sits in registers (thread t holds columns 4 t + 2048 j .. + 3,
-// j < NJ: dim <= 2048 NJ), the candidate rows are read once each, FOUR per step (coalesced 16-byte loads, four rows' loads in
-// flight per thread and column group), products and sums in float64, one fixed reduction tree per step: deterministic.
+// One workgroup of 512 threads per query.  The query row -- or, SLICED, one column slice of it after the other -- sits in the
+// registers of a Source, the candidate rows are read once each, FOUR per step (RS_G: four rows' loads in flight per thread and
+// column group), products and sums in float64, one fixed reduction tree per step (wave shuffles, then the eight waves' partial
+// sums through LDS as ((0+1)+(2+3))+((4+5)+(6+7))): deterministic.  A short last group re-reads its last row; the copy is
+// neither stored nor added.
+// !SLICED: the whole row is one slice (the slice loop folds away) and a step's totals are stored at once.
+// SLICED serves rows of ANY width: the columns are cut into slices of `slice` columns (a multiple of 4096 that the Source's
+// registers hold; the last one may be short), per slice the Source loads the query slice and the candidate loop runs over that
+// slice's columns of every candidate row, and a step's four totals are added to the candidates' float64 accumulators in LDS
+// (tot_s: SCREEN_CMAX doubles, 4 KiB).  Slices are added in ascending column order: deterministic, and for a row of one slice
+// 0 + total, the bits of !SLICED.  Every byte of a candidate row is still read exactly once.
+// A Source owns what differs between the fp32 rows and the planes of a prepared index: load_query(the query's columns from
+// col0 on, how many of them), accumulate(four candidate columns, col0, the four float64 sums of this thread) and
+// value(a candidate's float64 total, its column) -> the fp32 score; SLICE_COLS is the widest slice its kernels are compiled for.
 constexpr int RS_G = 4;
-template <int NJ>
-__global__ __launch_bounds__(512) void screen_rescore_kernel(const float* __restrict__ queries, const float* __restrict__ db,
-                                                             int64_t dim, int cmax, const int* __restrict__ cand,
-                                                             const int* __restrict__ count, int metric, const float* __restrict__ qn,
-                                                             const float* __restrict__ dn, const float* __restrict__ dnorm,
-                                                             float* __restrict__ cand_v) {
-  __shared__ double red[8][RS_G];
+template <bool SLICED, class Source>
+__device__ __forceinline__ void screen_rescore_body(Source& src, double (&red)[8][RS_G], double* tot_s, const float* __restrict__ queries,
+                                                    int64_t dim, int64_t slice, int cmax, const int* __restrict__ cand,
+                                                    const int* __restrict__ count, int metric, const float* __restrict__ qn,
+                                                    const float* __restrict__ dn, const float* __restrict__ dnorm,
+                                                    float* __restrict__ cand_v) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t q = blockIdx.x;
   const int n = min(count[q], cmax);
-  const int n4 = (int)(dim >> 2);
-  f32x4 qv[NJ];
+  // (the query's norm is read where a value is stored: held across the loops it costs screen_rescore_sliced_kernel<24> its last register)
+  auto store = [&](int i, double tot) {
+    const int ci = cand[q * cmax + i];
+    cand_v[q * cmax + i] = screen_value(src.value(tot, ci), ci, metric, metric ? qn[q] : 0.f, dn, dnorm);
+  };
+  if constexpr (SLICED)
+    for (int i = tid; i < n; i += 512) tot_s[i] = 0.0;   // (first touched again after the barrier of a step)
+  const int ncol = (int)dim, nslice = SLICED ? (int)slice : ncol;
+  int col0 = 0;
+  do {
+    src.load_query(queries + q * dim + col0, min(nslice, ncol - col0));
+    for (int i0 = 0; i0 < n; i0 += RS_G) {
+      int c[RS_G];
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int idx = tid + 512 * j;
-    qv[j] = idx < n4 ? reinterpret_cast<const f32x4*>(queries + q * dim)[idx] : f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  const float qq = metric ? qn[q] : 0.f;
-  for (int i0 = 0; i0 < n; i0 += RS_G) {
-    int c[RS_G];
-    const f32x4* dr[RS_G];
+      for (int g = 0; g < RS_G; ++g) c[g] = cand[q * cmax + min(i0 + g, n - 1)];
+      double s[RS_G];
 #pragma unroll
-    for (int g = 0; g < RS_G; ++g) {
-      c[g] = cand[q * cmax + min(i0 + g, n - 1)];        // (a short last group re-reads its last row; the copy is not stored)
-      dr[g] = reinterpret_cast<const f32x4*>(db + (int64_t)c[g] * dim);
+      for (int g = 0; g < RS_G; ++g) s[g] = 0.0;
+      src.accumulate(c, col0, s);
+#pragma unroll
+      for (int g = 0; g < RS_G; ++g) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s[g] += __shfl_xor(s[g], off, 64);
+        if (lane == 0) red[wave][g] = s[g];
+      }
+      __syncthreads();
+      if (tid < RS_G && i0 + tid < n) {
+        const double tot = ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid])) + ((red[4][tid] + red[5][tid]) + (red[6][tid] + red[7][tid]));
+        if constexpr (SLICED) tot_s[i0 + tid] += tot;
+        else store(i0 + tid, tot);
+      }
+      __syncthreads();
     }
-    double s[RS_G];
-#pragma unroll
-    for (int g = 0; g < RS_G; ++g) s[g] = 0.0;
+    col0 += nslice;
+  } while (SLICED && col0 < ncol);
+  if constexpr (SLICED)
+    for (int i = tid; i < n; i += 512) store(i, tot_s[i]);   // (n > 0: the last step ended with a barrier)
+}
+
+// The fp32 rows `db` [*, dim]: thread t holds query columns 4 t + 2048 j .. + 3 of the slice, j < NJ (a slice of <= 2048 NJ
+// columns), and reads the same columns of the four rows (coalesced 16-byte loads).
+template <int NJ>
+struct RescoreRows {
+  static constexpr int64_t SLICE_COLS = 2048 * 24;
+  const float* __restrict__ db;
+  int64_t dim;
+  int n4;
+  f32x4 qv[NJ];
+
+  __device__ __forceinline__ void load_query(const float* __restrict__ qrow, int ncols) {
+    n4 = ncols >> 2;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const int idx = tid + 512 * j;
+      const int idx = (int)threadIdx.x + 512 * j;
+      qv[j] = idx < n4 ? reinterpret_cast<const f32x4*>(qrow)[idx] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+  __device__ __forceinline__ void accumulate(const int (&c)[RS_G], int col0, double (&s)[RS_G]) {
+    const f32x4* dr[RS_G];
+#pragma unroll
+    for (int g = 0; g < RS_G; ++g) dr[g] = reinterpret_cast<const f32x4*>(db + (int64_t)c[g] * dim + col0);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int idx = (int)threadIdx.x + 512 * j;
       if (idx < n4) {
         f32x4 d[RS_G];
 #pragma unroll
@@ -264,133 +316,60 @@ __global__ __launch_bounds__(512) void screen_rescore_kernel(const float* __rest
                   ((double)qv[j][2] * (double)d[g][2] + (double)qv[j][3] * (double)d[g][3]);
       }
     }
-#pragma unroll
-    for (int g = 0; g < RS_G; ++g) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) s[g] += __shfl_xor(s[g], off, 64);
-      if (lane == 0) red[wave][g] = s[g];
-    }
-    __syncthreads();
-    if (tid < RS_G && i0 + tid < n) {
-      const double tot = ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid])) + ((red[4][tid] + red[5][tid]) + (red[6][tid] + red[7][tid]));
-      cand_v[q * cmax + i0 + tid] = screen_value((float)tot, cand[q * cmax + i0 + tid], metric, qq, dn, dnorm);
-    }
-    __syncthreads();
   }
-}
+  __device__ __forceinline__ float value(double tot, int) const { return (float)tot; }
+};
+static_assert(RescoreRows<1>::SLICE_COLS == SCREEN_RESCORE_COLS, "the plan's widest slice is the rows kernels'");
 
-// The same for rows of ANY width: the columns are cut into slices of `slice` <= 2048 NJ columns (a multiple of 4096; the last one
-// may be short).  Per slice the query slice is loaded into the registers and the candidate loop above runs over that slice's columns
-// of every candidate row -- four rows per step, float64, the same wave / LDS tree -- and the step's four totals are added to the
-// candidates' float64 accumulators in LDS (SCREEN_CMAX doubles: 4 KiB).  Slices are added in ascending column order: deterministic,
-// and for a row of one slice 0 + total, the bits of the kernel above.  Every byte of a candidate row is still read exactly once.
-template <int NJ>
-__global__ __launch_bounds__(512) void screen_rescore_sliced_kernel(const float* __restrict__ queries, const float* __restrict__ db,
-                                                                    int64_t dim, int64_t slice, int cmax, const int* __restrict__ cand,
-                                                                    const int* __restrict__ count, int metric, const float* __restrict__ qn,
-                                                                    const float* __restrict__ dn, const float* __restrict__ dnorm,
-                                                                    float* __restrict__ cand_v) {
-  __shared__ double red[8][RS_G];
-  __shared__ double tot_s[SCREEN_CMAX];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t q = blockIdx.x;
-  const int n = min(count[q], cmax);
-  for (int i = tid; i < n; i += 512) tot_s[i] = 0.0;     // (first touched again after the barrier of a step)
-  for (int64_t col0 = 0; col0 < dim; col0 += slice) {
-    const int n4 = (int)(min(slice, dim - col0) >> 2);
-    f32x4 qv[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int idx = tid + 512 * j;
-      qv[j] = idx < n4 ? reinterpret_cast<const f32x4*>(queries + q * dim + col0)[idx] : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    for (int i0 = 0; i0 < n; i0 += RS_G) {
-      const f32x4* dr[RS_G];
-#pragma unroll
-      for (int g = 0; g < RS_G; ++g)                       // (a short last group re-reads its last row; the copy is not added)
-        dr[g] = reinterpret_cast<const f32x4*>(db + (int64_t)cand[q * cmax + min(i0 + g, n - 1)] * dim + col0);
-      double s[RS_G];
-#pragma unroll
-      for (int g = 0; g < RS_G; ++g) s[g] = 0.0;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int idx = tid + 512 * j;
-        if (idx < n4) {
-          f32x4 d[RS_G];
-#pragma unroll
-          for (int g = 0; g < RS_G; ++g) d[g] = dr[g][idx];
-#pragma unroll
-          for (int g = 0; g < RS_G; ++g)
-            s[g] += ((double)qv[j][0] * (double)d[g][0] + (double)qv[j][1] * (double)d[g][1]) +
-                    ((double)qv[j][2] * (double)d[g][2] + (double)qv[j][3] * (double)d[g][3]);
-        }
-      }
-#pragma unroll
-      for (int g = 0; g < RS_G; ++g) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s[g] += __shfl_xor(s[g], off, 64);
-        if (lane == 0) red[wave][g] = s[g];
-      }
-      __syncthreads();
-      if (tid < RS_G && i0 + tid < n)
-        tot_s[i0 + tid] += ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid])) + ((red[4][tid] + red[5][tid]) + (red[6][tid] + red[7][tid]));
-      __syncthreads();
-    }
-  }
-  const float qq = metric ? qn[q] : 0.f;
-  for (int i = tid; i < n; i += 512)                       // (n > 0: the last step ended with a barrier)
-    cand_v[q * cmax + i] = screen_value((float)tot_s[i], cand[q * cmax + i], metric, qq, dn, dnorm);
-}
-
-// ------------------------------------------------------------------------------------------ re-score from the index
-// The same re-scoring WITHOUT the fp32 rows (ANYLOC_TOPK_RESCORE_PLANES): a candidate row is read from the two fp16 planes of
-// the prepared index (topk.hip: index_view), whose sum (hi + lo) 2^-e IS the database the index holds -- every element within
-// 2^-23 of its row's maximum, the operands the unscreened indexed search scores.  Candidate column c of the range that starts
-// at database row s0 is global row r = s0 + c = panel p, local row lr; panel p's image starts at img + p * slot and has
+// WITHOUT the fp32 rows (ANYLOC_TOPK_RESCORE_PLANES): a candidate row is read from the two fp16 planes of the prepared index
+// (topk.hip: index_view), whose sum (hi + lo) 2^-e IS the database the index holds -- every element within 2^-23 of its row's
+// maximum, the operands the unscreened indexed search scores.  Candidate column c of the range that starts at database row s0
+// is global row r = s0 + c = panel p, local row lr; panel p's image starts at img + p * slot and has
 // R_p = min(panel, ndb - p * panel) rows; k-block kb, plane pl of the row is the 32 bytes at ((kb * 2 + pl) * R_p + lr) * 32,
-// 16-byte halves swapped when (lr >> 3) & 1 (gemm_h3.hip).  Thread t holds query columns 8 u .. 8 u + 7 of the units
-// u = t + 512 j, j < NU (dim <= 4096 NU): unit u = half (u & 1) of k-block u >> 1, so a thread fetches 16 bytes of the leading
-// plane and the matching 16 of the residual plane (a lane pair reads one 32-byte piece, pieces 2 R_p * 32 bytes apart: the
-// bytes of the fp32 row in dim / 16 * 2 pieces).  Plain 64-bit global loads: the index may be far larger than a buffer
-// descriptor's range.  (double)hi + (double)lo is exact, products and sums in float64, the fixed tree of the sibling, and the
-// row's 2^-e (a power of two: exact) on the sum.
+// 16-byte halves swapped when (lr >> 3) & 1 (gemm_h3.hip).  Thread t holds query columns 8 u .. 8 u + 7 of the slice's units
+// u = t + 512 j, j < NU (a slice of <= 4096 NU columns; dim % 16 == 0 and slices that are multiples of 4096: whole k-blocks,
+// 512 units per j): unit u = half (u & 1) of k-block u >> 1, so a thread fetches 16 bytes of the leading plane and the
+// matching 16 of the residual plane (a lane pair reads one 32-byte piece, pieces 2 R_p * 32 bytes apart: the bytes of the fp32
+// row in dim / 16 * 2 pieces).  A slice starts at k-block col0 / 16 of every candidate row's image, (col0 / 16) 2 R_p 32 bytes
+// into it.  Plain 64-bit global loads: the index may be far larger than a buffer descriptor's range; the row inside its panel
+// image is a 64-bit base (the same for the whole workgroup) and everything behind it a 32-bit offset: an image stays inside
+// 2 GiB.  (double)hi + (double)lo is exact, products and sums in float64, and the row's 2^-e (a power of two: exact) goes on the
+// whole sum, after the slices have met.
+// NU = 12 is compiled for the single-slice kernel only, so the sliced kernel stops at NU = 8 and SLICE_COLS at 32 768 columns:
+// written out as a kernel of its own, NU = 12 with the slice loop's state took all 256 VGPRs a 512-thread workgroup has and
+// spilled 40 bytes per lane (on this body the compiler reports 245 and no scratch; never instantiated, run or timed).
 template <int NU>
-__global__ __launch_bounds__(512) void screen_rescore_planes_kernel(const float* __restrict__ queries, const unsigned char* __restrict__ img,
-                                                                    size_t slot, int64_t panel, int64_t ndb, int64_t s0,
-                                                                    const float* __restrict__ dinv, int64_t dim, int cmax,
-                                                                    const int* __restrict__ cand, const int* __restrict__ count, int metric,
-                                                                    const float* __restrict__ qn, const float* __restrict__ dn,
-                                                                    const float* __restrict__ dnorm, float* __restrict__ cand_v) {
-  __shared__ double red[8][RS_G];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t q = blockIdx.x;
-  const int n = min(count[q], cmax);
-  const int n8 = (int)(dim >> 3);
+struct RescorePlanes {
+  static constexpr int64_t SLICE_COLS = 4096 * 8;
+  const unsigned char* __restrict__ img;
+  size_t slot;
+  int64_t panel, ndb, s0;
+  const float* __restrict__ dinv;
+  int n8;
   f32x4 qa[NU], qb[NU];
+
+  __device__ __forceinline__ void load_query(const float* __restrict__ qrow, int ncols) {
+    n8 = ncols >> 3;
 #pragma unroll
-  for (int j = 0; j < NU; ++j) {
-    const int u = tid + 512 * j;
-    const f32x4* qr = reinterpret_cast<const f32x4*>(queries + q * dim);
-    qa[j] = u < n8 ? qr[2 * u] : f32x4{0.f, 0.f, 0.f, 0.f};
-    qb[j] = u < n8 ? qr[2 * u + 1] : f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NU; ++j) {
+      const int u = (int)threadIdx.x + 512 * j;
+      const f32x4* qr = reinterpret_cast<const f32x4*>(qrow);
+      qa[j] = u < n8 ? qr[2 * u] : f32x4{0.f, 0.f, 0.f, 0.f};
+      qb[j] = u < n8 ? qr[2 * u + 1] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
   }
-  const float qq = metric ? qn[q] : 0.f;
-  for (int i0 = 0; i0 < n; i0 += RS_G) {
-    // the row inside its panel image (the same for the whole workgroup: a 64-bit base) + this thread's 16 bytes of k-block
-    // tid >> 1, leading plane (an image stays inside 2 GiB: 32-bit offsets)
+  __device__ __forceinline__ void accumulate(const int (&c)[RS_G], int col0, double (&s)[RS_G]) {
+    const int tid = threadIdx.x;
     const unsigned char* dr[RS_G];
     unsigned plane[RS_G], off0[RS_G];                      // bytes of one plane of the row's image: R_p * 32
 #pragma unroll
     for (int g = 0; g < RS_G; ++g) {
-      const int64_t r = s0 + cand[q * cmax + min(i0 + g, n - 1)];   // (a short last group re-reads its last row; the copy is not stored)
+      const int64_t r = s0 + c[g];
       const int64_t p = r / panel, lr = r - p * panel;
       plane[g] = (unsigned)(min(panel, ndb - p * panel) * 32);
       dr[g] = img + (size_t)p * slot + lr * 32;
-      off0[g] = (unsigned)(((tid & 1) ^ (int)((lr >> 3) & 1)) << 4) + (unsigned)(tid >> 1) * 2u * plane[g];
+      off0[g] = (unsigned)(((tid & 1) ^ (int)((lr >> 3) & 1)) << 4) + (unsigned)((col0 >> 4) + (tid >> 1)) * 2u * plane[g];
     }
-    double s[RS_G];
-#pragma unroll
-    for (int g = 0; g < RS_G; ++g) s[g] = 0.0;
     // the loads of unit j + 1 fly over the arithmetic of unit j (the compiler may not hoist further ones past the fence:
     // the whole row's loads in flight would not fit the registers next to the query)
     sc_f16x8 hi[RS_G], lo[RS_G], hi_n[RS_G], lo_n[RS_G];
@@ -398,7 +377,7 @@ __global__ __launch_bounds__(512) void screen_rescore_planes_kernel(const float*
       if (tid + 512 * j < n8) {
 #pragma unroll
         for (int g = 0; g < RS_G; ++g) {
-          const unsigned o = off0[g] + (unsigned)(512 * j) * plane[g];       // k-block (tid >> 1) + 256 j
+          const unsigned o = off0[g] + (unsigned)(512 * j) * plane[g];       // k-block (tid >> 1) + 256 j of the slice
           h[g] = *reinterpret_cast<const sc_f16x8*>(dr[g] + o);
           l[g] = *reinterpret_cast<const sc_f16x8*>(dr[g] + (o + plane[g]));
         }
@@ -406,7 +385,8 @@ __global__ __launch_bounds__(512) void screen_rescore_planes_kernel(const float*
     };
     load(0, hi, lo);
     // (the query stays fp32 in its registers: without this the float64 conversions of all of it are hoisted out of the loop
-    // over the candidates, twice the registers)
+    // over the candidates, twice the registers.  Inside the slice loop too: it is what keeps the conversions of the query
+    // slice out of the candidate loop's registers.)
 #pragma unroll
     for (int j = 0; j < NU; ++j) asm volatile("" : "+v"(qa[j]), "+v"(qb[j]));
 #pragma unroll
@@ -429,27 +409,46 @@ __global__ __launch_bounds__(512) void screen_rescore_planes_kernel(const float*
         lo[g] = lo_n[g];
       }
     }
-#pragma unroll
-    for (int g = 0; g < RS_G; ++g) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) s[g] += __shfl_xor(s[g], off, 64);
-      if (lane == 0) red[wave][g] = s[g];
-    }
-    __syncthreads();
-    if (tid < RS_G && i0 + tid < n) {
-      const int c = cand[q * cmax + i0 + tid];
-      const double tot = ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid])) + ((red[4][tid] + red[5][tid]) + (red[6][tid] + red[7][tid]));
-      cand_v[q * cmax + i0 + tid] = screen_value((float)(tot * (double)dinv[s0 + c]), c, metric, qq, dn, dnorm);
-    }
-    __syncthreads();
   }
+  __device__ __forceinline__ float value(double tot, int c) const { return (float)(tot * (double)dinv[s0 + c]); }
+};
+
+// The four kernels: {fp32 rows, planes} x {the whole row in one slice, sliced}.
+template <int NJ>
+__global__ __launch_bounds__(512) void screen_rescore_kernel(const float* __restrict__ queries, const float* __restrict__ db,
+                                                             int64_t dim, int cmax, const int* __restrict__ cand,
+                                                             const int* __restrict__ count, int metric, const float* __restrict__ qn,
+                                                             const float* __restrict__ dn, const float* __restrict__ dnorm,
+                                                             float* __restrict__ cand_v) {
+  __shared__ double red[8][RS_G];
+  RescoreRows<NJ> src{db, dim};
+  screen_rescore_body<false>(src, red, nullptr, queries, dim, 0, cmax, cand, count, metric, qn, dn, dnorm, cand_v);
 }
 
-// The same for rows of ANY width (dim % 16 == 0), sliced as screen_rescore_sliced_kernel: a slice of `slice` <= 4096 NU columns (a
-// multiple of 4096: whole k-blocks, 512 units per j) starts at k-block col0 / 16 of every candidate row's image, (col0 / 16) 2 R_p 32
-// bytes into it -- still a 32-bit offset: the whole image stays inside 2 GiB.  The totals of the slices meet in
-// the LDS accumulators in ascending column order; the row's 2^-e goes on the whole sum.  The fence on the query registers stays
-// inside the slice loop: it is what keeps the float64 conversions of the query slice out of the candidate loop's registers.
+template <int NJ>
+__global__ __launch_bounds__(512) void screen_rescore_sliced_kernel(const float* __restrict__ queries, const float* __restrict__ db,
+                                                                    int64_t dim, int64_t slice, int cmax, const int* __restrict__ cand,
+                                                                    const int* __restrict__ count, int metric, const float* __restrict__ qn,
+                                                                    const float* __restrict__ dn, const float* __restrict__ dnorm,
+                                                                    float* __restrict__ cand_v) {
+  __shared__ double red[8][RS_G];
+  __shared__ double tot_s[SCREEN_CMAX];
+  RescoreRows<NJ> src{db, dim};
+  screen_rescore_body<true>(src, red, tot_s, queries, dim, slice, cmax, cand, count, metric, qn, dn, dnorm, cand_v);
+}
+
+template <int NU>
+__global__ __launch_bounds__(512) void screen_rescore_planes_kernel(const float* __restrict__ queries, const unsigned char* __restrict__ img,
+                                                                    size_t slot, int64_t panel, int64_t ndb, int64_t s0,
+                                                                    const float* __restrict__ dinv, int64_t dim, int cmax,
+                                                                    const int* __restrict__ cand, const int* __restrict__ count, int metric,
+                                                                    const float* __restrict__ qn, const float* __restrict__ dn,
+                                                                    const float* __restrict__ dnorm, float* __restrict__ cand_v) {
+  __shared__ double red[8][RS_G];
+  RescorePlanes<NU> src{img, slot, panel, ndb, s0, dinv};
+  screen_rescore_body<false>(src, red, nullptr, queries, dim, 0, cmax, cand, count, metric, qn, dn, dnorm, cand_v);
+}
+
 template <int NU>
 __global__ __launch_bounds__(512) void screen_rescore_planes_sliced_kernel(const float* __restrict__ queries, const unsigned char* __restrict__ img,
                                                                            size_t slot, int64_t panel, int64_t ndb, int64_t s0,
@@ -459,86 +458,8 @@ __global__ __launch_bounds__(512) void screen_rescore_planes_sliced_kernel(const
                                                                            const float* __restrict__ dnorm, float* __restrict__ cand_v) {
   __shared__ double red[8][RS_G];
   __shared__ double tot_s[SCREEN_CMAX];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t q = blockIdx.x;
-  const int n = min(count[q], cmax);
-  for (int i = tid; i < n; i += 512) tot_s[i] = 0.0;     // (first touched again after the barrier of a step)
-  const int ncol = (int)dim, nslice = (int)slice;
-  for (int col0 = 0; col0 < ncol; col0 += nslice) {
-    const int n8 = min(nslice, ncol - col0) >> 3;
-    f32x4 qa[NU], qb[NU];
-#pragma unroll
-    for (int j = 0; j < NU; ++j) {
-      const int u = tid + 512 * j;
-      const f32x4* qr = reinterpret_cast<const f32x4*>(queries + q * dim + col0);
-      qa[j] = u < n8 ? qr[2 * u] : f32x4{0.f, 0.f, 0.f, 0.f};
-      qb[j] = u < n8 ? qr[2 * u + 1] : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    for (int i0 = 0; i0 < n; i0 += RS_G) {
-      const unsigned char* dr[RS_G];
-      unsigned plane[RS_G], off0[RS_G];                    // bytes of one plane of the row's image: R_p * 32
-#pragma unroll
-      for (int g = 0; g < RS_G; ++g) {
-        const int64_t r = s0 + cand[q * cmax + min(i0 + g, n - 1)];   // (a short last group re-reads its last row; the copy is not added)
-        const int64_t p = r / panel, lr = r - p * panel;
-        plane[g] = (unsigned)(min(panel, ndb - p * panel) * 32);
-        dr[g] = img + (size_t)p * slot + lr * 32;
-        off0[g] = (unsigned)(((tid & 1) ^ (int)((lr >> 3) & 1)) << 4) + (unsigned)((col0 >> 4) + (tid >> 1)) * 2u * plane[g];
-      }
-      double s[RS_G];
-#pragma unroll
-      for (int g = 0; g < RS_G; ++g) s[g] = 0.0;
-      sc_f16x8 hi[RS_G], lo[RS_G], hi_n[RS_G], lo_n[RS_G];
-      auto load = [&](int j, sc_f16x8 (&h)[RS_G], sc_f16x8 (&l)[RS_G]) {
-        if (tid + 512 * j < n8) {
-#pragma unroll
-          for (int g = 0; g < RS_G; ++g) {
-            const unsigned o = off0[g] + (unsigned)(512 * j) * plane[g];     // k-block (tid >> 1) + 256 j of the slice
-            h[g] = *reinterpret_cast<const sc_f16x8*>(dr[g] + o);
-            l[g] = *reinterpret_cast<const sc_f16x8*>(dr[g] + (o + plane[g]));
-          }
-        }
-      };
-      load(0, hi, lo);
-#pragma unroll
-      for (int j = 0; j < NU; ++j) asm volatile("" : "+v"(qa[j]), "+v"(qb[j]));
-#pragma unroll
-      for (int j = 0; j < NU; ++j) {
-        if (j + 1 < NU) load(j + 1, hi_n, lo_n);
-        asm volatile("" ::: "memory");
-        if (tid + 512 * j < n8) {
-#pragma unroll
-          for (int g = 0; g < RS_G; ++g) {
-            double v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (double)(float)hi[g][e] + (double)(float)lo[g][e];
-            s[g] += (((double)qa[j][0] * v[0] + (double)qa[j][1] * v[1]) + ((double)qa[j][2] * v[2] + (double)qa[j][3] * v[3])) +
-                    (((double)qb[j][0] * v[4] + (double)qb[j][1] * v[5]) + ((double)qb[j][2] * v[6] + (double)qb[j][3] * v[7]));
-          }
-        }
-#pragma unroll
-        for (int g = 0; g < RS_G; ++g) {
-          hi[g] = hi_n[g];
-          lo[g] = lo_n[g];
-        }
-      }
-#pragma unroll
-      for (int g = 0; g < RS_G; ++g) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s[g] += __shfl_xor(s[g], off, 64);
-        if (lane == 0) red[wave][g] = s[g];
-      }
-      __syncthreads();
-      if (tid < RS_G && i0 + tid < n)
-        tot_s[i0 + tid] += ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid])) + ((red[4][tid] + red[5][tid]) + (red[6][tid] + red[7][tid]));
-      __syncthreads();
-    }
-  }
-  const float qq = metric ? qn[q] : 0.f;
-  for (int i = tid; i < n; i += 512) {                     // (n > 0: the last step ended with a barrier)
-    const int c = cand[q * cmax + i];
-    cand_v[q * cmax + i] = screen_value((float)(tot_s[i] * (double)dinv[s0 + c]), c, metric, qq, dn, dnorm);
-  }
+  RescorePlanes<NU> src{img, slot, panel, ndb, s0, dinv};
+  screen_rescore_body<true>(src, red, tot_s, queries, dim, slice, cmax, cand, count, metric, qn, dn, dnorm, cand_v);
 }
 
 // ------------------------------------------------------------------------------------------------------------ select
@@ -734,7 +655,6 @@ int screen_overflow_plan(const int* over_q, int64_t nq, int side_cap, int* plan,
 bool screen_rescore_supported(int64_t dim) { return dim >= 4 && dim % 4 == 0; }
 
 // a slice of the sliced kernels: columns per slice, a multiple of 4096 the largest register footprint holds
-constexpr int64_t SCREEN_RESCORE_PLANES_COLS = 4096 * 8;   // the widest slice of screen_rescore_planes_sliced_kernel
 static bool rescore_slice_ok(int64_t slice) { return slice > 0 && slice % 4096 == 0 && slice <= SCREEN_RESCORE_COLS; }
 
 int screen_rescore(const float* queries, const float* db, int64_t dim, int64_t slice, int64_t nq, int cmax, const int* cand,
@@ -743,26 +663,16 @@ int screen_rescore(const float* queries, const float* db, int64_t dim, int64_t s
                    "screen_rescore: dim %lld in slices of %lld not served", (long long)dim, (long long)slice);
   ProfScope prof("topk_screen_rescore", stream, 0.0, 0.0);
   const int nj = (int)(((slice ? slice : dim) / 4 + 511) / 512);
-#define ANYLOC_RESCORE(NJ)                                                                                                      \
-  hipLaunchKernelGGL((screen_rescore_kernel<NJ>), dim3((unsigned)nq), dim3(512), 0, stream, queries, db, dim, cmax, cand, count, \
-                     metric, qn, dn, dnorm, cand_v)
-#define ANYLOC_RESCORE_SLICED(NJ)                                                                                                 \
-  hipLaunchKernelGGL((screen_rescore_sliced_kernel<NJ>), dim3((unsigned)nq), dim3(512), 0, stream, queries, db, dim, slice, cmax, \
-                     cand, count, metric, qn, dn, dnorm, cand_v)
-  if (slice) {
-    if (nj <= 2) ANYLOC_RESCORE_SLICED(2);
-    else if (nj <= 4) ANYLOC_RESCORE_SLICED(4);
-    else if (nj <= 8) ANYLOC_RESCORE_SLICED(8);
-    else if (nj <= 16) ANYLOC_RESCORE_SLICED(16);
-    else ANYLOC_RESCORE_SLICED(24);
-  } else if (nj <= 1) ANYLOC_RESCORE(1);
-  else if (nj <= 2) ANYLOC_RESCORE(2);
-  else if (nj <= 4) ANYLOC_RESCORE(4);
-  else if (nj <= 8) ANYLOC_RESCORE(8);
-  else if (nj <= 16) ANYLOC_RESCORE(16);
-  else ANYLOC_RESCORE(24);
-#undef ANYLOC_RESCORE
-#undef ANYLOC_RESCORE_SLICED
+  if (slice)
+    with_constant<2, 4, 8, 16, 24>(nj, [&](auto c) {
+      hipLaunchKernelGGL((screen_rescore_sliced_kernel<decltype(c)::value>), dim3((unsigned)nq), dim3(512), 0, stream, queries, db, dim, slice, cmax, cand,
+                         count, metric, qn, dn, dnorm, cand_v);
+    });
+  else
+    with_constant<1, 2, 4, 8, 16, 24>(nj, [&](auto c) {
+      hipLaunchKernelGGL((screen_rescore_kernel<decltype(c)::value>), dim3((unsigned)nq), dim3(512), 0, stream, queries, db, dim, cmax, cand, count,
+                         metric, qn, dn, dnorm, cand_v);
+    });
   return launch_status("screen_rescore_kernel");
 }
 
@@ -773,28 +683,18 @@ int screen_rescore_planes(const float* queries, const unsigned char* img, size_t
                    "screen_rescore_planes: dim %lld in slices of %lld not served", (long long)dim, (long long)slice);
   ANYLOC_CHECK_ARG(img && dinv && panel > 0 && s0 >= 0 && s0 < ndb, "screen_rescore_planes: bad index");
   ProfScope prof("topk_screen_rescore_planes", stream, 0.0, 0.0);
-  // (NU = 12 of the single-slice kernel leaves two VGPRs of the 256 a 512-thread workgroup has: with the slice loop's state it
-  // spills.  The sliced kernel stops at NU = 8, 237 VGPRs and no scratch: its slices are at most 32 768 columns.)
-  slice = std::min(slice, SCREEN_RESCORE_PLANES_COLS);
+  slice = std::min(slice, RescorePlanes<1>::SLICE_COLS);   // (narrower than the plan's: the planes source's widest slice)
   const int nu = (int)(((slice ? slice : dim) / 8 + 511) / 512);
-#define ANYLOC_RESCORE_PLANES(NU)                                                                                                \
-  hipLaunchKernelGGL((screen_rescore_planes_kernel<NU>), dim3((unsigned)nq), dim3(512), 0, stream, queries, img, slot, panel, ndb, s0, \
-                     dinv, dim, cmax, cand, count, metric, qn, dn, dnorm, cand_v)
-#define ANYLOC_RESCORE_PLANES_SLICED(NU)                                                                                          \
-  hipLaunchKernelGGL((screen_rescore_planes_sliced_kernel<NU>), dim3((unsigned)nq), dim3(512), 0, stream, queries, img, slot, panel, ndb, \
-                     s0, dinv, dim, slice, cmax, cand, count, metric, qn, dn, dnorm, cand_v)
-  if (slice) {
-    if (nu <= 1) ANYLOC_RESCORE_PLANES_SLICED(1);
-    else if (nu <= 2) ANYLOC_RESCORE_PLANES_SLICED(2);
-    else if (nu <= 4) ANYLOC_RESCORE_PLANES_SLICED(4);
-    else ANYLOC_RESCORE_PLANES_SLICED(8);
-  } else if (nu <= 1) ANYLOC_RESCORE_PLANES(1);
-  else if (nu <= 2) ANYLOC_RESCORE_PLANES(2);
-  else if (nu <= 4) ANYLOC_RESCORE_PLANES(4);
-  else if (nu <= 8) ANYLOC_RESCORE_PLANES(8);
-  else ANYLOC_RESCORE_PLANES(12);
-#undef ANYLOC_RESCORE_PLANES
-#undef ANYLOC_RESCORE_PLANES_SLICED
+  if (slice)
+    with_constant<1, 2, 4, 8>(nu, [&](auto c) {
+      hipLaunchKernelGGL((screen_rescore_planes_sliced_kernel<decltype(c)::value>), dim3((unsigned)nq), dim3(512), 0, stream, queries, img, slot, panel,
+                         ndb, s0, dinv, dim, slice, cmax, cand, count, metric, qn, dn, dnorm, cand_v);
+    });
+  else
+    with_constant<1, 2, 4, 8, 12>(nu, [&](auto c) {
+      hipLaunchKernelGGL((screen_rescore_planes_kernel<decltype(c)::value>), dim3((unsigned)nq), dim3(512), 0, stream, queries, img, slot, panel, ndb, s0,
+                         dinv, dim, cmax, cand, count, metric, qn, dn, dnorm, cand_v);
+    });
   return launch_status("screen_rescore_planes_kernel");
 }
 

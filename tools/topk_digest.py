@@ -7,6 +7,26 @@ arithmetics, k-chunks, the prepared index (built at once and by ranges, searched
 search (column ranges, k-chunks, the k limit, the overflow fallback), the empty database, k beyond the database, a call without queries (k = 0 is outside the documented [1, 1024] and refused).
 Two builds whose outputs of this tool are byte-identical launch the same tagged work and compute the same bits.
 
+The ``rescore_rows`` and ``rescore_planes`` cases (70 queries x 300 rows) reach every instantiation of the re-scoring kernels of
+csrc/scores_screen.hip (the names of tests/kernel_coverage.tsv) under the tags ``topk_screen_rescore`` and
+``topk_screen_rescore_planes``; a ``+ 16`` row has two slices, the second one k-block long:
+
+    dim (one slice)        rows: screen_rescore_kernel    planes: screen_rescore_planes_kernel
+      2 048                  <1>                            --
+      4 096                  <2>                            <1>
+      8 192                  <4>                            <2>
+     16 384                  <8>                            <4>
+     32 768                  <16>                           <8>
+     49 152                  <24>                           <12>
+    topk_rescore_cols, dim   rows: screen_rescore_sliced_kernel    planes: screen_rescore_planes_sliced_kernel
+      4 096,  4 112          <2>                            <1>
+      8 192,  8 208          <4>                            <2>
+     16 384, 16 400          <8>                            <4>
+     32 768, 32 784          <16>                           <8>
+     36 864, 36 880          <24>                           -- (the planes' slices end at 32 768 columns: <8> again)
+
+(checked with ``rocprofv3 --kernel-trace`` around ``--only rescore_`` and ``tools/kernel_coverage.py launched``).
+
     python tools/topk_digest.py > digest.jsonl          # needs the GPU; ``--list`` prints the case names only
 
 Inputs are torch.randn on the CPU from fixed seeds; the largest case (32 868 x 4096) holds half a gigabyte."""
@@ -24,6 +44,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 H3, SCREEN = {"topk_h3": 1, "topk_screen": 0}, {"topk_h3": 1, "topk_screen": 1}
 VARIANTS = tuple(itertools.product(("ip", "l2"), (0, 1)))              # metric x normalize_db
+RESCORE_DIMS = (2048, 4096, 8192, 16384, 32768, 49152)                 # the whole row in one slice: the top of every width class
+RESCORE_COLS = (4096, 8192, 16384, 32768, 36864)                       # topk_rescore_cols, on rows 16 columns wider: two slices
 
 
 def _cases():
@@ -65,6 +87,12 @@ def _cases():
     for k in (128, 129):
         add("screen", 70, 8492, 256, k=k, options=SCREEN)
     add("screen_overflow", 70, 1000, 256, options=SCREEN, duplicates=1)
+    # every instantiation of the four re-scoring kernels (the table in the docstring), from the fp32 rows and from the planes
+    for dim, cols in [(d, 0) for d in RESCORE_DIMS] + [(c + 16, c) for c in RESCORE_COLS]:
+        sliced = {"topk_rescore_cols": cols} if cols else {}
+        add("rescore_rows", 70, 300, dim, options=dict(SCREEN, **sliced))
+        if dim >= 4096 and cols != RESCORE_COLS[-1]:
+            add("rescore_planes", 70, 300, dim, options=dict({"topk_screen": 1}, **sliced), index="whole", rescore_planes=1)
     # edges: empty database (the padding list), k beyond the database, k = 1 and the largest k, calls that launch nothing
     add("edge", 9, 0, 64)
     add("edge", 9, 5, 64)
