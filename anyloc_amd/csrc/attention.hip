@@ -1006,6 +1006,10 @@ int attention(const float* qkv, float* out, int64_t n_img, int T, const int64_t*
   ANYLOC_CHECK_ARG(D == heads * HD, "attention: head_dim must be 64 (D=%d heads=%d)", D, heads);
   ANYLOC_CHECK_ARG(qkv && (out || out3) && T > 0 && n_img > 0 && n_img < 65536 && (tok_off || rows == n_img * T),
                    "attention: bad T/batch");
+  // the keys and values of an image are read through a buffer descriptor over its T rows of 3 D floats, with 32-bit byte offsets
+  ANYLOC_CHECK_ARG((int64_t)T * 3 * D * 4 < (1ll << 31),
+                   "attention: one image's qkv rows must stay inside 2 GiB of buffer addressing: tokens * 3 * dim * 4 < 2^31 "
+                   "(tokens=%d dim=%d)", T, D);
   const AttnF32Plan p = attn_f32_plan(n_img, T, heads, tok_off != nullptr, out3 != nullptr, x6);
   // (uniform: rows = n_img * T)
   ProfScope prof("attention", stream, 4.0 * heads * (double)rows * T * HD, 16.0 * rows * D);

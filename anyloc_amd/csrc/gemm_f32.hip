@@ -30,6 +30,7 @@
 //   * block id -> tile: XCD-aware (block b runs on XCD b % 8, each XCD has a
 //     private 4 MiB L2) + grouped ordering so co-resident blocks of one XCD
 //     share A row-panels and W column-panels.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -502,6 +503,22 @@ int run_plan(const GemmProblem& p, int epilogue, const GemmF32Plan& pl, hipStrea
   return ANYLOC_OK;
 }
 
+// The operands are read through buffer descriptors of 2^31 - 1 bytes at the tile's first row, with 32-bit byte offsets: the last
+// row a tile touches (rows past the matrix are clamped onto its last one) and the K range behind it must lie inside that window.
+// The few-query scores make the same check for their 128 x 64 tiles (scores_h3.hip, scores_x6.hip).
+int check_tile_span(const char* who, const GemmProblem& p, const GemmF32Plan& pl) {
+  for (int i = 0; i < pl.nparts; ++i) {
+    const F32Tile t = kF32Tile[pl.part[i].tile];
+    const int64_t ra = std::min<int64_t>(t.bm, pl.part[i].rows) - 1, rw = std::min<int64_t>(t.bn, p.N) - 1;
+    const double a_end = (double)ra * (double)p.lda * 4.0 + (double)p.K * 4.0, w_end = (double)rw * (double)p.ldw * 4.0 + (double)p.K * 4.0;
+    ANYLOC_CHECK_ARG(a_end < 2147483648.0 && w_end < 2147483648.0,
+                     "%s: a tile's rows must stay inside 2 GiB of buffer addressing: (min(tile rows, rows) - 1) * ld * 4 + K * 4 < 2^31 "
+                     "(A: %lld rows of lda=%lld, W: %lld rows of ldw=%lld, K=%lld)",
+                     who, (long long)(ra + 1), (long long)p.lda, (long long)(rw + 1), (long long)p.ldw, (long long)p.K);
+  }
+  return ANYLOC_OK;
+}
+
 }  // namespace
 
 int gemm_nt_splitk(const GemmProblem& p, hipStream_t stream) {
@@ -511,7 +528,9 @@ int gemm_nt_splitk(const GemmProblem& p, hipStream_t stream) {
   ANYLOC_CHECK_ARG(p.lda % 4 == 0 && p.ldw % 4 == 0 && (reinterpret_cast<uintptr_t>(p.A) & 15) == 0 &&
                        (reinterpret_cast<uintptr_t>(p.W) & 15) == 0,
                    "gemm_nt_splitk: operands must be 16-byte aligned with row strides that are multiples of 4");
-  return run_plan(p, EPI_STORE, GemmF32Plan{1, {{0, p.M, F32_TILE_SPLITK, true, true, 0}, {}}}, stream);
+  const GemmF32Plan pl{1, {{0, p.M, F32_TILE_SPLITK, true, true, 0}, {}}};
+  ANYLOC_TRY(check_tile_span("gemm_nt_splitk", p, pl));
+  return run_plan(p, EPI_STORE, pl, stream);
 }
 
 int gemm_nt(const GemmProblem& p, int epilogue, hipStream_t stream) {
@@ -530,7 +549,11 @@ int gemm_nt(const GemmProblem& p, int epilogue, hipStream_t stream) {
   ANYLOC_CHECK_ARG(epilogue != EPI_LS_RESID || (p.gamma && p.resid), "gemm_nt: LS_RESID needs gamma and resid");
   ANYLOC_CHECK_ARG(epilogue != EPI_SWIGLU || p.N % 64 == 0, "gemm_nt: SWIGLU needs N %% 64 == 0");
   ANYLOC_CHECK_ARG(epilogue != EPI_PATCH || (p.pos && p.patches > 0), "gemm_nt: PATCH needs pos and patches");
-  return run_plan(p, epilogue, gemm_f32_plan(p, epilogue), stream);
+  ANYLOC_CHECK_ARG(p.lda >= p.K && p.ldw >= p.K, "gemm_nt: lda and ldw must be at least K (K=%lld lda=%lld ldw=%lld)", (long long)p.K,
+                   (long long)p.lda, (long long)p.ldw);
+  const GemmF32Plan pl = gemm_f32_plan(p, epilogue);
+  ANYLOC_TRY(check_tile_span("gemm_nt", p, pl));
+  return run_plan(p, epilogue, pl, stream);
 }
 
 }  // namespace anyloc

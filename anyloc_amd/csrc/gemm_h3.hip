@@ -418,6 +418,7 @@ int row_scales_h2(const float* x, int64_t ldx, int64_t rows, int64_t K, float* i
 int split_h2(const float* x, int64_t ldx, int64_t rows, int64_t K, void* h2, float* inv_scale, hipStream_t stream) {
   ANYLOC_CHECK_ARG(x && h2 && inv_scale && rows > 0 && K > 0 && ldx >= K, "split_h2: bad arguments");
   ANYLOC_CHECK_ARG(K % 16 == 0 && ldx % 4 == 0, "split_h2: K must be a multiple of 16 (got %lld)", (long long)K);
+  ANYLOC_CHECK_ARG(rows < (1ll << 31) && K < (1ll << 31), "split_h2: rows %lld and K %lld must be below 2^31", (long long)rows, (long long)K);
   if (K > 4096) return split_h2_wide(x, ldx, rows, K, h2, inv_scale, nullptr, stream);
   ProfScope prof("split_h2", stream, 0.0, 8.0 * rows * K);
   const dim3 grid((unsigned)((rows + 15) / 16));

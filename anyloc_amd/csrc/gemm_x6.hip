@@ -424,6 +424,9 @@ size_t x3_bytes(int64_t rows, int64_t K) { return (size_t)((K + 15) / 16) * 3 * 
 
 int split_x3(const float* x, int64_t ldx, int64_t rows, int64_t K, void* x3, hipStream_t stream) {
   ANYLOC_CHECK_ARG(x && x3 && rows > 0 && K > 0 && ldx >= K, "split_x3: bad arguments");
+  // (one grid row per two k-blocks of 16 columns, one grid column per 128 rows)
+  ANYLOC_CHECK_ARG(rows < (1ll << 31) && K <= 16 * 2 * 65535, "split_x3: rows %lld must be below 2^31 and K %lld at most 2 097 120", (long long)rows,
+                   (long long)K);
   const int K16 = (int)((K + 15) / 16);
   ProfScope prof("split_x3", stream, 0.0, 10.0 * rows * K);
   hipLaunchKernelGGL(split_x3_kernel, dim3((unsigned)((rows + 127) / 128), (unsigned)((K16 + 1) / 2)), dim3(256), 0,

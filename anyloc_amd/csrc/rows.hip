@@ -357,6 +357,7 @@ extern "C" int anyloc_preprocess_u8(const unsigned char* img_hwc, int64_t batch,
   ANYLOC_CHECK_ARG(img_hwc && out && mean3 && std3, "preprocess_u8: null pointer");
   ANYLOC_CHECK_ARG(batch > 0 && batch < 65536 && height > 0 && width > 0 && height < 65536,
                    "preprocess_u8: batch %lld / height %lld outside [1, 65535], or no width", (long long)batch, (long long)height);
+  ANYLOC_CHECK_ARG(width < (1ll << 31), "preprocess_u8: width %lld must be below 2^31", (long long)width);
   ANYLOC_CHECK_ARG(crop_h > 0 && crop_w > 0 && crop_h <= height && crop_w <= width,
                    "preprocess_u8: crop %lldx%lld outside image %lldx%lld", (long long)crop_h, (long long)crop_w,
                    (long long)height, (long long)width);
@@ -418,6 +419,9 @@ extern "C" int anyloc_resize_bicubic(const float* in, int64_t planes, int64_t he
   ANYLOC_CHECK_ARG(in && out, "resize_bicubic: null pointer");
   ANYLOC_CHECK_ARG(planes > 0 && planes < 65536 && height > 0 && width > 0 && out_h > 0 && out_w > 0 && out_h < 65536,
                    "resize_bicubic: planes %lld / out_h %lld outside [1, 65535], or an empty image", (long long)planes, (long long)out_h);
+  ANYLOC_CHECK_ARG(height < (1ll << 31) && width < (1ll << 31) && out_w < (1ll << 31),
+                   "resize_bicubic: height %lld, width %lld and out_w %lld must be below 2^31", (long long)height, (long long)width,
+                   (long long)out_w);
   ANYLOC_CHECK_ARG(crop_top >= 0 && crop_left >= 0 && crop_h > 0 && crop_w > 0 && crop_top + crop_h <= out_h &&
                        crop_left + crop_w <= out_w, "resize_bicubic: crop window outside the resized image");
   hipStream_t s = static_cast<hipStream_t>(stream);

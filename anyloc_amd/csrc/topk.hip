@@ -682,6 +682,9 @@ int topk_impl(const float* queries, int64_t nq, const float* db, int64_t ndb, in
   ANYLOC_CHECK_ARG(metric == 0 || metric == 1, "topk: metric %d", metric);
   ANYLOC_CHECK_ARG(dim >= 4 && dim % 4 == 0, "topk: dim %lld must be a positive multiple of 4", (long long)dim);
   ANYLOC_CHECK_ARG(nq < (1ll << 31), "topk: too many queries");
+  // (the score kernels read the rows of one tile -- at most 256, gemm_f32.hip: check_tile_span -- through one 2 GiB buffer
+  // descriptor: 256 * dim * 4 < 2^31)
+  ANYLOC_CHECK_ARG(dim < (1ll << 21), "topk: dim %lld must be below 2^21", (long long)dim);
   ANYLOC_CHECK_ARG((flags & ~(ANYLOC_TOPK_NORMALIZE_DB | ANYLOC_TOPK_NO_WAIT | (indexed ? ANYLOC_TOPK_RESCORE_PLANES : 0u))) == 0,
                    "topk: unknown flags %u", flags);
   TopkCall c{queries, db, metric, (flags & ANYLOC_TOPK_NORMALIZE_DB) != 0, indexed && (flags & ANYLOC_TOPK_RESCORE_PLANES) != 0,

@@ -226,7 +226,9 @@ extern "C" {
 
 int anyloc_layernorm(const float* x, float* y, const float* weight, const float* bias, int64_t rows, int64_t dim,
                      float eps, void* stream) {
-  ANYLOC_CHECK_ARG(x && y && weight && bias && rows > 0 && rows < (1ll << 31) && dim > 0, "layernorm: bad args");
+  ANYLOC_CHECK_ARG(x && y && weight && bias && rows > 0 && dim > 0, "layernorm: bad args");
+  ANYLOC_CHECK_ARG(rows < (1ll << 31) && dim < (1ll << 31), "layernorm: rows %lld and dim %lld must both be below 2^31", (long long)rows,
+                   (long long)dim);
   return layernorm(x, y, weight, bias, rows, (int)dim, eps, static_cast<hipStream_t>(stream));
 }
 
@@ -234,6 +236,9 @@ int anyloc_attention(const float* qkv, float* out, int64_t batch, int64_t tokens
                      void* stream) {
   ANYLOC_CHECK_ARG(qkv && out, "attention: null pointer");
   ANYLOC_CHECK_ARG(batch > 0 && batch < 65536, "attention: batch %lld outside [1, 65535]", (long long)batch);
+  ANYLOC_CHECK_ARG(tokens > 0 && tokens < (1ll << 31) && dim > 0 && dim < (1ll << 31) && heads > 0 && heads < (1ll << 31),
+                   "attention: tokens %lld, dim %lld and heads %lld must be positive and below 2^31", (long long)tokens, (long long)dim,
+                   (long long)heads);
   return attention(qkv, out, batch, (int)tokens, nullptr, batch * tokens, (int)dim, (int)heads, static_cast<hipStream_t>(stream));
 }
 
@@ -246,6 +251,10 @@ size_t anyloc_attention_h3_workspace_bytes(int64_t batch, int64_t tokens, int64_
 // anyloc_attention_h3 and anyloc_attention_h3_ragged: the q | k | v tiles of fp32 qkv [rows, 3 * dim] in the caller's workspace
 static int h3_tiles_in_workspace(const char* who, const float* qkv, int64_t rows, int64_t dim, int64_t heads, void* workspace,
                                  size_t workspace_bytes, hipStream_t stream, unsigned char** planes, float** inv) {
+  // (attn_plan's limit on the q, k and v tile images, made here in front of the launch that builds them)
+  ANYLOC_CHECK_ARG(rows < (1ll << 31) && heads < (1 << 20) && heads * ((rows + 31) / 32) * 8192 < (1ll << 31),
+                   "%s: operand tiles exceed the 2 GiB buffer-addressing range: heads * ceil(rows / 32) * 8192 < 2^31 (rows=%lld heads=%lld)",
+                   who, (long long)rows, (long long)heads);
   if (workspace_bytes < anyloc_attention_h3_workspace_bytes(1, rows, heads)) {
     set_error("%s: workspace %zu < %zu", who, workspace_bytes, anyloc_attention_h3_workspace_bytes(1, rows, heads));
     return ANYLOC_ERR_WORKSPACE;
@@ -262,6 +271,7 @@ int anyloc_attention_h3(const float* qkv, void* out_img, float* out_inv, int64_t
   ANYLOC_CHECK_ARG(qkv && out_img && out_inv && workspace, "attention_h3: null pointer");
   ANYLOC_CHECK_ARG(batch > 0 && tokens > 0 && heads > 0 && dim == heads * 64, "attention_h3: bad shape");
   ANYLOC_CHECK_ARG(batch < 65536, "attention_h3: batch %lld outside [1, 65535]", (long long)batch);   // (before the tiles are built)
+  ANYLOC_CHECK_ARG(tokens < (1ll << 31), "attention_h3: tokens %lld must be below 2^31", (long long)tokens);
   unsigned char* planes;
   float* inv;
   ANYLOC_TRY(h3_tiles_in_workspace("attention_h3", qkv, batch * tokens, dim, heads, workspace, workspace_bytes, stream, &planes, &inv));

@@ -408,6 +408,14 @@ __global__ __launch_bounds__(256) void assigned_prep_kernel(const float* __restr
 
 inline int64_t kpad_of(int64_t K) { return (K + 31) / 32 * 32; }
 
+// Width limit of the entry points here: the two-pass paths hand the tokens to the fp32 GEMM with lda = K = D, whose tallest tile
+// (256 rows, option gemm_f32_cfg) must span less than 2 GiB -- 256 * D * 4 < 2^31 (gemm_f32.hip, check_tile_span) -- so D < 2^21
+// is refused with the other argument checks, before any launch; it also keeps K * D (K <= 256) inside an int.
+
+// Rows of one unit of the fused kernel (vlad_fused.hip) -- a k-means chunk, or one part of one image: the unit's rows are read
+// through a buffer descriptor with 32-bit byte offsets, so a unit holds fewer than 2^31 bytes of rows, in whole 16-row tiles.
+inline int64_t fused_unit_rows_limit(int64_t D) { return ((1ll << 31) - 1) / (4 * D) / 16 * 16; }
+
 // Workgroups per image of the fused kernel: one workgroup per image cannot fill 256 CUs below ~200 images, so a small
 // batch splits every image's token tiles over up to 8 workgroups (the last to finish reduces, vlad_fused.hip); every
 // part keeps >= 2 tiles of 16 tokens on average.  Option vlad_parts forces a count (A/B, tests).
@@ -598,6 +606,8 @@ static int vlad_common_checks(const float* tokens, const int64_t* offsets, int64
   ANYLOC_CHECK_ARG(K >= 1 && K <= 256, "vlad: num_clusters %lld outside [1,256]", (long long)K);
   ANYLOC_CHECK_ARG(D >= 4 && D % 4 == 0, "vlad: desc_dim %lld must be a positive multiple of 4", (long long)D);
   ANYLOC_CHECK_ARG(n_img < 65536ll * 32768, "vlad: too many images");
+  ANYLOC_CHECK_ARG(total < (1ll << 31) && D < (1ll << 21), "vlad: %lld tokens of %lld columns in one call (tokens < 2^31, desc_dim < 2^21)",
+                   (long long)total, (long long)D);
   return ANYLOC_OK;
 }
 
@@ -611,6 +621,19 @@ int anyloc_vlad_hard(const float* tokens, const int64_t* offsets, int64_t n_img,
   ANYLOC_CHECK_ARG(asked <= 64, "vlad_hard: ANYLOC_VLAD_PARTS(%d) outside 1..64", asked);
   // The fused kernel wherever it applies (K <= 32, the ViT widths); option vlad_two_pass = 1 selects the general path.
   const PartsPlan plan = plan_parts(D, K, n_img, total_tokens, asked);
+  if (plan.fused) {
+    ANYLOC_CHECK_ARG(n_img * plan.run < (1ll << 31), "vlad_hard: %lld images x %d parts: the one-pass kernel's grid holds fewer than 2^31 workgroups",
+                     (long long)n_img, plan.run);
+    // A unit of the fused kernel -- one image, or one of its plan.run parts (whole 16-token tiles) -- is read through a 32-bit
+    // buffer descriptor and must hold fewer than 2^31 bytes of tokens.  The offsets are on the device: the host bounds an image
+    // by the call's total_tokens (exact when n_img == 1) and refuses what it cannot show to fit.
+    const int64_t per_part = ((total_tokens + 15) / 16 + plan.run - 1) / plan.run * 16;
+    ANYLOC_CHECK_ARG(per_part <= fused_unit_rows_limit(D),
+                     "vlad_hard: the one-pass kernel serves fewer than 2^31 / (4 D) = %lld tokens per image and part; %lld tokens in "
+                     "%lld image(s) at %d part(s) cannot be shown to fit (fewer images per call, more ANYLOC_VLAD_PARTS, or option "
+                     "vlad_two_pass = 1)",
+                     (long long)fused_unit_rows_limit(D), (long long)total_tokens, (long long)n_img, plan.run);
+  }
   VladWs w = carve(workspace, workspace_bytes, total_tokens, D, K, n_img, plan.run);
   ANYLOC_TRY(check_workspace("vlad_hard", workspace, workspace_bytes, w.bytes));
   // labels = kmeans.predict(tokens) in the metric the vocabulary was built with (reference utilities.py:849 with
@@ -669,6 +692,7 @@ int anyloc_vlad_soft_weights(const float* tokens, int64_t n_tok, int64_t D, cons
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   ANYLOC_CHECK_ARG(centers && weights && (tokens || n_tok == 0), "vlad_soft_weights: null pointer");
   ANYLOC_CHECK_ARG(n_tok >= 0 && K >= 1 && K <= 64 && D >= 4 && D % 4 == 0, "vlad_soft_weights: bad shape (K <= 64)");
+  ANYLOC_CHECK_ARG(D < (1ll << 21), "vlad_soft_weights: desc_dim %lld must be below 2^21", (long long)D);
   if (n_tok == 0) return ANYLOC_OK;
   VladWs w = carve(workspace, workspace_bytes, n_tok, D, K);
   ANYLOC_TRY(check_workspace("vlad_soft_weights", workspace, workspace_bytes, w.bytes));
@@ -683,6 +707,7 @@ int anyloc_vlad_residuals(const float* tokens, int64_t n_tok, int64_t D, const f
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   ANYLOC_CHECK_ARG(centers && out && (tokens || n_tok == 0), "vlad_residuals: null pointer");
   ANYLOC_CHECK_ARG(n_tok >= 0 && n_tok < (1ll << 31) && K >= 1 && D >= 4 && D % 4 == 0, "vlad_residuals: bad shape");
+  ANYLOC_CHECK_ARG(K < (1ll << 31) && D < (1ll << 31), "vlad_residuals: K %lld and D %lld must be below 2^31", (long long)K, (long long)D);
   if (n_tok == 0) return ANYLOC_OK;
   ProfScope prof("vlad_residuals", stream, (double)n_tok * K * D, 4.0 * ((double)n_tok * D * (K + 1) + (double)K * D));
   hipLaunchKernelGGL(residuals_kernel, dim3((unsigned)n_tok), dim3(256), 0, stream, tokens, (int)D, (int)K, centers,
@@ -701,6 +726,7 @@ int anyloc_vlad_assigned(const float* tokens, int64_t n_tok, int64_t D, const fl
                    "vlad_assigned: pass labels (hard) or soft weights, not both");
   ANYLOC_CHECK_ARG(n_tok >= 0 && n_tok < (1ll << 31) && K >= 1 && K <= 256 && D >= 4 && D % 4 == 0,
                    "vlad_assigned: bad shape (n_tok < 2^31, K in [1, 256], D a positive multiple of 4)");
+  ANYLOC_CHECK_ARG(D < (1ll << 21), "vlad_assigned: desc_dim %lld must be below 2^21", (long long)D);
   ANYLOC_CHECK_ARG(n_tok == 0 || labels || K <= 64, "vlad_assigned: soft weights need K <= 64");
   VladWs w = carve(workspace, workspace_bytes, n_tok, D, K);
   ANYLOC_TRY(check_workspace("vlad_assigned", workspace, workspace_bytes, w.bytes));
@@ -725,7 +751,9 @@ int anyloc_vlad_assigned(const float* tokens, int64_t n_tok, int64_t D, const fl
 // overrides): every chunk costs a prologue, 196 KB of partial sums written and re-read, and with one fused workgroup
 // filling a CU more chunks only add rounds -- 5 M x 1536 rows: 2048 chunks 6.67 ms, 1024 6.20, 512 5.87, 256 5.87 per
 // step on clustered rows (profiles/r02_kmeans_chunks.log); two per CU keeps some slack for CUs of unequal speed.
-static int64_t kmeans_chunk_rows(int64_t n) {
+// A chunk is one unit of the fused kernel (fused_unit_rows_limit): a long input gets MORE chunks than kmeans_max_chunks asked for
+// rather than a wrong sum.
+static int64_t kmeans_chunk_rows(int64_t n, int64_t D) {
   static int cus = 0;
   if (cus == 0) {
     int dev = 0;
@@ -738,7 +766,9 @@ static int64_t kmeans_chunk_rows(int64_t n) {
   const int64_t forced = option(OPT_KMEANS_MAX_CHUNKS);
   const int64_t max_chunks = forced > 0 ? forced : 2ll * cus;
   int64_t rows = (n + max_chunks - 1) / max_chunks;
-  return rows < 1024 ? 1024 : rows;
+  if (rows < 1024) rows = 1024;
+  const int64_t cap = D > 0 ? fused_unit_rows_limit(D) : rows;
+  return rows > cap && cap >= 16 ? cap : rows;
 }
 
 // the VLAD slots, then one partial [K, D] sum and one [K] label histogram per chunk: the size function and the step both
@@ -746,7 +776,7 @@ static int64_t kmeans_chunk_rows(int64_t n) {
 struct KmeansWs : VladWs { int64_t rows, chunks; float* part; unsigned* cnt_part; };
 static KmeansWs carve_kmeans(void* ws, size_t cap, int64_t n, int64_t D, int64_t K) {
   KmeansWs k{carve(ws, cap, n, D, K)};
-  k.rows = kmeans_chunk_rows(n);
+  k.rows = kmeans_chunk_rows(n, D);
   k.chunks = std::max<int64_t>(1, (n + k.rows - 1) / k.rows);
   Arena tail(static_cast<char*>(ws) + k.bytes, 0);
   k.part = tail.take<float>(k.chunks * K * D);
@@ -787,8 +817,14 @@ int anyloc_kmeans_step(const float* x, int64_t n, int64_t D, const float* center
   ANYLOC_CHECK_ARG(K >= 1 && K <= 256, "kmeans_step: K %lld outside [1,256]", (long long)K);
   ANYLOC_CHECK_ARG(D >= 4 && D % 4 == 0, "kmeans_step: D %lld must be a positive multiple of 4", (long long)D);
   ANYLOC_CHECK_ARG(mode == 0 || mode == 1, "kmeans_step: mode %d", mode);
+  ANYLOC_CHECK_ARG(D < (1ll << 21), "kmeans_step: D %lld must be below 2^21", (long long)D);
+  ANYLOC_CHECK_ARG(n < (1ll << 31) || (fused_supported(D, K) && !two_pass_forced()), "kmeans_step: %lld rows, the two-pass path takes fewer than 2^31",
+                   (long long)n);
   const KmeansWs k = carve_kmeans(workspace, workspace_bytes, n, D, K);
   ANYLOC_TRY(check_workspace("kmeans_step", workspace, workspace_bytes, k.bytes + 256));   // = anyloc_kmeans_workspace_bytes
+  // (the two-pass path runs one grid row per chunk; the fused kernel a 1-D grid)
+  ANYLOC_CHECK_ARG(k.chunks <= 65535 || (fused_supported(D, K) && !two_pass_forced()),
+                   "kmeans_step: %lld chunks, the two-pass path takes at most 65535 (option kmeans_max_chunks)", (long long)k.chunks);
   ANYLOC_TRY(prep_centers(centers, k, K, D, mode, stream));
   if (fused_supported(D, K) && !two_pass_forced()) {
     FusedArgs fa{};

@@ -1170,6 +1170,9 @@ bool fused_supported(int64_t D, int64_t K) {
 int vlad_fused(const FusedArgs& a, int64_t units, bool kmeans, hipStream_t stream) {
   if (units <= 0) return ANYLOC_OK;
   ANYLOC_CHECK_ARG(units < (1ll << 31), "vlad_fused: too many units");
+  // (k-means mode: the host knows a unit's rows; VLAD mode: anyloc_vlad_hard bounds them, the offsets being on the device)
+  ANYLOC_CHECK_ARG(!kmeans || a.chunk_rows * a.D * 4 < (1ll << 31), "vlad_fused: a chunk of %lld rows exceeds the 2 GiB buffer-addressing range",
+                   (long long)a.chunk_rows);
   if (!fused_supported(a.D, 1)) {
     set_error("vlad_fused: unsupported D=%d", a.D);
     return ANYLOC_ERR_UNSUPPORTED;

@@ -113,6 +113,14 @@ def rope_table(h_img, w_img, patch=16, theta=ROPE_THETA):
     return torch.cat([torch.cos(angles), torch.sin(angles)], dim=1).contiguous()
 
 
+def max_rows_for(dim, hidden):
+    """Token rows one forward call takes: the plane image of one activation operand -- three bf16 planes of max(dim, hidden)
+    columns, 6 bytes per element, the larger of the two formats -- must stay inside 2 GiB of buffer addressing
+    (anyloc_x3_bytes / anyloc_h2_bytes < 2^31, include/anyloc_hip.h); 512 rows are kept back for the padding of a call's
+    last row tile."""
+    return (2 ** 31 - 1) // (6 * max(dim, hidden)) - 512
+
+
 def ragged_chunks(sizes, max_rows, patch=PATCH, registers=0):
     """Greedy packing of images of sizes [(H, W), ...] in input order under a budget of ``max_rows`` token rows per call
     (1 + ``registers`` + N_i per image): -> [(start, stop), ...] index ranges.  An image whose own rows exceed the budget
@@ -275,8 +283,7 @@ class HipDinoV2:
             _lib.check(lib.anyloc_vit_attach_x3(self._handle, x3), "anyloc_vit_attach_x3")
         if self.gemm == "h3":
             _lib.check(lib.anyloc_vit_attach_h2(self._handle, h2), "anyloc_vit_attach_h2")
-        # the plane image of one activation operand must stay inside 2 GiB of buffer addressing
-        self.max_rows = (2 ** 31 - 1) // (6 * max(dim, hidden)) - 512
+        self.max_rows = max_rows_for(dim, hidden)
         # FFN-bound telemetry (h3 mode): per-block looseness of the last call (max over its images), the blocks that ran on
         # the exact quantiser for some image of the last call, and how many images were run again over the handle's life
         self.ffn_check = True             # False: no telemetry, no host sync (capture / timing probes; the bound is then unchecked)

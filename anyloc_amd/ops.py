@@ -252,6 +252,49 @@ def _offsets_for(tokens_list_or_tensor, device):
     return packed, table_to_device(offsets, device), n_img, D
 
 
+VLAD_FUSED_DIMS = (384, 768, 1024, 1536)     # the one-pass kernel: these widths, K <= 32 (csrc/vlad_fused.hip, fused_supported)
+
+
+def vlad_fused_unit_rows(D):
+    """Tokens one unit of the one-pass VLAD kernel -- one image, or one of its ``parts`` -- may hold: fewer than 2^31 bytes,
+    in whole 16-token tiles (include/anyloc_hip.h, anyloc_vlad_hard)."""
+    return ((1 << 31) - 1) // (4 * int(D)) // 16 * 16
+
+
+def vlad_rows_per_part(rows, parts):
+    """Tokens per part of an image of ``rows`` tokens split over ``parts`` workgroups: whole 16-token tiles."""
+    return -(-(-(-int(rows) // 16)) // int(parts)) * 16
+
+
+def _vlad_hard_pieces(offsets, n_img, total, D, K, parts):
+    """How a hard-VLAD batch goes to anyloc_vlad_hard.  The one-pass kernel reads a unit's tokens through 32-bit buffer
+    offsets, and the C entry point, which cannot read the device's offsets, refuses every batch whose TOTAL could not fit one
+    unit.  Here one host read of the offsets settles it: -> (parts to pass, [(first image, last image + 1, first row, last
+    row + 1), ...]).  A batch that fits goes over in one piece with the caller's ``parts``; a longer one in pieces that fit,
+    each with the workgroups-per-image count of the WHOLE batch -- the bits of the one-call result (ANYLOC_VLAD_PARTS).  One
+    image that does not fit its parts is a ValueError that names the limit."""
+    whole = (parts, [(0, n_img, 0, total)])
+    if K > 32 or D not in VLAD_FUSED_DIMS or n_img == 0 or get_option("vlad_two_pass") != 0:
+        return whole
+    limit = vlad_fused_unit_rows(D)
+    run = parts or vlad_auto_parts(n_img, total, D, K)
+    if vlad_rows_per_part(total, run) <= limit:
+        return whole
+    off = offsets.cpu().tolist()
+    longest = max(b - a for a, b in zip(off[:-1], off[1:]))
+    if vlad_rows_per_part(longest, run) > limit:
+        raise ValueError(f"vlad: an image of {longest} tokens at {run} part(s): the one-pass kernel serves fewer than "
+                         f"2^31 / (4 D) = {limit} tokens per image and part (pass more parts, up to 64, or set option "
+                         f"vlad_two_pass = 1)")
+    pieces, a = [], 0
+    for b in range(1, n_img + 1):
+        if vlad_rows_per_part(off[b] - off[a], run) > limit:       # image b - 1 no longer fits: the piece ends in front of it
+            pieces.append((a, b - 1, off[a], off[b - 1]))
+            a = b - 1
+    pieces.append((a, n_img, off[a], off[n_img]))
+    return run, pieces
+
+
 def vlad_auto_parts(n_img, n_tok_total, D, K):
     """Workgroups per image the one-pass VLAD kernel would use for a batch of ``n_img`` images (``vlad(parts=...)``)."""
     return int(_lib.load().anyloc_vlad_auto_parts(int(n_tok_total), int(n_img), int(D), int(K)))
@@ -266,8 +309,12 @@ def vlad(tokens, centers, mode="hard", norm_descs=True, intra_norm=True, soft_te
     centers: [K, D].  ``dist_mode``: the metric of the hard assignment (the VLAD object's ``dist_mode``; the soft
     weights are always cosine, as in the reference).  ``parts`` (hard mode): workgroups per image as the caller's choice
     (ANYLOC_VLAD_PARTS; 0 = the library's) -- a batch handed over in pieces keeps the bits of the one-call result when every
-    piece passes the whole batch's count.  ``out``: an [n_img, K*D] fp32 device tensor to fill (a caller that streams a
-    batch in pieces hands over slices of ONE result tensor).  Returns [n_img, K*D] (and int64 labels [total] for hard mode)."""
+    piece passes the whole batch's count; a batch too long for the one-pass kernel's 32-bit token offsets in one call (2 GiB
+    of tokens per image and part) is handed over in such pieces here, after ONE blocking read of the offsets (a
+    ``.cpu()`` of n_img + 1 integers: such a call cannot be captured into a graph; a batch that fits -- anything below 2 GiB of
+    tokens per part -- makes no host read and goes over in one call as before).  Soft mode has no parts: its flags carry none
+    and its workspace is sized without them (anyloc_vlad_soft runs the two-pass kernels and never read the count).  ``out``: an [n_img, K*D] fp32 device tensor to fill
+    (a caller that streams a batch in pieces hands over slices of ONE result tensor).  Returns [n_img, K*D] (and int64 labels [total] for hard mode)."""
     device = _lib.require_gpu()
     centers = _f32c(centers, device)
     K, D = centers.shape
@@ -287,15 +334,21 @@ def vlad(tokens, centers, mode="hard", norm_descs=True, intra_norm=True, soft_te
     if not 0 <= parts <= 64:
         raise ValueError(f"vlad: parts {parts} outside 0..64 (0 = the library's choice)")
     flags = (VLAD_NORM_DESCS if norm_descs else 0) | (VLAD_INTRA_NORM if intra_norm else 0) | \
-        (VLAD_EUCLIDEAN if dist_mode == "euclidean" else 0) | (parts << 8)
-    # (sized for the larger of the library's workgroups-per-image count and the caller's)
-    ws_bytes = lib.anyloc_vlad_workspace_bytes_parts(total, n_img, D, K, parts)
-    ws = _lib.workspace(ws_bytes, device, "vlad")
+        (VLAD_EUCLIDEAN if dist_mode == "euclidean" else 0)
     if mode == "hard":
-        _lib.check(lib.anyloc_vlad_hard(_lib.ptr(packed), _lib.ptr(offsets), n_img, total, D,
-                                        _lib.ptr(centers), K, flags, _lib.ptr(out), _lib.ptr(labels),
-                                        _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "anyloc_vlad_hard")
-    elif mode == "soft":
+        parts, pieces = _vlad_hard_pieces(offsets, n_img, total, D, K, parts)
+        for i0, i1, r0, r1 in pieces:
+            whole = (i0, i1) == (0, n_img)
+            off_p = offsets if whole else offsets[i0:i1 + 1] - r0
+            # (sized for the larger of the library's workgroups-per-image count and the caller's)
+            ws = _lib.workspace(lib.anyloc_vlad_workspace_bytes_parts(r1 - r0, i1 - i0, D, K, parts), device, "vlad")
+            _lib.check(lib.anyloc_vlad_hard(_lib.ptr(packed[r0:r1]), _lib.ptr(off_p), i1 - i0, r1 - r0, D,
+                                            _lib.ptr(centers), K, flags | (parts << 8), _lib.ptr(out[i0:i1]),
+                                            _lib.ptr(labels[r0:r1]) if labels is not None else None,
+                                            _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "anyloc_vlad_hard")
+        return (out, labels) if return_labels else out
+    ws = _lib.workspace(lib.anyloc_vlad_workspace_bytes_parts(total, n_img, D, K, 0), device, "vlad")
+    if mode == "soft":
         _lib.check(lib.anyloc_vlad_soft(_lib.ptr(packed), _lib.ptr(offsets), n_img, total, D,
                                         _lib.ptr(centers), K, float(soft_temp), flags, _lib.ptr(out),
                                         _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "anyloc_vlad_soft")

@@ -55,6 +55,17 @@
  *     *_workspace_bytes() functions answer hold for any such pointer.
  *     tests/test_gpu_guard_bands.py holds every entry point to this between guard
  *     bands, at exactly the documented sizes.
+ *     anyloc_gemm_nt reads the rows of one tile through 2 GiB of 32-bit buffer addressing: (min(tile rows, rows) - 1) * ld * 4
+ *     + K * 4 < 2^31 for A (tiles of 64, 128 or 256 rows: anyloc_gemm_plan_describe) and for W (tiles of 32, 64 or 128 columns);
+ *     a wider row stride is ANYLOC_ERR_INVALID_ARG.
+ *   - Sizes.  Sizes, row counts, offsets and leading dimensions are 64-bit: a tensor may cross 2^31 bytes, 2^32 bytes and
+ *     2^31 elements unless its entry point states a smaller limit.  A shape beyond a limit is never served wrongly: the call
+ *     returns ANYLOC_ERR_INVALID_ARG (ANYLOC_ERR_UNSUPPORTED where this build lacks the kernel) from its argument checks,
+ *     before any device work, and anyloc_last_error() names the limit.  The limits that stem from 32-bit addressing inside
+ *     the kernels are listed, with the line that enforces each, in profiles/addressing_audit.md;
+ *     tests/test_addressing_limits_cpu.py calls every one from its far side, tests/test_gpu_addressing.py runs the near side
+ *     and the entry points at 4 - 8 GiB.  Row counts of the row-wise calls (l2norm, layernorm, the splitters, VLAD and k-means
+ *     tokens, top-k queries) are below 2^31.
  *   - return value: 0 on success, a negative anyloc_status otherwise;
  *     anyloc_last_error() returns a thread-local description of the last
  *     failure.  No C++ exception crosses the ABI.
@@ -163,7 +174,7 @@ int anyloc_reset_options(void);      /* defaults, then ANYLOC_OPTIONS */
 /* ---------------------------------------------------------------- rows ---
  * out[r,:] = x[r,:] / max(||x[r,:]||_2, eps)      (torch F.normalize, eps 1e-12)
  * replaces: F.normalize calls at utilities.py:283, :436-437, :785, :960.
- * x and out may alias. */
+ * x and out may alias.  rows < 2^31; rows * dim is not limited. */
 int anyloc_l2norm_rows(const float* x, float* out, int64_t rows, int64_t dim,
                        float eps, void* stream);
 
@@ -198,7 +209,9 @@ int anyloc_resize_bicubic(const float* in, int64_t planes, int64_t height, int64
  * utilities.py:269 model forward) on the bf16 matrix cores with fp32-level
  * accuracy: every fp32 operand is the exact sum of three bf16 planes and the six
  * leading plane products are accumulated in fp32 (csrc/gemm_x6.hip).
- *   anyloc_x3_bytes   size of the plane image of an fp32 matrix [rows, K]
+ *   anyloc_x3_bytes   size of the plane image of an fp32 matrix [rows, K]; an image anyloc_gemm_nt_x6 reads is below 2^31
+ *                     bytes (6 bytes per element of [rows, K padded to 16]); anyloc_split_x3 writes larger ones too
+ *                     (rows < 2^31, K <= 2 097 120)
  *   anyloc_split_x3   fp32 row-major [rows, K] (leading dim ldx) -> plane image
  *   anyloc_gemm_nt_x6 C[M,N] = A * W^T (+ bias[N]) from the plane images of A [M,K]
  *                     and W [N,K]; C fp32, leading dim ldc. */
@@ -214,7 +227,8 @@ int anyloc_gemm_nt_x6(const void* a3, const void* w3, const float* bias, float* 
  * (22 mantissa bits); the epilogue descales with inv_a[row] * inv_w[col]
  * (csrc/gemm_h3.hip, tools/split_fp16_study.py).
  *   anyloc_split_h2    fp32 [rows, K] (K % 16 == 0, K <= 4096, ldx % 4 == 0) -> plane image
- *                      (anyloc_h2_bytes) + inv_scale[rows] (2^-e of each row)
+ *                      (anyloc_h2_bytes) + inv_scale[rows] (2^-e of each row); rows < 2^31.  An image anyloc_gemm_nt_h3
+ *                      reads is below 2^31 bytes (4 bytes per element); the splitter writes larger ones too
  *   anyloc_gemm_nt_h3  C[M,N] = A W^T (+ bias[N]) from the two images */
 size_t anyloc_h2_bytes(int64_t rows, int64_t K);
 int anyloc_split_h2(const float* x, int64_t ldx, int64_t rows, int64_t K, void* h2,
@@ -304,7 +318,8 @@ int anyloc_gemm_nt_f64(const double* A, int64_t a_rs, int64_t a_cs,
  * (v_mfma_f32_32x32x2_f32) behind retrieval, the VLAD / k-means scores, the patch
  * embedding and the ViT blocks of small batches (torch Linear layout: both
  * operands K-contiguous).  lda/ldw/ldc are row strides in floats.  Requires
- * K % 4 == 0 and 16-byte aligned rows.  Exposed for tests/benchmarks. */
+ * K % 4 == 0 and 16-byte aligned rows, lda and ldw >= K, and the rows of one tile inside 2 GiB (Conventions, Buffers);
+ * M * lda, N * ldw and M * ldc may pass 2^31 elements.  Exposed for tests/benchmarks. */
 int anyloc_gemm_nt(const float* A, int64_t lda, const float* W, int64_t ldw,
                    const float* bias, float* C, int64_t ldc,
                    int64_t M, int64_t N, int64_t K, void* stream);
@@ -337,7 +352,10 @@ int anyloc_gemm_plan_describe(int64_t M, int64_t N, int64_t K, const char* epilo
  * LayerNorm over the last dim (eps as given; DINOv2 uses 1e-6) and multi-head
  * self-attention softmax((q/8) k^T) v with head_dim 64 on a packed QKV buffer
  * [B*T, 3*D] (q | k | v, heads contiguous) -> out [B*T, D].  batch in [1, 65535] for both
- * attention entry points (65 536 images and more: ANYLOC_ERR_INVALID_ARG). */
+ * attention entry points (65 536 images and more: ANYLOC_ERR_INVALID_ARG).  anyloc_layernorm: rows and dim below 2^31; x and y must not overlap (every row is read three times).
+ * anyloc_attention: ONE image's rows stay inside 2 GiB -- tokens * 3 * dim * 4 < 2^31 (21 845 tokens at dim 8192) -- while
+ * the batch may pass 2^31 elements; tokens, dim, heads below 2^31.  anyloc_attention_h3: heads * ceil(batch * tokens / 32) *
+ * 8192 < 2^31 (its q, k and v tile images are below 2 GiB each: batch * tokens * dim * 4 < 2^31 up to the padding). */
 int anyloc_layernorm(const float* x, float* y, const float* weight, const float* bias,
                      int64_t rows, int64_t dim, float eps, void* stream);
 int anyloc_attention(const float* qkv, float* out, int64_t batch, int64_t tokens,
@@ -365,6 +383,13 @@ int anyloc_attention_h3(const float* qkv, void* out_img, float* out_inv, int64_t
  * Limits: K in [1, 256] (anyloc_vlad_soft, anyloc_vlad_soft_weights and the soft weights of anyloc_vlad_assigned: K in
  *   [1, 64]), D a positive multiple of 4; anything else is ANYLOC_ERR_INVALID_ARG.  n_img is not limited by a grid
  *   dimension: the two-pass kernels run in groups of 65 535 images, the one-pass kernel on a 1-D grid.
+ *   total_tokens < 2^31 and D < 2^21 (the score GEMM's tallest tile of 256 rows stays inside 2 GiB); total_tokens * D may pass 2^31 elements.  The one-pass kernel (anyloc_vlad_hard with
+ *   K <= 32 and D in {384, 768, 1024, 1536}, option vlad_two_pass = 0) reads one image's part through 32-bit offsets:
+ *   tokens per image and part < 2^31 / (4 D), in whole tiles of 16 -- at most floor((2^31 - 1) / (4 D) / 16) * 16.  The offsets
+ *   live on the device, so the call bounds an image by total_tokens: ceil(ceil(total_tokens / 16) / parts) * 16 above that
+ *   limit is ANYLOC_ERR_INVALID_ARG (parts: the caller's ANYLOC_VLAD_PARTS, else anyloc_vlad_auto_parts) -- exact for one
+ *   image; a batch of many ordinary images with 2 GiB of tokens per part and more goes over in several calls with the
+ *   whole batch's ANYLOC_VLAD_PARTS (anyloc_amd/ops.py does that), or on the two-pass path, which is 64-bit throughout.
  * flags: ANYLOC_VLAD_NORM_DESCS re-normalises tokens before the residual
  *   (utilities.py:959-960); ANYLOC_VLAD_INTRA_NORM normalises each cluster
  *   block (:859-860).  Labels are argmax_k of the fast-pytorch-kmeans cosine
@@ -432,7 +457,11 @@ int anyloc_vlad_assigned(const float* tokens, int64_t n_tok, int64_t D, const fl
  *   NaN->0 rule, the tolerance test and (multi-GPU) the all-reduce of
  *   sums/counts are done by the host (anyloc_amd/kmeans.py).
  *   mode 0 = cosine (rows/(norm+1e-8)), 1 = euclidean (2ab - a^2 - b^2).
- *   Limits: n >= 1, K in [1, 256], D a positive multiple of 4; anything else is ANYLOC_ERR_INVALID_ARG. */
+ *   Limits: n >= 1, K in [1, 256], D a positive multiple of 4 below 2^21; anything else is ANYLOC_ERR_INVALID_ARG.  n * D may
+ *   pass 2^31 elements.  Option kmeans_max_chunks is an upper bound the library leaves where it must: a chunk never holds
+ *   2 GiB of rows or more (the one-pass kernel reads a chunk through 32-bit offsets), so a long input gets more chunks than
+ *   the option asked for -- at most floor((2^31 - 1) / (4 D) / 16) * 16 rows each; anyloc_kmeans_workspace_bytes counts them.
+ *   The two-pass path (K > 32 or another D): n < 2^31 and at most 65 535 chunks. */
 size_t anyloc_kmeans_workspace_bytes(int64_t n, int64_t D, int64_t K);
 int anyloc_kmeans_step(const float* x, int64_t n, int64_t D, const float* centers,
                        int64_t K, int mode, float* sums, float* counts,
@@ -453,7 +482,8 @@ int anyloc_kmeans_update(const float* sums, const float* counts, const float* ce
  *   metric 0: inner product, best = largest;  1: squared L2, best = smallest.
  *   dist [nq,k] fp32 and idx [nq,k] int64, best first; idx = index_base + row.
  *   k in [1, 1024] (the running lists are merged in LDS); k = 0 and k > 1024 are ANYLOC_ERR_INVALID_ARG, in the
- *   searches of a prepared index too.  dim a positive multiple of 4.
+ *   searches of a prepared index too.  dim a positive multiple of 4 below 2^21 (256 rows of a score tile inside 2 GiB); nq < 2^31; ndb * dim is not limited (the
+ *   database is walked in panels), and idx = index_base + row is an int64 sum.
  *   If k > ndb the tail is padded with idx -1 (faiss behaviour).
  *   Ties are broken towards the lower database index.
  *   flags: ANYLOC_TOPK_NORMALIZE_DB -- the database is given RAW and every row is used as

@@ -125,6 +125,11 @@ def test_pca_u_based_sign_rule_and_rank_deficient_axes():
     assert float((z[:, :39].var(dim=0, unbiased=True) - 1.0).abs().max()) < 1e-2      # whitened: unit variance
 
 
+def f64_product_bar(want_max, contraction):
+    """the float64 matrix-core products against torch float64: 1e-13 of the largest entry x sqrt(contraction length)"""
+    return 1e-13 * want_max * contraction ** 0.5
+
+
 @pytest.mark.parametrize("n,f", [(70, 130), (130, 70), (64, 64), (1, 5), (257, 1031), (260, 1032), (1032, 132)])
 def test_pca_f64_products_vs_float64(n, f):
     """csrc/pca_f64.hip (the float64 matrix-core products of the fit) against the same products in torch float64 of the
@@ -138,12 +143,12 @@ def test_pca_f64_products_vs_float64(n, f):
         got = ops.pca_gram_f64(x, mean, side)
         assert got.dtype == torch.float64 and got.shape == want.shape
         assert torch.equal(got, got.t())                                  # mirrored, not recomputed
-        assert float((got - want).abs().max()) <= 1e-13 * float(want.abs().max()) * max(n, f) ** 0.5
+        assert float((got - want).abs().max()) <= f64_product_bar(float(want.abs().max()), max(n, f))
     k = min(n, 7)
     vec = torch.linalg.qr(torch.randn(n, n, generator=g, dtype=torch.float64))[0].to(DEV)
     got = ops.pca_axes_f64(vec, k, x, mean)
     want = vec[:, :k].t() @ xw
-    assert got.shape == (k, f) and float((got - want).abs().max()) <= 1e-13 * float(want.abs().max() + 1) * n ** 0.5
+    assert got.shape == (k, f) and float((got - want).abs().max()) <= f64_product_bar(float(want.abs().max() + 1), n)
     # eigenvectors are read where they lie: a view of the first k columns, and column-major storage (what eigh returns)
     assert torch.equal(ops.pca_axes_f64(vec[:, :k], k, x, mean), got)
     assert torch.equal(ops.pca_axes_f64(vec.t().contiguous().t(), k, x, mean), got)

@@ -12,6 +12,7 @@ from oracle import faiss_flat, vlad_ref
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 VLAD_RTOL = 1e-5      # north_star: VLAD descriptors within 1e-5 relative (L2-relative, fp32)
+KMEANS_SUMS_RTOL = 1e-6      # the sums of one k-means step against the float64 sums under the same labels (L2-relative)
 
 
 def l2rel(a, b):
@@ -235,7 +236,7 @@ def check_kmeans_step(x, c, mode, sums, counts, lab):
     onehot = (lab_c[None] == torch.arange(K)[:, None]).double()
     assert torch.equal(counts.cpu(), onehot.sum(-1).float())
     err = l2rel(sums, onehot @ x.double())
-    assert err < 1e-6, err
+    assert err < KMEANS_SUMS_RTOL, err
     return excused, err
 
 
