@@ -1,6 +1,7 @@
 """The matrices and the checks that tests/test_eigs_cpu.py and tests/test_gpu_eigs.py share (not a test module): five
 symmetric matrices  S = V diag(lambda) V^T  with a seeded orthogonal V and a known spectrum, their LAPACK decomposition
-(computed once), and the properties a result of ``eigs.sym_topk`` must have.  Everything here runs on the CPU in float64."""
+(computed once), and the properties a result of ``eigs.sym_topk`` must have -- all of that on the CPU in float64; and
+``decaying``, the fp32 data of the PCA tests (tests/test_gpu_pca.py, tests/test_gpu_eigs.py), drawn in float64 on the CPU."""
 import math
 
 import torch
@@ -39,6 +40,16 @@ def case(name):
         lam, vec = torch.linalg.eigh(s)
         _cache[name] = dict(S=s, m=m, k=k, lam=lam.flip(0), vec=vec.flip(1))
     return _cache[name]
+
+
+def decaying(n, f, seed, decay=0.9, rank=None):
+    """[n, f] fp32 rows with singular values 10 * decay^j (a well-separated spectrum) around a common offset: the PCA tests' data"""
+    g = torch.Generator().manual_seed(seed)
+    r = min(n, f) if rank is None else rank
+    q1, _ = torch.linalg.qr(torch.randn(n, r, generator=g, dtype=torch.float64))
+    q2, _ = torch.linalg.qr(torch.randn(f, r, generator=g, dtype=torch.float64))
+    s = 10.0 * decay ** torch.arange(r, dtype=torch.float64)
+    return ((q1 * s) @ q2.t() + 0.3 * torch.randn(1, f, generator=g, dtype=torch.float64)).float()
 
 
 def rank_deficient(m=300, rank=20):

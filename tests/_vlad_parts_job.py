@@ -8,15 +8,11 @@ import sys
 
 import torch
 
+from _vlad_refs import l2rel
 from anyloc_amd import ops, synth
 from oracle import vlad_ref
 
 DEV = "cuda"
-
-
-def l2rel(a, b):
-    a, b = torch.as_tensor(a).double().cpu(), torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
 def main():

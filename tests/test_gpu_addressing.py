@@ -19,6 +19,7 @@ import pytest
 import torch
 
 import _big_cases as BC
+import _vlad_refs as VR
 import test_gpu_kernels as TK
 import test_gpu_long_sequences as TL
 import test_gpu_pca as TPCA
@@ -231,7 +232,7 @@ def _check_kmeans(case, x, centers, mode, got, tag):
     assert differ == 0, (tag, differ)
     assert torch.equal(counts.double(), torch.bincount(want_lab, minlength=K).double()), tag
     assert float(counts.sum()) == c["rows"]
-    err = VT.l2rel(sums, _sums_f64(x, want_lab, K))
+    err = VR.l2rel(sums, _sums_f64(x, want_lab, K))
     print(f"[kmeans {tag}] sums l2rel {err:.3e} (bar {VT.KMEANS_SUMS_RTOL:.0e}), 0 labels differ")
     assert err < VT.KMEANS_SUMS_RTOL, (tag, err)
 
@@ -262,21 +263,6 @@ def test_kmeans_step_past_2g_elements(mode):
 
 
 # ------------------------------------------------------------------------------------------------------------- VLAD
-def _vlad_f64(x, labels, centers, norm_descs, slab=1 << 18):
-    """hard VLAD of ONE image in float64 on the device: per-cluster sums of normalise(x) - c, intra-norm, global norm"""
-    K, D = centers.shape
-    cd = centers.double()
-    acc = torch.zeros(K, D, dtype=torch.float64, device=x.device)
-    for r0 in range(0, x.shape[0], slab):
-        xs = x[r0:r0 + slab].double()
-        if norm_descs:
-            xs = torch.nn.functional.normalize(xs, dim=-1)
-        lab = labels[r0:r0 + slab]
-        acc.index_add_(0, lab, xs - cd[lab])
-    acc = torch.nn.functional.normalize(acc, dim=-1)
-    return torch.nn.functional.normalize(acc.reshape(-1), dim=0)
-
-
 def _vlad_hard(x, offsets, n_img, centers, flags, labels=True):
     """anyloc_vlad_hard into fresh outputs -> (status, out, labels)"""
     from anyloc_amd import _lib
@@ -312,13 +298,13 @@ def test_vlad_hard_one_image_of_2_gib():
     want_lab = _labels_f64(x, centers, "cosine")
     sample = BC.case_sample("tokens_2g")
     assert torch.equal(want_lab[_idx(sample)].cpu(), BC.mode_of(torch.tensor(sample)))
-    want = _vlad_f64(x, want_lab, centers, False)
+    want = VR.hard_vlad_f64(x, centers, want_lab, False, slab=1 << 18)
     for tag, opts, flags in (("one-pass, 2 parts", {}, ops.VLAD_INTRA_NORM | (2 << 8)), ("two-pass", dict(vlad_two_pass=1), ops.VLAD_INTRA_NORM)):
         with ops.options(**opts):
             st, out, lab = _vlad_hard(x, offsets, 1, centers, flags)
         _ok(lib, st, tag)
         assert int((lab != want_lab).sum()) == 0, tag
-        err = VT.l2rel(out[0], want)
+        err = VR.l2rel(out[0], want)
         print(f"[vlad hard, one image of 2 GiB, {tag}] l2rel {err:.3e} (bar {VT.VLAD_RTOL:.0e})")
         assert err < VT.VLAD_RTOL, (tag, err)
 
@@ -359,7 +345,7 @@ def test_vlad_hard_batch_past_2g_elements():
                 xi = x[off_h[i]:off_h[i + 1]]
                 want_lab = _labels_f64(xi, centers, "cosine")
                 assert torch.equal(lab[off_h[i]:off_h[i + 1]], want_lab), (tag, i)
-                err = VT.l2rel(out[i], _vlad_f64(xi, want_lab, centers, norm_descs))
+                err = VR.l2rel(out[i], VR.hard_vlad_f64(xi, centers, want_lab, norm_descs, slab=1 << 18))
                 assert err < VT.VLAD_RTOL, (tag, i, err)
                 worst = max(worst, err)
             print(f"[vlad hard, 8 GiB batch, {tag}, norm_descs={norm_descs}] worst of {len(images)} images {worst:.3e} (bar {VT.VLAD_RTOL:.0e})")
@@ -774,7 +760,7 @@ def test_vlad_assigned_one_image_past_2g_elements():
     ws = _lib.workspace(lib.anyloc_vlad_workspace_bytes(n, 1, D, K), x.device, "vlad")
     _ok(lib, lib.anyloc_vlad_assigned(ptr(x), n, D, ptr(centers), K, ptr(labels), None, ops.VLAD_INTRA_NORM, ptr(out), ptr(ws), ws.numel(),
                                       stream), "vlad_assigned")
-    err = VT.l2rel(out, _vlad_f64(x, labels, centers, False))
+    err = VR.l2rel(out, VR.hard_vlad_f64(x, centers, labels, False, slab=1 << 18))
     print(f"[vlad_assigned, one image of 8 GiB] l2rel {err:.3e} (bar {VT.VLAD_RTOL:.0e})")
     assert err < VT.VLAD_RTOL
 

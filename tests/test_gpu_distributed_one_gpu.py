@@ -5,39 +5,15 @@ all-reduce of sums / counts, broadcast initial draw) -- compared with the single
 on a multi-GPU node is only the transport of the same collectives (tests/test_distributed_cpu.py covers the host logic
 with an injected CPU step)."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
+
+from _ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, fn, out_dir):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        fn(rank, world, out_dir)
-        torch.cuda.synchronize()
-    finally:
-        dist.destroy_process_group()
-
-
-def _run(fn, tmp_path, world=2):
-    mp.spawn(_worker, args=(world, _free_port(), fn, str(tmp_path)), nprocs=world, join=True)
 
 
 def _search_job(rank, world, out_dir):
@@ -102,10 +78,10 @@ def _kmeans_job(rank, world, out_dir):
 
 
 def test_sharded_search_two_ranks_one_gpu(tmp_path):
-    _run(_search_job, tmp_path)
+    run_ranks(_search_job, 2, tmp_path)
     assert (tmp_path / "search_ok").exists()
 
 
 def test_sharded_kmeans_two_ranks_one_gpu(tmp_path):
-    _run(_kmeans_job, tmp_path)
+    run_ranks(_kmeans_job, 2, tmp_path)
     assert (tmp_path / "kmeans_ok").exists()

@@ -12,16 +12,6 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-def decaying(n, f, seed, decay=0.9, rank=None):
-    """(as in tests/test_gpu_pca.py)"""
-    g = torch.Generator().manual_seed(seed)
-    r = min(n, f) if rank is None else rank
-    q1, _ = torch.linalg.qr(torch.randn(n, r, generator=g, dtype=torch.float64))
-    q2, _ = torch.linalg.qr(torch.randn(f, r, generator=g, dtype=torch.float64))
-    s = 10.0 * decay ** torch.arange(r, dtype=torch.float64)
-    return ((q1 * s) @ q2.t() + 0.3 * torch.randn(1, f, generator=g, dtype=torch.float64)).float()
-
-
 def _rand64(*shape, seed):
     g = torch.Generator().manual_seed(seed)
     return torch.randn(*shape, generator=g, dtype=torch.float64).to(DEV)
@@ -130,7 +120,7 @@ def _sklearn_fit(shape, k, whiten):
     from sklearn.decomposition import PCA as SkPCA
     key = (shape, k, whiten)
     if key not in _sk:
-        x = decaying(*shape, seed=1, rank=100)
+        x = E.decaying(*shape, seed=1, rank=100)
         _sk[key] = (x, SkPCA(k, svd_solver="full", whiten=whiten).fit(x.double().numpy()))
     return _sk[key]
 
@@ -151,7 +141,7 @@ def test_pca_subspace_matches_sklearn_full_svd(shape, k, whiten):
     assert full.solver_used_ == "full" and full.n_iter_ == 0
     # the total variance from the trace against the sum of all eigenvalues of the same float64 matrix
     assert torch.allclose(ours.explained_variance_ratio_.double(), full.explained_variance_ratio_.double(), rtol=1e-10, atol=0)
-    y = decaying(33, shape[1], seed=2, rank=33).to(DEV)
+    y = E.decaying(33, shape[1], seed=2, rank=33).to(DEV)
     want = sk.transform(y.double().cpu().numpy())
     tol = 5e-4 if whiten else 1e-4                       # (the bars of test_pca_matches_sklearn_full_svd)
     assert np.abs(ours.transform(y).cpu().numpy() - want).max() < tol * np.abs(want).max()
@@ -159,7 +149,7 @@ def test_pca_subspace_matches_sklearn_full_svd(shape, k, whiten):
 
 def test_pca_subspace_falls_back_on_rank_deficient_data():
     from anyloc_amd import pca
-    x = decaying(600, 2048, seed=1, rank=20).to(DEV)
+    x = E.decaying(600, 2048, seed=1, rank=20).to(DEV)
     sub, full = pca.PCA(32, solver="subspace").fit(x), pca.PCA(32).fit(x)
     assert sub.solver_used_ == "full" and sub.n_iter_ == 0
     assert torch.equal(sub.components_, full.components_) and torch.equal(sub.explained_variance_, full.explained_variance_)
@@ -167,7 +157,7 @@ def test_pca_subspace_falls_back_on_rank_deficient_data():
 
 def test_pca_subspace_falls_back_on_an_ineligible_shape():
     from anyloc_amd import eigs, pca
-    x = decaying(100, 2048, seed=1, rank=60).to(DEV)
+    x = E.decaying(100, 2048, seed=1, rank=60).to(DEV)
     assert not eigs.eligible(100, 32)
     sub, full = pca.PCA(32, solver="subspace").fit(x), pca.PCA(32).fit(x)
     assert sub.solver_used_ == "full" and full.solver_used_ == "full"
@@ -186,7 +176,7 @@ def test_reduce_pca_maps_arpack_to_the_subspace_solver(monkeypatch):
         calls.append(a[1])
         return real(*a, **kw)
     monkeypatch.setattr(eigs, "sym_topk", spy)
-    x, y = decaying(600, 2048, seed=1, rank=100), decaying(33, 2048, seed=2, rank=33)
+    x, y = E.decaying(600, 2048, seed=1, rank=100), E.decaying(33, 2048, seed=2, rank=33)
     a_full, b_full = utilities.reduce_pca(x.numpy(), y.numpy(), 32, svd_solver="full")
     assert calls == []
     utilities.reduce_pca(x.numpy(), y.numpy(), 32)

@@ -5,6 +5,8 @@ import math
 import pytest
 import torch
 
+from _attention_refs import attention_f64
+
 pytestmark = pytest.mark.gpu
 
 
@@ -105,14 +107,6 @@ def test_attention(dev, B, T, heads, kernel, monkeypatch):
     qkv[0, T - 2, D:2 * D] *= 6.0
     out = ops.attention(qkv.to(dev), heads).cpu()
     check_attention(out, qkv, heads)
-
-
-def attention_f64(qkv, heads):
-    """softmax((q / 8) k^T) v per 64-wide head in float64: qkv [B, T, 3 D] -> [B, T, D]"""
-    B, T, D3 = qkv.shape
-    q, k, v = qkv.double().reshape(B, T, 3, heads, 64).permute(2, 0, 3, 1, 4)
-    a = torch.softmax((q * 0.125) @ k.transpose(-2, -1), dim=-1)
-    return (a @ v).transpose(1, 2).reshape(B, T, D3 // 3)
 
 
 def check_attention(out, qkv, heads):

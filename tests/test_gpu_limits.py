@@ -19,9 +19,10 @@ import pytest
 import torch
 
 import _limits_cases as LC
+import _retrieval_refs as R
+import _vlad_refs as VR
 import test_gpu_kernels as TK
 import test_gpu_pooling as TP
-import test_gpu_screen as SC
 import test_gpu_vlad_soft as VS
 import test_gpu_vlad_topk as VT
 from oracle import pool_ref, vlad_ref
@@ -106,15 +107,11 @@ def test_topk_screened_search_ends_at_128(k, screens):
     both give the float64 lists (the rules of tests/test_gpu_screen.py)."""
     from anyloc_amd import ops
     nq, ndb, dim = 130, 9000, 2048
-    qu, db = SC._data(nq, ndb, dim, nq + ndb + dim)
+    qu, db = R.planted_rows(nq, ndb, dim, nq + ndb + dim)
     with ops.options(topk_screen=1, topk_h3=1):
-        ops.profile_enable(True); ops.profile_reset()
-        d, i = ops.topk(qu, db, k, "ip", normalize_db=True)
-        torch.cuda.synchronize()
-        prof = ops.profile_dump()
-        ops.profile_enable(False)
+        (d, i), prof = R.profiled(lambda: ops.topk(qu, db, k, "ip", normalize_db=True))
     assert ("topk_screen_gemm" in prof) == screens and ("topk_scores_gemm" in prof) == (not screens), sorted(prof)
-    SC._check(d, i, qu, db, k, "ip", f"k={k}")
+    R.check_search(d, i, qu, db, k, "ip", f"k={k}")
 
 
 @pytest.mark.parametrize("order", ["constant", "ascending"])
@@ -231,9 +228,9 @@ def test_vlad_65538_images(mode, D, K):
             if mode == "hard":
                 err = VT.check_vlad_hard_image(out[i], lab[t0:t1], x_i, centers)
             else:
-                err = VT.l2rel(out[i], vlad_ref.vlad_soft(x_i, centers, 7.5)[0])
+                err = VR.l2rel(out[i], vlad_ref.vlad_soft(x_i, centers, 7.5)[0])
                 assert err < VT.VLAD_RTOL, (i, err)
-            assert VT.l2rel(out[i], alone[i - a]) < VT.VLAD_RTOL, i
+            assert VR.l2rel(out[i], alone[i - a]) < VT.VLAD_RTOL, i
             worst = max(worst, err)
     print(f"[vlad {mode} D={D} K={K}, {N_IMG} images] worst l2rel to the oracle {worst:.3e} (bar {VT.VLAD_RTOL:.0e})")
 

@@ -17,6 +17,7 @@ tests: attention <= 2e-5 abs, unit-norm tokens <= 2e-5 max-abs in all three GEMM
 import pytest
 import torch
 
+from _attention_refs import attention_f64, spiky_qkv
 from anyloc_amd import synth, weights
 from oracle import dinov2_ref
 
@@ -29,23 +30,6 @@ VPAIR = (588, 798)               # T = 2395
 DEMO_CAP = (1022, 1022)          # T = 5330
 
 
-def _attention_f64(qkv, heads, want_smax=False):
-    """softmax((q / 8) k^T) v in float64, one head at a time (T = 5330: 227 MB per head); ``want_smax``: also the
-    largest |logit| of every query row over its heads."""
-    B, T, D3 = qkv.shape
-    D = D3 // 3
-    out = torch.empty(B, T, D, dtype=torch.float64)
-    smax = torch.zeros(B, T, dtype=torch.float64)
-    x = qkv.double().reshape(B, T, 3, heads, 64)
-    for b in range(B):
-        for h in range(heads):
-            q, k, v = x[b, :, 0, h], x[b, :, 1, h], x[b, :, 2, h]
-            s = (q * 0.125) @ k.t()
-            smax[b] = torch.maximum(smax[b], s.abs().amax(dim=1))
-            out[b, :, h * 64:(h + 1) * 64] = torch.softmax(s, dim=-1) @ v
-    return (out, smax) if want_smax else out
-
-
 def check_attention_long(err_rows, smax, vmax, ref_max):
     """anyloc_attention at long sequences: the largest absolute error of every query row against float64.  fp32 logits carry
     2^-24 |s| of rounding, i.e. that RELATIVE error on the row's probabilities (the reference's fp32 attention has the same):
@@ -55,20 +39,6 @@ def check_attention_long(err_rows, smax, vmax, ref_max):
     assert bool((err_rows <= bar).all()), (float(err_rows.max()), float((err_rows / bar).max()))
     assert float(err_rows.max() / ref_max) < 1e-5
     return float((err_rows / bar).max())
-
-
-def _spiky_qkv(B, T, heads, seed):
-    D = heads * 64
-    g = torch.Generator().manual_seed(seed)
-    qkv = torch.randn(B, T, 3 * D, generator=g) * 1.5
-    qkv[0, 3, :D] *= 6.0                                  # a spiky query / key pair: the running-max rescale path
-    qkv[0, T - 2, D:2 * D] *= 6.0
-    qkv[:, ::7] *= 0.05                                   # small-magnitude tokens next to ordinary ones
-    qkv[:, 5, 2 * D:] *= 40.0                             # one value row far above the others (sets the image scale)
-    if T > 2080:
-        qkv[0, 2048:2080, 2 * D:] = 0.0                   # an all-zero V tile beyond key group 64: must not set the scale
-    qkv[B - 1, T - 40:, D:2 * D] *= 3.0                   # loud keys in the LAST key groups of the last image
-    return qkv
 
 
 LONG_T = [(1, 1531, 24), (3, 1531, 2), (2, 2395, 3), (1, 5330, 2), (3, 5330, 1), (2, 2047, 2), (2, 2049, 1)]
@@ -85,10 +55,10 @@ def test_attention_h3_long_sequences(B, T, heads, ks):
     _lib.load()
     ops.set_option("attn_h3_ks", ks)                      # both workgroup shapes (the library picks by grid size)
     D = heads * 64
-    qkv = _spiky_qkv(B, T, heads, B * T + heads)
+    qkv = spiky_qkv(B, T, heads, B * T + heads)
     img, inv = ops.attention_h3(qkv.to(DEV), heads)
     out = ops.h2_image_to_f32(img, inv, B * T, D).reshape(B, T, D).cpu()
-    ref = _attention_f64(qkv, heads)
+    ref = attention_f64(qkv, heads, per_head=True)
     vmax = qkv[:, :, 2 * D:].abs().amax(dim=(1, 2)).double()
     err = (out - ref).abs().amax(dim=(1, 2))
     # every row of an image carries 22 bits relative to the image's largest |v| (tests/test_gpu_kernels.py)
@@ -114,7 +84,7 @@ def test_attention_long_sequences(B, T, heads, kernel):
     qkv[0, 3, :D] *= 6.0
     qkv[0, T - 2, D:2 * D] *= 6.0
     out = ops.attention(qkv.to(DEV), heads).cpu()
-    ref, smax = _attention_f64(qkv, heads, want_smax=True)
+    ref, smax = attention_f64(qkv, heads, per_head=True, want_smax=True)
     vmax = float(qkv[:, :, 2 * D:].abs().max())
     check_attention_long((out.double() - ref).abs().amax(dim=2), smax, vmax, ref.abs().max())
 

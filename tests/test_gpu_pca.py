@@ -5,17 +5,10 @@ import numpy as np
 import pytest
 import torch
 
+from _eigs_cases import decaying
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def decaying(n, f, seed, decay=0.9, rank=None):
-    g = torch.Generator().manual_seed(seed)
-    r = min(n, f) if rank is None else rank
-    q1, _ = torch.linalg.qr(torch.randn(n, r, generator=g, dtype=torch.float64))
-    q2, _ = torch.linalg.qr(torch.randn(f, r, generator=g, dtype=torch.float64))
-    s = 10.0 * decay ** torch.arange(r, dtype=torch.float64)
-    return ((q1 * s) @ q2.t() + 0.3 * torch.randn(1, f, generator=g, dtype=torch.float64)).float()
 
 
 @pytest.mark.parametrize("shape,k,whiten", [((200, 3072), 32, False), ((200, 3072), 32, True),

@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _attention_refs import attention_f64, spiky_qkv_image
 from anyloc_amd import synth, weights
 from oracle import dinov2_ref
 
@@ -17,30 +18,6 @@ SIZES = [(224, 224), (476, 630), (14, 14), (322, 322), (98, 154)]
 
 
 # ---------------------------------------------------------------- attention kernels alone ----
-
-def _attention_f64(qkv, heads):
-    T, D3 = qkv.shape
-    D = D3 // 3
-    x = qkv.double().reshape(T, 3, heads, 64)
-    out = torch.empty(T, D, dtype=torch.float64)
-    for h in range(heads):
-        q, k, v = x[:, 0, h], x[:, 1, h], x[:, 2, h]
-        out[:, h * 64:(h + 1) * 64] = torch.softmax((q * 0.125) @ k.t(), dim=-1) @ v
-    return out
-
-
-def _spiky_qkv(T, heads, seed):
-    """The spiky generator of tests/test_gpu_long_sequences.py, one image: a loud query / key pair (running-max rescale),
-    small-magnitude tokens next to ordinary ones, one value row far above the others (sets the image's scale)."""
-    D = heads * 64
-    g = torch.Generator().manual_seed(seed)
-    qkv = torch.randn(T, 3 * D, generator=g) * 1.5
-    qkv[min(3, T - 1), :D] *= 6.0
-    qkv[max(T - 2, 0), D:2 * D] *= 6.0
-    qkv[::7] *= 0.05
-    qkv[min(5, T - 1), 2 * D:] *= 40.0
-    return qkv
-
 
 # token counts: T = 2 (a 14 x 14 image), T > 1984 (more than 64 key groups: per-tile scales from memory), ordinary ones;
 # none a multiple of 32, so every image after the first starts inside a 32-row group it shares with its neighbour
@@ -89,13 +66,13 @@ def test_ragged_attention_vs_float64(kernel, ks, xcd):
     ops.set_option("attn_h3_ragged_xcd", xcd)          # both workgroup orders of the two-term fp16 kernel
     heads = 2
     D = heads * 64
-    parts = [_spiky_qkv(t, heads, 100 + i) for i, t in enumerate(RAGGED_T)]
+    parts = [spiky_qkv_image(t, heads, 100 + i) for i, t in enumerate(RAGGED_T)]
     qkv = torch.cat(parts)
     try:
         out, off = _run_ragged_attention(kernel, qkv, RAGGED_T, heads)
         assert bool(torch.isfinite(out).all())
         for i, p in enumerate(parts):
-            ref = _attention_f64(p, heads)
+            ref = attention_f64(p, heads, per_head=True)
             got = out[off[i]:off[i + 1]]
             vmax = float(p[:, 2 * D:].abs().max())
             err = float((got - ref).abs().max())

@@ -4,18 +4,14 @@
   prints one JSON line with ``n_gpus: 2`` -- through the ``ANYLOC_DIST_BACKEND=gloo`` override, both ranks on cuda:0;
 * every tensor the sharded retrieval / sharded k-means hand to a collective lives on the comm device when the backend is
   not gloo (a "fake RCCL" group: gloo transport, ``get_backend`` answering "nccl", collectives asserting ``is_cuda``);
-* a hub-layout ``.pth`` on disk (a random-init ``transformers.Dinov2Model`` remapped to the facebookresearch key
-  names) is found through ``ANYLOC_DINOV2_WEIGHTS`` and gives the tokens the HF model itself computes
-  (reference ``utilities.py:239-242``: ``torch.hub.load`` + ``.eval().to(device)``).
+* scheduling variants of LayerNorm, the transposed SwiGLU epilogue and gemm_h3 on the 16x16x32 MFMA against the forms they
+  replace.
 
-The reference's own ``scripts/dino_v2_vlad.py`` is not run here: a GPU test reads nothing outside this tree.  The script runs
-unmodified on the CPU oracle backend in tests/test_reference_scripts_cpu.py, its call sequence runs on the HIP path in
-tests/test_gpu_round4.py (tests/drivers/vlad_driver_standin.py), and tools/reference_scripts_on_hip.py runs the reference's
-scripts on the HIP path wherever a reference tree is at hand.
+The round's top-k tests are in tests/test_gpu_topk_panels.py and tests/test_gpu_topk_fewq.py, its checkpoint-file test in
+tests/test_gpu_call_patterns.py.
 """
 import json
 import os
-import socket
 import subprocess
 import sys
 
@@ -25,6 +21,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from _ranks import free_port
 from anyloc_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -46,15 +43,6 @@ def test_bench_gpus2_plain_invocation_spawns_its_ranks():
     assert out["config"]["images_per_step"] == 16 and out["config"]["parallelism"] == "dp2+db-shard2"
     # merged global indices over both shards (rank r's places live at rows r * 10 000 ...): recalls are fractions, nested in k
     assert 0.0 <= out["recall"]["1"] <= out["recall"]["5"] <= out["recall"]["10"] <= 1.0
-
-
-# ------------------------------------------------------------------------------------- collectives on the comm device
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _fake_rccl():
@@ -156,184 +144,8 @@ def _fake_rccl_worker(rank, world, port, out_dir):
 
 
 def test_collectives_get_device_tensors_under_a_non_gloo_backend(tmp_path):
-    mp.spawn(_fake_rccl_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_fake_rccl_worker, args=(2, free_port(), str(tmp_path)), nprocs=2, join=True)
     assert (tmp_path / "ok").exists()
-
-
-# ---------------------------------------------------------------------------------- checkpoint file in hub layout
-def hf_to_hub(hf_sd, depth, swiglu):
-    """transformers.Dinov2Model state dict -> facebookresearch/dinov2 key layout (the inverse of the remap in
-    tests/test_oracle_dinov2_hf.py): fused qkv, ``ls*.gamma``, ``mlp.w12 / w3``."""
-    sd = {"cls_token": hf_sd["embeddings.cls_token"], "mask_token": hf_sd["embeddings.mask_token"],
-          "pos_embed": hf_sd["embeddings.position_embeddings"],
-          "patch_embed.proj.weight": hf_sd["embeddings.patch_embeddings.projection.weight"],
-          "patch_embed.proj.bias": hf_sd["embeddings.patch_embeddings.projection.bias"],
-          "norm.weight": hf_sd["layernorm.weight"], "norm.bias": hf_sd["layernorm.bias"]}
-    for i in range(depth):
-        p, q = f"blocks.{i}.", f"encoder.layer.{i}."
-        sd[p + "attn.qkv.weight"] = torch.cat([hf_sd[q + f"attention.attention.{n}.weight"] for n in ("query", "key", "value")])
-        sd[p + "attn.qkv.bias"] = torch.cat([hf_sd[q + f"attention.attention.{n}.bias"] for n in ("query", "key", "value")])
-        sd[p + "attn.proj.weight"], sd[p + "attn.proj.bias"] = hf_sd[q + "attention.output.dense.weight"], hf_sd[q + "attention.output.dense.bias"]
-        for n in ("norm1", "norm2"):
-            sd[p + n + ".weight"], sd[p + n + ".bias"] = hf_sd[q + n + ".weight"], hf_sd[q + n + ".bias"]
-        sd[p + "ls1.gamma"], sd[p + "ls2.gamma"] = hf_sd[q + "layer_scale1.lambda1"], hf_sd[q + "layer_scale2.lambda1"]
-        if swiglu:
-            sd[p + "mlp.w12.weight"], sd[p + "mlp.w12.bias"] = hf_sd[q + "mlp.weights_in.weight"], hf_sd[q + "mlp.weights_in.bias"]
-            sd[p + "mlp.w3.weight"], sd[p + "mlp.w3.bias"] = hf_sd[q + "mlp.weights_out.weight"], hf_sd[q + "mlp.weights_out.bias"]
-        else:
-            for f in ("fc1", "fc2"):
-                sd[p + f"mlp.{f}.weight"], sd[p + f"mlp.{f}.bias"] = hf_sd[q + f"mlp.{f}.weight"], hf_sd[q + f"mlp.{f}.bias"]
-    return {k: v.detach().clone().contiguous() for k, v in sd.items()}
-
-
-def test_hub_layout_checkpoint_file_through_env(tmp_path, monkeypatch):
-    transformers = pytest.importorskip("transformers")
-    import utilities
-    from anyloc_amd import weights
-    from oracle import dinov2_ref
-    name, layer = "dinov2_vits14", 9
-    dim, depth, heads, ffn, hidden = dinov2_ref.ARCH[name]
-    torch.manual_seed(5)
-    cfg = transformers.Dinov2Config(hidden_size=dim, num_hidden_layers=depth, num_attention_heads=heads, mlp_ratio=4,
-                                    image_size=518, patch_size=14, layerscale_value=1.0, use_swiglu_ffn=False,
-                                    layer_norm_eps=1e-6, qkv_bias=True, hidden_act="gelu", attn_implementation="eager")
-    hf = transformers.Dinov2Model(cfg).eval()
-    with torch.no_grad():                                   # HF initialises biases to zero: give the file real ones
-        for n_, p_ in hf.named_parameters():
-            if n_.endswith(".bias"):
-                p_.normal_(0.0, 0.02)
-    path = tmp_path / f"{name}_pretrain.pth"                # the file name facebookresearch publishes
-    torch.save(hf_to_hub(hf.state_dict(), depth, False), str(path))
-    weights.unregister_state_dict()
-    monkeypatch.setenv("ANYLOC_DINOV2_WEIGHTS", str(tmp_path))      # a directory holding <name>_pretrain.pth ...
-    ext = utilities.DinoV2ExtractFeatures(name, layer, "value", device="cuda")
-    monkeypatch.setenv("ANYLOC_DINOV2_WEIGHTS", str(path))          # ... or the file itself
-    ext_file = utilities.DinoV2ExtractFeatures(name, layer, "value", device="cuda:0")
-    g = torch.Generator().manual_seed(1)
-    img = torch.randn(2, 3, 518, 518, generator=g)          # native grid: HF and the hub code use the same positional table
-    got = ext(img.to("cuda")).cpu()
-    assert torch.equal(got, ext_file(img.to("cuda")).cpu())
-    with torch.no_grad():
-        hs = hf(pixel_values=img, output_hidden_states=True).hidden_states[layer]
-        lay = hf.encoder.layer[layer]
-        v_hf = torch.nn.functional.normalize(lay.attention.attention.value(lay.norm1(hs))[:, 1:], dim=-1)
-        model = dinov2_ref.build(name, torch.load(str(path)))
-        v_or = dinov2_ref.extract_facet(model, img, layer, "value")
-    assert got.shape == (2, 1369, dim)
-    assert float((got - v_or).abs().max()) < 2e-5            # the restated hub model on the same file
-    assert float((got - v_hf).abs().max()) < 1e-4            # the independent implementation the file came from
-
-
-# ------------------------------------------------------------- retrieval score panels on the two-term fp16 GEMM
-def _flat_oracle(qu, db, k, metric, norm):
-    from oracle import faiss_flat
-    q = torch.nn.functional.normalize(qu) if norm else qu
-    d = torch.nn.functional.normalize(db) if norm else db
-    return faiss_flat.flat_search(q, d, k, metric)
-
-
-def _check_topk(d_g, i_g, qu, db, k, metric, norm):
-    """Indices identical to the flat-index restatement except at PROVEN near-ties (float64 scores of the two swapped
-    rows closer than 2e-6), distances within 3e-6 of the float64 scores of the rows the kernel returned."""
-    d_r, i_r = _flat_oracle(qu, db, k, metric, norm)
-    q64 = (torch.nn.functional.normalize(qu.double()) if norm else qu.double())
-    d64 = (torch.nn.functional.normalize(db.double()) if norm else db.double())
-    i_g, d_g = i_g.cpu(), d_g.cpu()
-    for n in range(qu.shape[0]):
-        rows = d64[i_g[n]]
-        exact = rows @ q64[n] if metric == "ip" else ((rows - q64[n]) ** 2).sum(1)
-        scale = max(1.0, float(exact.abs().max()))
-        assert float((d_g[n].double() - exact).abs().max()) <= 3e-6 * scale, (n, float((d_g[n].double() - exact).abs().max()))
-        bad = (i_g[n] != i_r[n]).nonzero().flatten()
-        for j in bad.tolist():
-            other = d64[i_r[n, j]]
-            e_o = float(other @ q64[n]) if metric == "ip" else float(((other - q64[n]) ** 2).sum())
-            assert abs(e_o - float(exact[j])) <= 2e-6 * scale, (n, j, e_o, float(exact[j]))
-
-
-@pytest.mark.parametrize("metric", ["ip", "l2"])
-@pytest.mark.parametrize("norm", [False, True])
-def test_topk_fp16_score_panels_vs_oracle(metric, norm):
-    """Option topk_h3 = 1: the many-query score panels on gemm_h3 (22-bit row-scaled operands, fp32 accumulate) -- uneven
-    panel tail (8192 + 1808 rows), a tie across panels, rows of very different magnitude, k above one panel's merge step."""
-    from anyloc_amd import ops
-    g = torch.Generator().manual_seed(3)
-    dim, ndb, nq, k = 2048, 10000, 150, 25
-    db = torch.randn(ndb, dim, generator=g) * (0.05 + torch.rand(ndb, 1, generator=g) * 20.0)
-    qu = torch.randn(nq, dim, generator=g)
-    qu[:40] = db[torch.arange(40) * 211 + 7] + 0.3 * torch.randn(40, dim, generator=g)
-    db[9000] = db[12]                                              # identical rows in two panels: lower index first
-    with ops.options(topk_h3=1):
-        d, i = ops.topk(torch.nn.functional.normalize(qu).to("cuda") if norm else qu.to("cuda"), db.to("cuda"), k, metric,
-                        normalize_db=norm)
-        d1, i1 = ops.topk(torch.nn.functional.normalize(qu).to("cuda") if norm else qu.to("cuda"), db.to("cuda"), k, metric,
-                          normalize_db=norm)
-    assert torch.equal(i, i1) and torch.equal(d, d1)               # run-to-run reproducible
-    _check_topk(d, i, qu, db, k, metric, norm)
-    hit = (i.cpu() == 12).nonzero()
-    for n, j in hit.tolist():                                      # the duplicated row: index 12 directly before 9000
-        if j + 1 < k:
-            assert int(i[n, j + 1]) == 9000 and float(d[n, j]) == float(d[n, j + 1])
-    # ... and the same lists as the fp32-MFMA panels give (identical except proven near-ties, checked against float64 above)
-    with ops.options(topk_h3=0):
-        d0, i0 = ops.topk(torch.nn.functional.normalize(qu).to("cuda") if norm else qu.to("cuda"), db.to("cuda"), k, metric,
-                          normalize_db=norm)
-    assert float((i0 != i).float().mean()) < 0.002
-
-
-def test_topk_fp16_score_panels_vlad_width():
-    """The config-3 row width (49 152) at a size the CPU can score: 300 queries x 3000 unit-block VLADs, cosine with the
-    database normalised inside the search."""
-    from anyloc_amd import ops
-    g = torch.Generator().manual_seed(9)
-    K, D = 32, 1536
-    db = torch.nn.functional.normalize(torch.randn(3000, K, D, generator=g), dim=-1).reshape(3000, K * D) * 3.0
-    qu = torch.nn.functional.normalize(torch.randn(300, K, D, generator=g), dim=-1).reshape(300, K * D)
-    qu[:50] = 0.8 * db[torch.arange(50) * 37 + 3] / 3.0 + 0.2 * qu[:50]
-    with ops.options(topk_h3=1):
-        d, i = ops.topk(torch.nn.functional.normalize(qu).to("cuda"), db.to("cuda"), 20, "ip", normalize_db=True)
-    assert torch.equal(i[:50, 0].cpu(), torch.arange(50) * 37 + 3)
-    _check_topk(d, i, qu, db, 20, "ip", True)
-
-
-def test_topk_fp16_score_panels_on_the_16x16x32_kernel():
-    """>= 2048 queries against a full 8192-row panel of >= 4096 columns: the panel GEMM is gemm_h3m_kernel (256 x 256 tiles,
-    v_mfma_f32_16x16x32_f16), first K chunk plain, second chunk accumulating (here on gemm_h3_kernel: 512 columns), the
-    600-row tail panel on gemm_h3_kernel -- checked like every other panel path, and against the lists gemm_h3_kernel gives."""
-    from anyloc_amd import ops
-    g = torch.Generator().manual_seed(11)
-    dim, ndb, nq, k = 8192 + 512, 8192 + 600, 2100, 20
-    db = torch.randn(ndb, dim, generator=g) * (0.05 + torch.rand(ndb, 1, generator=g) * 20.0)
-    qu = torch.randn(nq, dim, generator=g)
-    qu[:64] = db[torch.arange(64) * 131 + 5] + 0.3 * torch.randn(64, dim, generator=g)
-    qu[-64:] = db[torch.arange(64) * 7 + 8200 - 448] + 0.3 * torch.randn(64, dim, generator=g)   # (rows of both panels)
-    qg, dg = torch.nn.functional.normalize(qu).to("cuda"), db.to("cuda")
-    d, i = ops.topk(qg, dg, k, "ip", normalize_db=True)
-    with ops.options(h3_mfma16=0):
-        d0, i0 = ops.topk(qg, dg, k, "ip", normalize_db=True)
-    assert float((i0 != i).float().mean()) < 0.002 and float((d0 - d).abs().max()) <= 3e-6
-    sel = torch.cat([torch.arange(0, 128), torch.arange(nq - 128, nq)])
-    _check_topk(d[sel.to("cuda")], i[sel.to("cuda")], qu[sel], db, k, "ip", True)
-
-
-def test_split_h2_wide_rows():
-    """anyloc_split_h2 above 4096 columns (retrieval rows): 22 bits relative to the row maximum, rows of any magnitude,
-    a zero row, a ragged last row group."""
-    from anyloc_amd import ops
-    g = torch.Generator().manual_seed(1)
-    rows, K = 37, 49152
-    x = torch.randn(rows, K, generator=g) * torch.pow(10.0, torch.randint(-6, 6, (rows, 1), generator=g).float())
-    x[5] = 0.0
-    x[7, 100] = 3e4 * float(x[7].abs().max())                      # one element 3e4 above the rest of its row
-    img, inv = ops.split_h2(x.to("cuda"))
-    back = ops.h2_image_to_f32(img, inv, rows, K).cpu()
-    amax = x.double().abs().max(dim=1, keepdim=True)[0]
-    err = (back - x.double()).abs() / amax.clamp_min(1e-300)
-    assert float(err[torch.arange(rows) != 5].max()) <= 2.0 ** -21 and float(back[5].abs().max()) == 0.0
-    # the scale puts the row maximum in [2^14, 2^15)
-    top = amax.squeeze(1) / inv.cpu().double()
-    ok = (top >= 2.0 ** 14) & (top < 2.0 ** 15)
-    assert bool(ok[torch.arange(rows) != 5].all())
 
 
 # ------------------------------------------------------------------- scheduling variants must not change a bit
@@ -355,54 +167,6 @@ def test_scheduling_variants_are_bitwise_equal():
                 assert torch.equal(ext(img), base), opts
     finally:
         weights.unregister_state_dict(name)
-
-
-@pytest.mark.parametrize("metric,norm", [("ip", True), ("ip", False), ("l2", True), ("l2", False)])
-def test_topk_few_queries_on_the_fly_bf16_split(metric, norm):
-    """Option topk_fewq_x6 = 1: <= 64 queries, the database rows split on the fly into three bf16 planes (six bf16 MFMA
-    products, csrc/scores_x6.hip) -- ragged row tail (10 000 + 37 rows = 79 tiles, the last one 5 rows), 61 and 3 queries
-    (zero-padded query columns), K slices, row norms from the same pass, vs the flat-index restatement and float64."""
-    from anyloc_amd import ops
-    g = torch.Generator().manual_seed(11)
-    dim, ndb = 8192, 10037
-    scale = 0.05 + torch.rand(ndb, 1, generator=g) * 20.0
-    scale[12] = 25.0                                                # the planted top hit also wins the raw inner product
-    db = torch.randn(ndb, dim, generator=g) * scale
-    db[5000] = db[12]
-    for nq, k in ((61, 20), (3, 7)):
-        qu = torch.randn(nq, dim, generator=g)
-        pick = torch.arange(min(nq, 30)) * 301 + 12
-        qu[: len(pick)] = db[pick] + 0.3 * scale[pick] * torch.randn(len(pick), dim, generator=g)
-        qd = (torch.nn.functional.normalize(qu) if norm else qu).to("cuda")
-        with ops.options(topk_fewq_x6=1):
-            d, i = ops.topk(qd, db.to("cuda"), k, metric, normalize_db=norm)
-            d1, i1 = ops.topk(qd, db.to("cuda"), k, metric, normalize_db=norm)
-        assert torch.equal(i, i1) and torch.equal(d, d1)
-        _check_topk(d, i, qu, db, k, metric, norm)
-        assert int(i[0, 0]) == 12 and int(i[0, 1]) == 5000          # the duplicated row: lower index first
-        with ops.options(topk_fewq_x6=0):
-            d0, i0 = ops.topk(qd, db.to("cuda"), k, metric, normalize_db=norm)
-        assert float((i0 != i).float().mean()) < 0.003
-
-
-@pytest.mark.parametrize("nq", [8, 200])
-def test_topk_self_match_keeps_the_small_products(nq):
-    """A query that IS a database row (cosine 1): every term of the contraction is a square, so products that are dropped or
-    absorbed add up instead of averaging out -- the few-query bf16 split keeps its 2^-16-sized plane products in their own
-    accumulator, the fp16 panels cut K into chunks.  131 072 columns (the ViT-L two-tap VLAD), vs float64."""
-    from anyloc_amd import ops
-    g = torch.Generator().manual_seed(5)
-    dim, ndb = 131072, 260
-    db = torch.nn.functional.normalize(torch.randn(ndb, dim, generator=g).abs() + 0.5, dim=1) * 2.5     # all-positive rows
-    qu = db[:nq].clone()
-    with ops.options(topk_h3=1):
-        d, i = ops.topk(torch.nn.functional.normalize(qu).to("cuda"), db.to("cuda"), 5, "ip", normalize_db=True)
-    assert torch.equal(i[:, 0].cpu(), torch.arange(nq))
-    _check_topk(d, i, qu, db, 5, "ip", True)
-    q64 = torch.nn.functional.normalize(qu.double())
-    d64 = torch.nn.functional.normalize(db.double())
-    exact = (q64 @ d64.t()).topk(5, dim=1)[0]
-    assert float((d.cpu().double() - exact).abs().max()) <= 2e-6
 
 
 def test_swiglu_transposed_epilogue_agrees_with_the_lds_one():

@@ -1,171 +1,68 @@
-"""Round 6 (``pytest -m gpu``): the prepared flat index (faiss' ``index.add`` apart from ``index.search``: ABI 8,
-``anyloc_topk_index_build`` / ``anyloc_topk_search_index``), the overlapped sharded step on it, the workspace of a caller's
-workgroups-per-image count, and the gather hazard of the one-pass VLAD kernel."""
+"""Round 6 (``pytest -m gpu``): the overlapped sharded step on the prepared flat index, the workspace of a caller's
+workgroups-per-image count, the gather hazard of the one-pass VLAD kernel, the FFN-bound telemetry and the
+LayerNorm lead role.  The tests of the prepared index itself are in tests/test_gpu_topk_panels.py."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
+
+from _ranks import run_ranks
+from _retrieval_refs import _screened_without_fallback, check_lists, exact_scores64, profiled, spread_rows
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-def _rows(n, dim, seed, spread=True):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n, dim, generator=g)
-    if spread:
-        x = x * (0.25 + 4.0 * torch.rand(n, 1, generator=g))          # row norms over more than a decade
-    return x
-
-
-@pytest.mark.parametrize("ndb,dim,nq,k", [(9001, 1024, 70, 20), (8192, 512, 300, 5), (20000, 256, 129, 33), (300, 2048, 65, 400)])
-def test_prepared_index_gives_the_lists_of_the_one_shot_search(ndb, dim, nq, k):
-    """``anyloc_topk_search_index`` reads the panels ``anyloc_topk_index_build`` left instead of quantising the database per
-    call: the same score kernels on the same operand images, so distances and indices are those of ``anyloc_topk`` on its fp16
-    panels BIT FOR BIT -- both metrics, normalising or not, a ragged last panel, k beyond the database (-1 padding), an index
-    base -- and identical to a float64 flat search."""
-    from anyloc_amd import ops
-    db, qu = _rows(ndb, dim, 1).to(DEV), _rows(nq, dim, 2).to(DEV)
-    db[7] = db[ndb - 3]                                                # a tie across panels: lower index first
-    index = ops.topk_index_build(db)
-    assert index.numel() == ops.topk_index_bytes(ndb, dim) > 0
-    for metric in ("ip", "l2"):
-        for norm in (False, True):
-            q = ops.l2norm_rows(qu) if norm else qu
-            with ops.options(topk_h3=1):                               # the one-shot search on the same (fp16 panel) path
-                d0, i0 = ops.topk(q, db, k, metric, index_base=11, normalize_db=norm)
-            d1, i1 = ops.topk_indexed(q, index, ndb, k, metric, index_base=11, normalize_db=norm)
-            assert torch.equal(i0, i1), (metric, norm)
-            assert torch.equal(d0, d1), (metric, norm)
-            # against float64
-            dbn = torch.nn.functional.normalize(db.double(), dim=1) if norm else db.double()
-            s = q.double() @ dbn.t()
-            if metric == "l2":
-                s = -((q.double() ** 2).sum(1, keepdim=True) + (dbn ** 2).sum(1)[None] - 2 * s)
-            kk = min(k, ndb)
-            ref = torch.sort(s, dim=1, descending=True, stable=True)
-            got_i = (i1[:, :kk] - 11)
-            same = got_i == ref.indices[:, :kk]
-            # a differing index is a near-tie of the float64 scores
-            alt = torch.gather(s, 1, got_i.clamp_min(0))
-            assert bool((same | ((alt - ref.values[:, :kk]).abs() <= 3e-6 * ref.values[:, :kk].abs().clamp_min(1.0))).all()), (metric, norm)
-            if k > ndb:
-                assert bool((i1[:, ndb:] == -1).all())
-
-
-def test_flat_index_object_serves_few_and_many_queries_and_drops_the_rows():
-    """``retrieval.FlatIndex``: built once, searched several times -- few queries stream the fp32 rows (anyloc_topk's few-query
-    path), many read the prepared planes; ``keep_fp32=False`` serves both from the planes.  All agree with ``retrieval.search``."""
+def _prepared_shards_job(rank, world, out_dir):
     from anyloc_amd import retrieval
-    dim = 4096
-    db, qu = _rows(3000, dim, 3).to(DEV), _rows(300, dim, 4).to(DEV)
-    for method in ("cosine", "l2"):
-        ix = retrieval.FlatIndex(db, method, planes=True)
-        assert ix.has_planes and ix.ntotal == 3000
-        for n in (9, 200, 300):                                      # few-query stream / fp32-MFMA panels / fp16 panels (prepared)
-            d0, i0 = retrieval.search(db, qu[:n], 10, method)
-            d1, i1 = ix.search(qu[:n], 10)
-            assert torch.equal(i0, i1) and torch.equal(d0, d1), (method, n)
-            d2, i2 = retrieval.search(ix, qu[:n], 10, method)
-            assert torch.equal(i1, i2) and torch.equal(d1, d2)
-        lean = retrieval.FlatIndex(db, method, planes=True, keep_fp32=False)
-        assert lean.db is None
-        d3, i3 = lean.search(qu[:9], 10)                             # (no fp32 rows left: the panels serve nine queries too)
-        d0, i0 = retrieval.search(db, qu[:9], 10, method)
-        assert float((d3 - d0).abs().max()) <= 3e-6
-        assert bool(((i3 == i0) | ((d3 - d0).abs() <= 3e-6)).all())
-    with pytest.raises(ValueError):
-        retrieval.search(retrieval.FlatIndex(db, "cosine", planes=False), qu, 5, "l2")
-    plain = retrieval.FlatIndex(db, "cosine", planes=False)
-    assert not plain.has_planes and torch.equal(plain.search(qu, 5)[1], retrieval.search(db, qu, 5)[1])
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, out_dir):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from anyloc_amd import retrieval
-        dev = torch.device("cuda", 0)
-        dim = 1024
-        db, qu = _rows(5001, dim, 5), _rows(256, dim, 6)
-        bounds = [0, 2100, 5001]
-        shard = retrieval.FlatIndex(db[bounds[rank]:bounds[rank + 1]].to(dev), "cosine", planes=True)
-        q_loc = qu[128 * rank:128 * (rank + 1)].to(dev)
-        d_ref, i_ref = retrieval.search(db.to(dev), qu.to(dev), 10)
-        for overlap in (True, False, "auto"):
-            d, i = retrieval.sharded_search(shard, bounds[rank], q_loc, 10, counts=[128, 128], overlap=overlap)
-            if rank == 0:
-                assert np.array_equal(i, i_ref.cpu().numpy()), overlap
-                np.testing.assert_allclose(d, d_ref.cpu().numpy(), atol=2e-6)
+    dev = torch.device("cuda", 0)
+    dim = 1024
+    db, qu = spread_rows(5001, dim, 5), spread_rows(256, dim, 6)
+    bounds = [0, 2100, 5001]
+    shard = retrieval.FlatIndex(db[bounds[rank]:bounds[rank + 1]].to(dev), "cosine", planes=True)
+    q_loc = qu[128 * rank:128 * (rank + 1)].to(dev)
+    d_ref, i_ref = retrieval.search(db.to(dev), qu.to(dev), 10)
+    for overlap in (True, False, "auto"):
+        d, i = retrieval.sharded_search(shard, bounds[rank], q_loc, 10, counts=[128, 128], overlap=overlap)
         if rank == 0:
-            open(os.path.join(out_dir, "ok"), "w").write("1")
-        torch.cuda.synchronize()
-    finally:
-        dist.destroy_process_group()
+            assert np.array_equal(i, i_ref.cpu().numpy()), overlap
+            np.testing.assert_allclose(d, d_ref.cpu().numpy(), atol=2e-6)
+    if rank == 0:
+        open(os.path.join(out_dir, "ok"), "w").write("1")
 
 
-def _worker_screened(rank, world, port, out_dir):
+def _screened_shards_job(rank, world, out_dir):
     """The same step at a shape the SCREENED search serves (forced: topk_screen = 1): every rank's shard search scores on the
     leading planes and re-scores its candidates; the merged lists are checked against a float64 search over the whole database."""
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from anyloc_amd import ops, retrieval
-        dev = torch.device("cuda", 0)
-        dim = 4096
-        db, qu = _rows(36000, dim, 7), _rows(600, dim, 8)
-        bounds = [0, 17000, 36000]
-        with ops.options(topk_screen=1, topk_h3=1):
-            shard = retrieval.FlatIndex(db[bounds[rank]:bounds[rank + 1]].to(dev), "cosine", planes=True)
-            q_loc = qu[300 * rank:300 * (rank + 1)].to(dev)
-            outs = [retrieval.sharded_search(shard, bounds[rank], q_loc, 20, counts=[300, 300], overlap=ov) for ov in (True, False)]
-            ops.profile_enable(True); ops.profile_reset()
-            retrieval.sharded_search(shard, bounds[rank], q_loc, 20, counts=[300, 300], overlap=True)
-            torch.cuda.synchronize()
-            prof = ops.profile_dump()
-            ops.profile_enable(False)
-        assert "topk_screen_gemm" in prof and "topk_scores_gemm" not in prof, sorted(prof)
-        if rank == 0:
-            s = torch.nn.functional.normalize(qu.to(dev).double()) @ torch.nn.functional.normalize(db.to(dev).double()).t()
-            o = torch.sort(s, dim=1, descending=True, stable=True)
-            for d, i in outs:
-                i_t = torch.as_tensor(i, device=dev)
-                got = torch.gather(s, 1, i_t)
-                assert float((torch.as_tensor(d, device=dev).double() - got).abs().max()) <= 3e-6
-                mism = i_t != o.indices[:, :20]
-                assert (not bool(mism.any())) or float((got[mism] - o.values[:, :20][mism]).abs().max()) <= 3e-6
-            assert np.array_equal(outs[0][1], outs[1][1])
-            open(os.path.join(out_dir, "ok_screened"), "w").write("1")
-        torch.cuda.synchronize()
-    finally:
-        dist.destroy_process_group()
+    from anyloc_amd import ops, retrieval
+    dev = torch.device("cuda", 0)
+    dim = 4096
+    db, qu = spread_rows(36000, dim, 7), spread_rows(600, dim, 8)
+    bounds = [0, 17000, 36000]
+    with ops.options(topk_screen=1, topk_h3=1):
+        shard = retrieval.FlatIndex(db[bounds[rank]:bounds[rank + 1]].to(dev), "cosine", planes=True)
+        q_loc = qu[300 * rank:300 * (rank + 1)].to(dev)
+        outs = [retrieval.sharded_search(shard, bounds[rank], q_loc, 20, counts=[300, 300], overlap=ov) for ov in (True, False)]
+        _, prof = profiled(lambda: retrieval.sharded_search(shard, bounds[rank], q_loc, 20, counts=[300, 300], overlap=True))
+    assert _screened_without_fallback(prof), sorted(prof)
+    if rank == 0:
+        s = exact_scores64(torch.nn.functional.normalize(qu.to(dev).double()), db.to(dev), "ip")
+        for d, i in outs:
+            check_lists(torch.as_tensor(d, device=dev), torch.as_tensor(i, device=dev), s, 20, "ip", "screened shards", cap=None)
+        assert np.array_equal(outs[0][1], outs[1][1])
+        open(os.path.join(out_dir, "ok_screened"), "w").write("1")
 
 
 def test_overlapped_sharded_step_with_the_screened_shard_search(tmp_path):
-    mp.spawn(_worker_screened, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    run_ranks(_screened_shards_job, 2, tmp_path)
     assert (tmp_path / "ok_screened").exists()
 
 
 def test_overlapped_sharded_step_on_a_prepared_shard_two_ranks_one_gpu(tmp_path):
     """The overlapped sharded step (own queries searched while the others' travel, the rest afterwards) on prepared shards with
     the real kernels: two ranks share cuda:0 over gloo; the merged lists are those of one flat search, with and without overlap."""
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    run_ranks(_prepared_shards_job, 2, tmp_path)
     assert (tmp_path / "ok").exists()
 
 

@@ -3,93 +3,25 @@
 ``anyloc_topk_index_build_range`` / ``FlatIndex.from_chunks``).  The candidates of the screened search are re-scored from the
 two fp16 planes of the index in float64: the lists are the float64-exact ones over the 22-bit rows the index holds, which lie
 within 1e-7 (normalised score; tests/test_screen_rowsfree_cpu.py) of the fp32 rows -- so they are checked against a float64
-flat search over the fp32 rows with the bars and the near-tie rule of tests/test_gpu_screen.py (3e-6 inner product, 1e-5 L2; a
+flat search over the fp32 rows with the bars and the near-tie rule of tests/_retrieval_refs.py (3e-6 inner product, 1e-5 L2; a
 differing index only where the two float64 scores are closer than the bar).
 
-A cap on what the near-tie rule may excuse: the excused entries of a case are counted and must not exceed
+A cap on what the near-tie rule may excuse (check_lists' cap="gaps"): the excused entries of a case are counted and must not exceed
 2 x (adjacent gaps below g in the exact float64 top-(k+1) lists), g = 3e-7 (inner product) / 1e-6 (L2), times the scale of
 the queries where they are not unit vectors.  Why: a rows-free score is within 1e-7 of the fp32-exact one, the compared value
 is rounded to fp32 once (6e-8 at 1; a few such roundings on values up to 4 for L2), and one swapped pair is two entries."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
+
+import _ranks
+import _retrieval_refs as R
+from _retrieval_refs import _rows_free
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-BAR = {"ip": 3e-6, "l2": 1e-5}                             # (the bars of tests/test_gpu_screen.py)
-GAP = {"ip": 3e-7, "l2": 1e-6}
-
-
-def _exact64(qu, db, metric, normalize=True):
-    """float64 score matrix of a flat search on the device (larger = better): over F.normalize(db), or the raw rows."""
-    q = qu.double()
-    d = torch.nn.functional.normalize(db.double()) if normalize else db.double()
-    s = q @ d.t()
-    if metric == "l2":
-        s = -((q * q).sum(1, keepdim=True) + (d * d).sum(1)[None, :] - 2.0 * s)
-    return s
-
-
-def _check(d, i, s, k, metric, tag, scale=1.0):
-    """Lists (d, i) against the float64 score matrix ``s``: padding, distances within the bar, a differing index only at a
-    float64 near-tie, and no more such entries than the near-ties of the float64 lists themselves allow.  -> excused entries."""
-    ndb = s.shape[1]
-    kk = min(k, ndb)
-    o = torch.sort(s, dim=1, descending=True, stable=True)
-    assert bool((i[:, kk:] == -1).all()), tag
-    got64 = torch.gather(s, 1, i[:, :kk])
-    val = -d[:, :kk].double() if metric == "l2" else d[:, :kk].double()
-    tol = BAR[metric] * scale
-    err = float((val - got64).abs().max())
-    mism = i[:, :kk] != o.indices[:, :kk]
-    excused = int(mism.sum())
-    top = o.values[:, :min(k + 1, ndb)]
-    gaps = top[:, :-1] - top[:, 1:]
-    cap = 2 * int((gaps < GAP[metric] * scale).sum())
-    print(f"{tag}: max |distance - float64| {err:.2e} (bar {tol:.1e}); {excused} entries at float64 near-ties, cap {cap}, of {i[:, :kk].numel()}")
-    assert err <= tol, (tag, err)
-    if excused:
-        off = (got64[mism] - o.values[:, :kk][mism]).abs()
-        assert float(off.max()) <= tol, (tag, float(off.max()))
-        if excused > cap:
-            print(f"{tag}: float64 score differences of the excused entries: {sorted(off.tolist())[-20:]}")
-        assert excused <= cap, (tag, excused, cap)
-    return excused
-
-
-def _data(nq, ndb, dim, seed, planted=True):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    db = torch.randn(ndb, dim, generator=g, device=DEV) * (0.3 + 2.0 * torch.rand(ndb, 1, generator=g, device=DEV))
-    qu = torch.nn.functional.normalize(torch.randn(nq, dim, generator=g, device=DEV))
-    if planted and ndb >= 64:
-        # every query has a handful of true neighbours at graded distances, some closer to each other than the screening bound
-        for j in range(6):
-            rows = torch.randint(0, ndb, (nq,), generator=g, device=DEV)
-            noise = torch.nn.functional.normalize(torch.randn(nq, dim, generator=g, device=DEV))
-            db[rows] = (qu + (0.02 + 0.0004 * j) * noise) * (0.5 + j)
-    return qu, db
-
-
-def _profiled(fn):
-    from anyloc_amd import ops
-    ops.profile_enable(True); ops.profile_reset()
-    out = fn()
-    torch.cuda.synchronize()
-    prof = ops.profile_dump()
-    ops.profile_enable(False)
-    return out, prof
-
-
-def _rows_free(prof):
-    """screened, re-scored from the planes, no fallback and no fp32 rows read"""
-    return ("topk_screen_gemm" in prof and "topk_screen_rescore_planes" in prof and "topk_scores_gemm" not in prof
-            and "topk_screen_rescore" not in prof)
-
 
 # the shapes of test_screened_search_gives_the_exact_lists (seed nq + ndb + dim) and of
 # test_screened_search_chunk_edges_and_query_norms (seed nq + dim, scaled queries) of tests/test_gpu_screen.py
@@ -107,24 +39,24 @@ def test_rows_free_screened_search_gives_the_exact_lists(nq, ndb, dim, k, metric
     ``index_base`` shifts the indices and nothing else.  Every shape class: several panels, a short last panel, two column
     ranges (140 000 rows), fewer rows than k, k = 128, queries that are not unit vectors, L2, 1 000 x 10 000 x 49 152."""
     from anyloc_amd import ops, retrieval
-    qu, db = _data(nq, ndb, dim, nq + dim if kind == "edge" else nq + ndb + dim)
+    qu, db = R.planted_rows(nq, ndb, dim, nq + dim if kind == "edge" else nq + ndb + dim)
     method = "cosine" if metric == "ip" else "l2"
     with ops.options(topk_screen=1, topk_h3=1):
         index = retrieval.FlatIndex(db, method, True, planes=True, keep_fp32=False, rescore="planes")
         assert index.db is None and index.has_planes and index.planes.numel() == ops.topk_index_bytes(ndb, dim)
         if qscale == 1.0:
             q = ops.l2norm_rows(qu)                        # the queries FlatIndex.search scores (F.normalize of the reference)
-            (d, i), prof = _profiled(lambda: index.search(qu, k))
+            (d, i), prof = R.profiled(lambda: index.search(qu, k))
         else:                                              # FlatIndex normalises its queries: scaled ones go through ops
             q = qu * qscale
-            (d, i), prof = _profiled(lambda: ops.topk_indexed(q, index.planes, ndb, k, metric, normalize_db=True, rescore_planes=True))
+            (d, i), prof = R.profiled(lambda: ops.topk_indexed(q, index.planes, ndb, k, metric, normalize_db=True, rescore_planes=True))
         assert _rows_free(prof), sorted(prof)
         d_again, i_again = ops.topk_indexed(q, index.planes, ndb, k, metric, normalize_db=True, rescore_planes=True)
         assert torch.equal(d, d_again) and torch.equal(i, i_again)                              # deterministic, and one path
         d_b, i_b = ops.topk_indexed(q, index.planes, ndb, k, metric, index_base=5000, normalize_db=True, rescore_planes=True)
         assert torch.equal(torch.where(i_b >= 0, i_b - 5000, i_b), i) and torch.equal(d_b, d)
     scale = (max(1.0, qscale * qscale) if metric == "l2" else qscale)                           # (as the existing file scales its bars)
-    _check(d, i, _exact64(q, db, metric), k, metric, f"rows-free {nq}x{ndb}x{dim} k={k} {metric} x{qscale}", scale)
+    R.check_lists(d, i, R.exact_scores64(q, db, metric), k, metric, f"rows-free {nq}x{ndb}x{dim} k={k} {metric} x{qscale}", scale=scale, cap="gaps")
 
 
 @pytest.mark.parametrize("metric", ["ip", "l2"])
@@ -134,33 +66,33 @@ def test_rows_free_screened_search_on_raw_rows(metric):
     reach 150 here, so for L2 the scaled gap is wide and the cap on excused entries says little on this shape; the normalised
     shapes above are where it bites.)"""
     from anyloc_amd import ops, retrieval
-    qu, db = _data(400, 20000, 4096, 21)
+    qu, db = R.planted_rows(400, 20000, 4096, 21)
     with ops.options(topk_screen=1, topk_h3=1):
         index = retrieval.FlatIndex(db, "cosine" if metric == "ip" else "l2", False, keep_fp32=False, rescore="planes")
         assert index.db is None
-        (d, i), prof = _profiled(lambda: index.search(qu, 20))
+        (d, i), prof = R.profiled(lambda: index.search(qu, 20))
     assert _rows_free(prof), sorted(prof)
     scale = float(db.double().norm(dim=1).max()) ** (2 if metric == "l2" else 1)
-    _check(d, i, _exact64(qu, db, metric, normalize=False), 20, metric, f"rows-free raw rows {metric}", scale)
+    R.check_lists(d, i, R.exact_scores64(qu, db, metric, normalize=False), 20, metric, f"rows-free raw rows {metric}", scale=scale, cap="gaps")
 
 
 @pytest.mark.parametrize("nq,ndb,dim,k,metric", [(600, 20000, 4096, 20, "ip"), (600, 20000, 4096, 20, "l2"), (1000, 10000, 49152, 20, "ip")])
 def test_rows_free_against_the_rows_kept_screened_search(nq, ndb, dim, k, metric):
     """The two re-scorings on ONE index: distances within the bar, indices equal except at float64 near-ties (capped)."""
     from anyloc_amd import ops
-    qu, db = _data(nq, ndb, dim, nq + ndb + dim)
+    qu, db = R.planted_rows(nq, ndb, dim, nq + ndb + dim)
     planes = ops.topk_index_build(db)
     with ops.options(topk_screen=1, topk_h3=1):
-        (d_r, i_r), prof_r = _profiled(lambda: ops.topk_indexed(qu, planes, ndb, k, metric, normalize_db=True, db=db))
-        (d_p, i_p), prof_p = _profiled(lambda: ops.topk_indexed(qu, planes, ndb, k, metric, normalize_db=True, rescore_planes=True))
+        (d_r, i_r), prof_r = R.profiled(lambda: ops.topk_indexed(qu, planes, ndb, k, metric, normalize_db=True, db=db))
+        (d_p, i_p), prof_p = R.profiled(lambda: ops.topk_indexed(qu, planes, ndb, k, metric, normalize_db=True, rescore_planes=True))
     assert "topk_screen_rescore" in prof_r and "topk_screen_rescore_planes" not in prof_r and "topk_scores_gemm" not in prof_r
     assert _rows_free(prof_p), sorted(prof_p)
     diff = float((d_r - d_p).abs().max())
     print(f"rows-free vs rows-kept {nq}x{ndb}x{dim} {metric}: max |distance difference| {diff:.3e}, {int((i_r != i_p).sum())} indices differ")
-    assert diff <= BAR[metric]
-    s = _exact64(qu, db, metric)
-    n_r = _check(d_r, i_r, s, k, metric, "rows-kept")
-    n_p = _check(d_p, i_p, s, k, metric, "rows-free")
+    assert diff <= R.BAR[metric]
+    s = R.exact_scores64(qu, db, metric)
+    n_r = R.check_lists(d_r, i_r, s, k, metric, "rows-kept", cap="gaps")
+    n_p = R.check_lists(d_p, i_p, s, k, metric, "rows-free", cap="gaps")
     assert int((i_r != i_p).sum()) <= n_r + n_p                    # a differing pair differs from the float64 list on one side at least
 
 
@@ -169,7 +101,7 @@ def test_the_flag_with_the_rows_at_hand_reads_the_planes():
     kernel and the bits of the rows-free call."""
     from anyloc_amd import _lib, ops
     nq, ndb, dim, k = 520, 17000, 4096, 20
-    qu, db = _data(nq, ndb, dim, 9)
+    qu, db = R.planted_rows(nq, ndb, dim, 9)
     planes = ops.topk_index_build(db)
     lib = _lib.load()
     with ops.options(topk_screen=1, topk_h3=1):
@@ -186,7 +118,7 @@ def test_the_flag_with_the_rows_at_hand_reads_the_planes():
                 if rows is None:
                     return lib.anyloc_topk_search_index(_lib.ptr(qu), nq, _lib.ptr(planes), *common)
                 return lib.anyloc_topk_search_index_rows(_lib.ptr(qu), nq, _lib.ptr(rows), _lib.ptr(planes), *common)
-            st, prof = _profiled(call)
+            st, prof = R.profiled(call)
             assert st == 0, lib.anyloc_last_error()
             assert _rows_free(prof), (name, sorted(prof))
             out[name] = (d, i)
@@ -201,21 +133,21 @@ def test_rows_free_ties_and_overflow():
     """Exact duplicates of a query's best rows: lower index first; 40 copies fit the candidate list.  700 copies do not: the
     call falls back to the unscreened indexed search and gives the bits of ``FlatIndex(keep_fp32=False)`` without the flag."""
     from anyloc_amd import ops, retrieval
-    qu, db = _data(300, 12000, 2048, 5, planted=False)
+    qu, db = R.planted_rows(300, 12000, 2048, 5, planted=False)
     db[100] = 3.0 * qu[0]
     copies = torch.arange(200, 240, device=DEV)
     db[copies] = db[100].clone().expand(len(copies), -1)
     q = ops.l2norm_rows(qu)
     with ops.options(topk_screen=1, topk_h3=1):
         index = retrieval.FlatIndex(db, "cosine", True, keep_fp32=False, rescore="planes")
-        (d, i), prof = _profiled(lambda: index.search(qu, 20))
+        (d, i), prof = R.profiled(lambda: index.search(qu, 20))
     assert _rows_free(prof), sorted(prof)
     assert i[0, 0] == 100 and torch.equal(i[0, 1:20], copies[:19])
-    _check(d, i, _exact64(q, db, "ip"), 20, "ip", "rows-free duplicates")
+    R.check_lists(d, i, R.exact_scores64(q, db, "ip"), 20, "ip", "rows-free duplicates", cap="gaps")
     db[3000:3700] = db[100].clone().expand(700, -1)
     with ops.options(topk_screen=1, topk_h3=1):
         index = retrieval.FlatIndex(db, "cosine", True, keep_fp32=False, rescore="planes")
-        (d, i), prof = _profiled(lambda: index.search(qu, 20))
+        (d, i), prof = R.profiled(lambda: index.search(qu, 20))
         assert "topk_screen_gemm" in prof and "topk_scores_gemm" in prof, sorted(prof)            # screened first, then the fallback
         bare = retrieval.FlatIndex(db, "cosine", True, planes=True, keep_fp32=False)
         d0, i0 = bare.search(qu, 20)
@@ -237,7 +169,7 @@ def _build_zeroed(db):
                                             (9001, 1024, [(0, 9001)])])
 def test_index_built_by_ranges_is_the_index_built_at_once(ndb, dim, pieces):
     from anyloc_amd import ops
-    qu, db = _data(300, ndb, dim, ndb + dim)
+    qu, db = R.planted_rows(300, ndb, dim, ndb + dim)
     assert ops.topk_index_panel(dim) == 8192
     whole = _build_zeroed(db)
     parts = torch.zeros_like(whole)
@@ -247,7 +179,7 @@ def test_index_built_by_ranges_is_the_index_built_at_once(ndb, dim, pieces):
     assert torch.equal(whole, parts)
     for screen, flag in ((0, False), (1, True)):
         with ops.options(topk_screen=screen, topk_h3=1):
-            (d0, i0), prof = _profiled(lambda: ops.topk_indexed(qu, whole, ndb, 20, "ip", normalize_db=True, rescore_planes=flag))
+            (d0, i0), prof = R.profiled(lambda: ops.topk_indexed(qu, whole, ndb, 20, "ip", normalize_db=True, rescore_planes=flag))
             d1, i1 = ops.topk_indexed(qu, parts, ndb, 20, "ip", normalize_db=True, rescore_planes=flag)
         assert _rows_free(prof) if screen else ("topk_scores_gemm" in prof and "topk_screen_gemm" not in prof), sorted(prof)
         assert torch.equal(d0, d1) and torch.equal(i0, i1), screen
@@ -260,7 +192,7 @@ def test_index_built_by_ranges_is_the_index_built_at_once(ndb, dim, pieces):
 def test_flat_index_from_chunks(ndb, dim, where):
     """Ragged chunks, on the host or the device: the rows-free index of the whole database, bit for bit."""
     from anyloc_amd import ops, retrieval
-    qu, db = _data(300, ndb, dim, ndb + dim + 1)
+    qu, db = R.planted_rows(300, ndb, dim, ndb + dim + 1)
     lens = [1, 5000, 3191, 8192, 17, ndb]                               # cut points: inside panels, on a boundary, across two
     chunks, r0 = [], 0
     for n, ln in enumerate(lens):
@@ -276,11 +208,11 @@ def test_flat_index_from_chunks(ndb, dim, where):
     ref = retrieval.FlatIndex(db, "cosine", True, keep_fp32=False, rescore="planes")
     for screen in (1, 0):
         with ops.options(topk_screen=screen, topk_h3=1):
-            (d, i), prof = _profiled(lambda: index.search(qu, 20))
+            (d, i), prof = R.profiled(lambda: index.search(qu, 20))
             d0, i0 = ref.search(qu, 20)
         assert ("topk_screen_rescore_planes" in prof) == bool(screen)
         assert torch.equal(d, d0) and torch.equal(i, i0), screen
-    _check(d, i, _exact64(ops.l2norm_rows(qu), db, "ip"), 20, "ip", "from_chunks, unscreened")
+    R.check_lists(d, i, R.exact_scores64(ops.l2norm_rows(qu), db, "ip"), 20, "ip", "from_chunks, unscreened", cap="gaps")
     with pytest.raises(ValueError):
         retrieval.FlatIndex.from_chunks(iter(chunks[:-1]), ndb, dim)    # rows missing
     with pytest.raises(ValueError):
@@ -292,11 +224,11 @@ def test_flat_index_from_chunks(ndb, dim, where):
 def test_default_index_without_rows_still_searches_unscreened():
     """``rescore`` defaults to "rows": today's object -- without its rows it scores on the three-product panels."""
     from anyloc_amd import ops, retrieval
-    qu, db = _data(520, 17000, 4096, 9)
+    qu, db = R.planted_rows(520, 17000, 4096, 9)
     with ops.options(topk_screen=1):
         bare = retrieval.FlatIndex(db, "cosine", True, planes=True, keep_fp32=False)
         assert bare.rescore == "rows" and bare.db is None
-        (d, i), prof = _profiled(lambda: bare.search(qu, 20))
+        (d, i), prof = R.profiled(lambda: bare.search(qu, 20))
     assert "topk_scores_gemm" in prof and "topk_screen_gemm" not in prof and "topk_screen_rescore_planes" not in prof, sorted(prof)
     with ops.options(topk_screen=0):
         d0, i0 = retrieval.search(db, qu, 20)
@@ -304,49 +236,29 @@ def test_default_index_without_rows_still_searches_unscreened():
 
 
 # ------------------------------------------------------------------------------------------------------------- sharded
-def _cpu_rows(n, dim, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(n, dim, generator=g) * (0.25 + 4.0 * torch.rand(n, 1, generator=g))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker_rows_free(rank, world, port, out_dir):
-    """tests/test_gpu_round6.py::_worker_screened with shards that keep no rows."""
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from anyloc_amd import ops, retrieval
-        dev = torch.device("cuda", 0)
-        dim = 4096
-        db, qu = _cpu_rows(36000, dim, 7), _cpu_rows(600, dim, 8)
-        bounds = [0, 17000, 36000]
-        with ops.options(topk_screen=1, topk_h3=1):
-            shard = retrieval.FlatIndex(db[bounds[rank]:bounds[rank + 1]].to(dev), "cosine", keep_fp32=False, rescore="planes")
-            assert shard.db is None
-            q_loc = qu[300 * rank:300 * (rank + 1)].to(dev)
-            outs = [retrieval.sharded_search(shard, bounds[rank], q_loc, 20, counts=[300, 300], overlap=ov) for ov in (True, False)]
-            _, prof = _profiled(lambda: retrieval.sharded_search(shard, bounds[rank], q_loc, 20, counts=[300, 300], overlap=True))
-        assert _rows_free(prof), sorted(prof)
-        if rank == 0:
-            s = _exact64(ops.l2norm_rows(qu.to(dev)), db.to(dev), "ip")
-            for (d, i), tag in zip(outs, ("overlapped", "plain")):
-                _check(torch.as_tensor(d, device=dev), torch.as_tensor(i, device=dev), s, 20, "ip", f"rows-free shards, {tag}")
-            assert np.array_equal(outs[0][1], outs[1][1]) and np.array_equal(outs[0][0], outs[1][0])
-            open(os.path.join(out_dir, "ok_rows_free"), "w").write("1")
-        torch.cuda.synchronize()
-    finally:
-        dist.destroy_process_group()
+def _rows_free_job(rank, world, out_dir):
+    """The screened shard job of the overlapped sharded step (test_overlapped_sharded_step_with_the_screened_shard_search), with
+    shards that keep no rows."""
+    from anyloc_amd import ops, retrieval
+    dev = torch.device("cuda", 0)
+    dim = 4096
+    db, qu = R.spread_rows(36000, dim, 7), R.spread_rows(600, dim, 8)
+    bounds = [0, 17000, 36000]
+    with ops.options(topk_screen=1, topk_h3=1):
+        shard = retrieval.FlatIndex(db[bounds[rank]:bounds[rank + 1]].to(dev), "cosine", keep_fp32=False, rescore="planes")
+        assert shard.db is None
+        q_loc = qu[300 * rank:300 * (rank + 1)].to(dev)
+        outs = [retrieval.sharded_search(shard, bounds[rank], q_loc, 20, counts=[300, 300], overlap=ov) for ov in (True, False)]
+        _, prof = R.profiled(lambda: retrieval.sharded_search(shard, bounds[rank], q_loc, 20, counts=[300, 300], overlap=True))
+    assert _rows_free(prof), sorted(prof)
+    if rank == 0:
+        s = R.exact_scores64(ops.l2norm_rows(qu.to(dev)), db.to(dev), "ip")
+        for (d, i), tag in zip(outs, ("overlapped", "plain")):
+            R.check_lists(torch.as_tensor(d, device=dev), torch.as_tensor(i, device=dev), s, 20, "ip", f"rows-free shards, {tag}", cap="gaps")
+        assert np.array_equal(outs[0][1], outs[1][1]) and np.array_equal(outs[0][0], outs[1][0])
+        open(os.path.join(out_dir, "ok_rows_free"), "w").write("1")
 
 
 def test_sharded_step_on_rows_free_shards_two_ranks_one_gpu(tmp_path):
-    mp.spawn(_worker_rows_free, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    _ranks.run_ranks(_rows_free_job, 2, tmp_path)
     assert (tmp_path / "ok_rows_free").exists()

@@ -3,8 +3,8 @@ screened search without its read-back.  What the host decides from the overflow 
 (csrc/topk.hip, device_fallback): up to 64 overflowed queries are searched unscreened as a batch of their own and only THEIR
 lists are replaced; more than 64 run the unscreened search for every query, as the waiting call does.
 
-Data recipe and list check are those of tests/test_gpu_screen_rowsfree.py, restated: bars 3e-6 (inner product) / 1e-5 (L2)
-against a float64 flat search, a differing index only at a float64 near-tie, and at most 2 x the near-ties of the float64 lists
+Data recipe and list check are those of tests/_retrieval_refs.py: bars 3e-6 (inner product) / 1e-5 (L2) against a float64 flat
+search, a differing index only at a float64 near-tie, and (cap="gaps") at most 2 x the near-ties of the float64 lists
 themselves.  The overflow recipes are those of tests/test_gpu_screen.py: a zero query (every row ties inside its bound) and 700
 copies of one query's best row (more than the 512 candidates a query may have per column range).
 
@@ -18,78 +18,12 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _retrieval_refs as R
+from _retrieval_refs import _screened_then_fallback, _screened_without_fallback
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-BAR = {"ip": 3e-6, "l2": 1e-5}
-GAP = {"ip": 3e-7, "l2": 1e-6}
 SCREEN = dict(topk_screen=1, topk_h3=1)
-
-
-def _exact64(qu, db, metric, normalize=True):
-    """float64 score matrix of a flat search on the device (larger = better): over F.normalize(db), or the raw rows."""
-    q = qu.double()
-    d = torch.nn.functional.normalize(db.double()) if normalize else db.double()
-    s = q @ d.t()
-    if metric == "l2":
-        s = -((q * q).sum(1, keepdim=True) + (d * d).sum(1)[None, :] - 2.0 * s)
-    return s
-
-
-def _check(d, i, s, k, metric, tag, scale=1.0):
-    """Lists (d, i) against the float64 score matrix ``s``: padding, distances within the bar, a differing index only at a
-    float64 near-tie, and no more such entries than the near-ties of the float64 lists themselves allow."""
-    ndb = s.shape[1]
-    kk = min(k, ndb)
-    o = torch.sort(s, dim=1, descending=True, stable=True)
-    assert bool((i[:, kk:] == -1).all()), tag
-    assert bool(((i[:, :kk] >= 0) & (i[:, :kk] < ndb)).all()), tag
-    got64 = torch.gather(s, 1, i[:, :kk])
-    val = -d[:, :kk].double() if metric == "l2" else d[:, :kk].double()
-    tol = BAR[metric] * scale
-    err = float((val - got64).abs().max())
-    mism = i[:, :kk] != o.indices[:, :kk]
-    excused = int(mism.sum())
-    top = o.values[:, :min(k + 1, ndb)]
-    gaps = top[:, :-1] - top[:, 1:]
-    cap = 2 * int((gaps < GAP[metric] * scale).sum())
-    print(f"{tag}: max |distance - float64| {err:.2e} (bar {tol:.1e}); {excused} entries at float64 near-ties, cap {cap}, of {i[:, :kk].numel()}")
-    assert err <= tol, (tag, err)
-    if excused:
-        off = (got64[mism] - o.values[:, :kk][mism]).abs()
-        assert float(off.max()) <= tol, (tag, float(off.max()))
-        assert excused <= cap, (tag, excused, cap)
-    return excused
-
-
-def _data(nq, ndb, dim, seed, planted=True):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    db = torch.randn(ndb, dim, generator=g, device=DEV) * (0.3 + 2.0 * torch.rand(ndb, 1, generator=g, device=DEV))
-    qu = torch.nn.functional.normalize(torch.randn(nq, dim, generator=g, device=DEV))
-    if planted and ndb >= 64:
-        for j in range(6):
-            rows = torch.randint(0, ndb, (nq,), generator=g, device=DEV)
-            noise = torch.nn.functional.normalize(torch.randn(nq, dim, generator=g, device=DEV))
-            db[rows] = (qu + (0.02 + 0.0004 * j) * noise) * (0.5 + j)
-    return qu, db
-
-
-def _profiled(fn):
-    from anyloc_amd import ops
-    ops.profile_enable(True); ops.profile_reset()
-    out = fn()
-    torch.cuda.synchronize()
-    prof = ops.profile_dump()
-    ops.profile_enable(False)
-    return out, prof
-
-
-def _screened_without_fallback(prof):
-    return "topk_screen_gemm" in prof and "topk_scores_gemm" not in prof
-
-
-def _screened_then_fallback(prof):
-    return "topk_screen_gemm" in prof and "topk_scores_gemm" in prof
 
 
 def _same(a, b):
@@ -107,15 +41,15 @@ def test_without_overflow_the_flag_changes_no_bit(nq, ndb, dim, k, metric):
     "No overflow" is then not the case under test; the flagged call gives those queries a side batch, and its lists are held to
     the float64 search over the raw rows with the scaled bars of tests/test_gpu_screen.py::test_screened_search_on_raw_rows."""
     from anyloc_amd import ops, retrieval
-    qu, db = _data(nq, ndb, dim, nq + ndb + dim)
+    qu, db = R.planted_rows(nq, ndb, dim, nq + ndb + dim)
     method = "cosine" if metric == "ip" else "l2"
     with ops.options(**SCREEN):
         for normalize in (True, False):
-            want, prof = _profiled(lambda: ops.topk(qu, db, k, metric, normalize_db=normalize))
+            want, prof = R.profiled(lambda: ops.topk(qu, db, k, metric, normalize_db=normalize))
             got = ops.topk(qu, db, k, metric, normalize_db=normalize, no_wait=True)
             if not normalize and _screened_then_fallback(prof):
                 scale = float(db.double().norm(dim=1).max()) ** (2 if metric == "l2" else 1)
-                _check(got[0], got[1], _exact64(qu, db, metric, normalize=False), k, metric, f"raw rows, overflow, {nq}x{ndb}x{dim} {metric}", scale)
+                R.check_lists(got[0], got[1], R.exact_scores64(qu, db, metric, normalize=False), k, metric, f"raw rows, overflow, {nq}x{ndb}x{dim} {metric}", scale=scale, cap="gaps")
                 print(f"raw rows {nq}x{ndb}x{dim} {metric}: the waiting call fell back; {int((got[1] != want[1]).any(1).sum())} lists differ from it")
                 continue
             assert _screened_without_fallback(prof), (normalize, sorted(prof))
@@ -124,7 +58,7 @@ def test_without_overflow_the_flag_changes_no_bit(nq, ndb, dim, k, metric):
         assert _same(ops.topk(qu, db, k, metric, index_base=5000, normalize_db=True, no_wait=True), want), "index_base"
         for name, index in (("rows kept", retrieval.FlatIndex(db, method, True, planes=True)),
                             ("rows free", retrieval.FlatIndex(db, method, True, keep_fp32=False, rescore="planes"))):
-            want, prof = _profiled(lambda: index.search(qu, k))
+            want, prof = R.profiled(lambda: index.search(qu, k))
             assert _screened_without_fallback(prof), (name, sorted(prof))
             assert _same(index.search(qu, k, no_wait=True), want), name
             assert _same(retrieval.search(index, qu, k, method, True, no_wait=True), want), name
@@ -150,15 +84,15 @@ def _few_overflowed(qu, db, how, k, metric, zero, dup_q, first, tag):
         planes = None if how == "one-shot" else ops.topk_index_build(db)
         d, i = _search(how, qu, db, planes, k, metric, no_wait=True)
         # the waiting call on the same input falls back for everyone: screened first, then the unscreened bits
-        (d_w, i_w), prof = _profiled(lambda: _search(how, qu, db, planes, k, metric))
+        (d_w, i_w), prof = R.profiled(lambda: _search(how, qu, db, planes, k, metric))
         assert _screened_then_fallback(prof), (tag, sorted(prof))
         # ... so the lists nobody should have touched come from a waiting call WITHOUT the overflowing queries
         calm = qu.clone()
         other = next(q for q in range(nq) if q not in over)
         calm[over] = qu[other]
-        (d_c, i_c), prof = _profiled(lambda: _search(how, calm, db, planes, k, metric))
+        (d_c, i_c), prof = R.profiled(lambda: _search(how, calm, db, planes, k, metric))
         assert _screened_without_fallback(prof), (tag, sorted(prof))
-    _check(d, i, _exact64(qu, db, metric), k, metric, tag)
+    R.check_lists(d, i, R.exact_scores64(qu, db, metric), k, metric, tag, cap="gaps")
     keep = torch.ones(nq, dtype=torch.bool, device=DEV)
     keep[over] = False
     assert torch.equal(d[keep], d_c[keep]) and torch.equal(i[keep], i_c[keep]), (tag, "a list outside the side batch moved")
@@ -176,7 +110,7 @@ def _few_overflowed(qu, db, how, k, metric, zero, dup_q, first, tag):
 @pytest.mark.parametrize("metric", ["ip", "l2"])
 @pytest.mark.parametrize("how", ["one-shot", "rows free"])
 def test_a_few_overflowed_queries_go_through_the_side_batch(how, metric):
-    qu, db = _data(300, 17000, 4096, 77)
+    qu, db = R.planted_rows(300, 17000, 4096, 77)
     qu[3] = 0.0
     db[100] = 3.0 * qu[0]
     db[3000:3700] = db[100].clone().expand(700, -1)
@@ -187,7 +121,7 @@ def test_a_few_overflowed_queries_go_through_the_side_batch(how, metric):
 def test_the_overflow_mark_of_a_query_is_sticky_across_column_ranges(where):
     """140 000 rows are two column ranges (131 072 + 8928); the candidate count of a query is per range and overwritten by the
     next one, the mark is not.  The issue asks for the second range; the first is where forgetting would show."""
-    qu, db = _data(300, 140000, 512, 300 + 140000 + 512)
+    qu, db = R.planted_rows(300, 140000, 512, 300 + 140000 + 512)
     at = 2000 if where == "first range only" else 131100
     db[at] = 3.0 * qu[0]
     db[at + 900:at + 1600] = db[at].clone().expand(700, -1)
@@ -196,7 +130,7 @@ def test_the_overflow_mark_of_a_query_is_sticky_across_column_ranges(where):
 
 def test_the_side_batch_is_reproducible():
     from anyloc_amd import ops
-    qu, db = _data(300, 17000, 4096, 77)
+    qu, db = R.planted_rows(300, 17000, 4096, 77)
     qu[3] = 0.0
     db[100] = 3.0 * qu[0]
     db[3000:3700] = db[100].clone().expand(700, -1)
@@ -212,14 +146,14 @@ def test_the_boundary_between_side_batch_and_full_fallback(n_zero):
     """64 overflowed queries still fit the side batch; 65 (and 200) run the unscreened search for every query, which is what the
     waiting call does for them: the same bits."""
     from anyloc_amd import ops
-    qu, db = _data(300, 17000, 4096, 77)
+    qu, db = R.planted_rows(300, 17000, 4096, 77)
     zero = torch.arange(300, device=DEV)[torch.randperm(300, generator=torch.Generator(device=DEV).manual_seed(n_zero), device=DEV)[:n_zero]]
     qu[zero] = 0.0
     with ops.options(**SCREEN):
         d, i = ops.topk(qu, db, 20, "ip", normalize_db=True, no_wait=True)
-        (d_w, i_w), prof = _profiled(lambda: ops.topk(qu, db, 20, "ip", normalize_db=True))
+        (d_w, i_w), prof = R.profiled(lambda: ops.topk(qu, db, 20, "ip", normalize_db=True))
     assert _screened_then_fallback(prof), sorted(prof)
-    _check(d, i, _exact64(qu, db, "ip"), 20, "ip", f"{n_zero} zero queries")
+    R.check_lists(d, i, R.exact_scores64(qu, db, "ip"), 20, "ip", f"{n_zero} zero queries", cap="gaps")
     assert torch.equal(i[zero], torch.arange(20, device=DEV).expand(n_zero, -1))
     if n_zero > 64:
         assert torch.equal(d, d_w) and torch.equal(i, i_w)
@@ -299,7 +233,7 @@ def test_a_flagged_call_writes_only_its_lists_and_its_workspace(overflow):
     from anyloc_amd import _lib, ops
     lib = _lib.load()
     nq, ndb, dim, k = 300, 17000, 4096, 20
-    qu, db = _data(nq, ndb, dim, 77)
+    qu, db = R.planted_rows(nq, ndb, dim, 77)
     if overflow:
         qu[3] = 0.0
         db[100] = 3.0 * qu[0]

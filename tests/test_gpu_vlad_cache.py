@@ -10,17 +10,13 @@ import numpy as np
 import pytest
 import torch
 
+from _vlad_refs import l2rel
 from anyloc_amd import synth
 from oracle import vlad_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 VLAD_RTOL = 1e-5
-
-
-def l2rel(a, b):
-    a, b = torch.as_tensor(a).double().cpu(), torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
 def _fitted(K, D, mode="hard", cache_dir=None, seed=0, **kw):

@@ -18,6 +18,7 @@ import pytest
 import torch
 from torch.nn import functional as F
 
+from _vlad_refs import hard_vlad_f64, l2rel
 from anyloc_amd import synth
 from oracle import vlad_ref
 
@@ -40,11 +41,6 @@ SOFT_CASES = [
 SOFT_IDS = [f"K{K}_D{D}_N{'_'.join(map(str, ns))}" for K, D, ns in SOFT_CASES]
 LABEL_CASES = [(129, 100, 300), (256, 100, 700), (128, 260, 257), (200, 64, 1), (5, 64, 77)]      # K, D, N
 WEIGHT_CASES = [(33, 68, 97), (43, 200, 129), (64, 132, 60)]
-
-
-def l2rel(a, b):
-    a, b = torch.as_tensor(a).double().cpu(), torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
 # ---------------------------------------------------------------------------------------------------------------- inputs
@@ -82,18 +78,6 @@ def _soft_f64(x, centers, w, norm_descs=True, intra_norm=True):
     x, c, w = x.double(), centers.double(), w.double()
     xh = x / x.norm(dim=1, keepdim=True).clamp_min(1e-12) if norm_descs else x
     out = K * (w.t() @ xh) - w.sum(dim=0)[:, None] * c.sum(dim=0)[None, :]
-    if intra_norm:
-        out = F.normalize(out, dim=1)
-    return F.normalize(out.reshape(-1), dim=0)
-
-
-def _hard_f64(x, centers, labels, norm_descs=True, intra_norm=True):
-    """The reference expression (utilities.py:959-962, :854-861, :889) in float64 under a given assignment."""
-    K, D = centers.shape
-    x = x.double()
-    xh = x / x.norm(dim=1, keepdim=True).clamp_min(1e-12) if norm_descs else x
-    out = torch.zeros(K, D, dtype=torch.float64)
-    out.index_add_(0, labels, xh - centers.double()[labels])
     if intra_norm:
         out = F.normalize(out, dim=1)
     return F.normalize(out.reshape(-1), dim=0)
@@ -207,7 +191,7 @@ def test_vlad_assigned_labels_vs_oracle(K, D, N):
         out = ops.vlad_assigned(x.to(DEV), centers.to(DEV), labels=labels.to(DEV), norm_descs=nd, intra_norm=intra)
         assert tuple(out.shape) == (K * D,)
         v32 = vlad_ref.vlad_hard(x, centers, nd, intra, labels=labels)[0]
-        v64 = _hard_f64(x, centers, labels, nd, intra)
+        v64 = hard_vlad_f64(x, centers, labels, nd, intra)
         ratio, rel = _judge(out, v32, v64, f"labels K{K} D{D} N{N} norm_descs {nd} intra {intra}")
         worst_ratio, worst_rel = max(worst_ratio, ratio), max(worst_rel, rel)
         assert not unused or float(out.reshape(K, D)[unused].abs().max()) == 0.0

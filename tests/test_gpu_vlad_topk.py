@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from _vlad_refs import hard_vlad_f64, l2rel
 from anyloc_amd import synth
 from oracle import faiss_flat, vlad_ref
 
@@ -13,11 +14,6 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 VLAD_RTOL = 1e-5      # north_star: VLAD descriptors within 1e-5 relative (L2-relative, fp32)
 KMEANS_SUMS_RTOL = 1e-6      # the sums of one k-means step against the float64 sums under the same labels (L2-relative)
-
-
-def l2rel(a, b):
-    a, b = torch.as_tensor(a).double().cpu(), torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
 def check_labels(lab, lab_ref, x, centers, gap_tol=1e-6):
@@ -412,16 +408,6 @@ def test_get_top_k_recall_surface():
         utilities.get_top_k_recall([1], db, qu, gt, method="manhattan")
 
 
-def _vlad_f64(x, centers, labels):
-    """The reference expression (utilities.py:959-962, :854-861, :889) evaluated in float64 under a given assignment."""
-    K, D = centers.shape
-    xh = torch.nn.functional.normalize(x.double())
-    out = torch.zeros(K, D, dtype=torch.float64)
-    out.index_add_(0, labels, xh - centers.double()[labels])
-    out = torch.nn.functional.normalize(out, dim=1)
-    return torch.nn.functional.normalize(out.reshape(-1), dim=0)
-
-
 @pytest.mark.parametrize("D,case", [(1536, "random"), (1536, "one_cluster"), (1536, "outlier"), (1024, "random"),
                                     (768, "one_cluster"), (384, "random")])
 def test_vlad_tight_clusters(D, case):
@@ -448,7 +434,7 @@ def test_vlad_tight_clusters(D, case):
         worst = 0.0
         for i in (0, n_img // 2, n_img - 1):
             v32 = vlad_ref.vlad_hard(x[i], c)[0]
-            v64 = _vlad_f64(x[i], c, lab[i])
+            v64 = hard_vlad_f64(x[i], c, lab[i])
             e_or = float((v32.double() - v64).norm())
             e_k = float((out[i].cpu().double() - v64).norm())
             assert e_k <= 3.0 * e_or + 1e-6, (case, D, n_img, i, e_k, e_or)
@@ -480,4 +466,3 @@ def test_vlad_reproducible_under_load(D, N):
         again = ops.vlad(toks, c)
         bad = (again != first).any(dim=1)
         assert not bool(bad.any()), (rep, int(bad.sum()), "image results differ from the first run")
-

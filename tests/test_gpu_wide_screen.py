@@ -1,10 +1,10 @@
 """Screened retrieval on rows wider than 49 152 columns (``pytest -m gpu``; ``screen_rescore_sliced_kernel`` and
 ``screen_rescore_planes_sliced_kernel`` of csrc/scores_screen.hip, option ``topk_rescore_cols``): the re-scoring kernels take
 the query in column slices and add the slices' float64 totals in LDS, so the screened search serves every width the fp16 panels
-serve.  Data recipe and float64 checker are those of tests/test_gpu_screen.py, restated here: planted neighbours at graded
-distances, a float64 flat search (computed in row blocks), distances within 3e-6 (inner product) / 1e-5 (L2) of it, a differing
-index only where the two float64 scores are closer than that bar -- and at most 0.1 % of a case's list entries may differ at
-all (a float64 search against itself gives 0; under fp32 rounding far less than one entry per case is expected).  Every case
+serve.  Data recipe and float64 checker are those of tests/_retrieval_refs.py: planted neighbours at graded distances, a
+float64 flat search (computed in blocks of 512 rows), distances within 3e-6 (inner product) / 1e-5 (L2) of it, a differing
+index only where the two float64 scores are closer than that bar -- and (cap=0.001) at most 0.1 % of a case's list entries may
+differ at all (a float64 search against itself gives 0; under fp32 rounding far less than one entry per case is expected).  Every case
 asserts from the profile that the leading-plane GEMM ran and the exact one did not: no silent fallback.
 
 The multi-slice path is reached at small shapes with ``topk_rescore_cols = 4096`` (8 208 columns: two slices and a 16-column
@@ -15,55 +15,12 @@ by tests/test_topk_wide_screen_cpu.py and it was run once by tools/time_wide_scr
 import pytest
 import torch
 
+import _retrieval_refs as R
+from _retrieval_refs import BAR
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-BAR = {"ip": 3e-6, "l2": 1e-5}                             # (the bars of tests/test_gpu_screen.py)
 SCREEN = dict(topk_screen=1, topk_h3=1)
-
-
-def _exact64(qu, db, metric):
-    """float64 score matrix of a flat search over F.normalize(db) on the device (larger = better), in blocks of 512 rows."""
-    q = qu.double()
-    out = torch.empty(qu.shape[0], db.shape[0], dtype=torch.float64, device=qu.device)
-    for r0 in range(0, db.shape[0], 512):
-        d = torch.nn.functional.normalize(db[r0:r0 + 512].double())
-        s = q @ d.t()
-        if metric == "l2":
-            s = -((q * q).sum(1, keepdim=True) + (d * d).sum(1)[None, :] - 2.0 * s)
-        out[:, r0:r0 + 512] = s
-    return out
-
-
-def _check(d, i, s, k, metric, tag):
-    """Lists (d, i) against the float64 score matrix ``s`` (ties -> lower index): padding, distances within the bar, a differing
-    index only at a float64 near-tie, and at most 0.1 % of the entries.  -> differing entries."""
-    kk = min(k, s.shape[1])
-    o = torch.sort(s, dim=1, descending=True, stable=True)
-    assert bool((i[:, kk:] == -1).all()), tag
-    got64 = torch.gather(s, 1, i[:, :kk])
-    val = -d[:, :kk].double() if metric == "l2" else d[:, :kk].double()
-    err = float((val - got64).abs().max())
-    mism = i[:, :kk] != o.indices[:, :kk]
-    differing = int(mism.sum())
-    print(f"{tag}: max |distance - float64| {err:.2e} (bar {BAR[metric]:.0e}); {differing} of {mism.numel()} entries differ")
-    assert err <= BAR[metric], (tag, err)
-    if differing:                                         # only float64 near-ties may swap
-        assert float((got64[mism] - o.values[:, :kk][mism]).abs().max()) <= BAR[metric], tag
-    assert differing <= 0.001 * mism.numel(), (tag, differing, mism.numel())
-    return differing
-
-
-def _data(nq, ndb, dim, seed, planted=True):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    db = torch.randn(ndb, dim, generator=g, device=DEV) * (0.3 + 2.0 * torch.rand(ndb, 1, generator=g, device=DEV))
-    qu = torch.nn.functional.normalize(torch.randn(nq, dim, generator=g, device=DEV))
-    if planted and ndb >= 64:
-        # every query has a handful of true neighbours at graded distances, some closer to each other than the screening bound
-        for j in range(6):
-            rows = torch.randint(0, ndb, (nq,), generator=g, device=DEV)
-            noise = torch.nn.functional.normalize(torch.randn(nq, dim, generator=g, device=DEV))
-            db[rows] = (qu + (0.02 + 0.0004 * j) * noise) * (0.5 + j)
-    return qu, db
 
 
 _CASE = {}
@@ -75,8 +32,8 @@ def _case(nq, ndb, dim, metric):
     key = (nq, ndb, dim, metric)
     if key not in _CASE:
         _CASE.clear()
-        qu, db = _data(nq, ndb, dim, nq + ndb + dim)
-        _CASE[key] = (qu, db, _exact64(qu, db, metric))
+        qu, db = R.planted_rows(nq, ndb, dim, nq + ndb + dim)
+        _CASE[key] = (qu, db, R.exact_scores64(qu, db, metric, block=512))
     return _CASE[key]
 
 
@@ -85,17 +42,7 @@ def _as_flat_index_scores_them(qu, db, s, metric):
     scores and their float64 scores"""
     from anyloc_amd import ops
     q = ops.l2norm_rows(qu)
-    return q, (s if torch.equal(q, qu) else _exact64(q, db, metric))
-
-
-def _profiled(fn):
-    from anyloc_amd import ops
-    ops.profile_enable(True); ops.profile_reset()
-    out = fn()
-    torch.cuda.synchronize()
-    prof = ops.profile_dump()
-    ops.profile_enable(False)
-    return out, prof
+    return q, (s if torch.equal(q, qu) else R.exact_scores64(q, db, metric, block=512))
 
 
 def _screened(prof, rescore="topk_screen_rescore"):
@@ -115,7 +62,7 @@ def _three_searches(qu, db, k, metric):
     for tag, fn, rescore in (("one-shot", lambda: ops.topk(qu, db, k, metric, normalize_db=True), "topk_screen_rescore"),
                              ("rows kept", lambda: kept.search(qu, k), "topk_screen_rescore"),
                              ("rows free", lambda: bare.search(qu, k), "topk_screen_rescore_planes")):
-        res, prof = _profiled(fn)
+        res, prof = R.profiled(fn)
         assert _screened(prof, rescore), (tag, sorted(prof))
         out.append((tag, res))
     return out
@@ -139,8 +86,8 @@ def test_slices_of_4096_columns_give_the_lists_of_one_slice(nq, ndb, dim, k, met
         whole = _three_searches(qu, db, k, metric)
     for (tag, (d, i)), (_, (d1, i1)) in zip(sliced, whole):
         ref = s if tag == "one-shot" else s_index
-        _check(d, i, ref, k, metric, f"{tag}, slices of 4096, {nq}x{ndb}x{dim} {metric}")
-        _check(d1, i1, ref, k, metric, f"{tag}, one slice, {nq}x{ndb}x{dim} {metric}")
+        R.check_lists(d, i, ref, k, metric, f"{tag}, slices of 4096, {nq}x{ndb}x{dim} {metric}", cap=0.001)
+        R.check_lists(d1, i1, ref, k, metric, f"{tag}, one slice, {nq}x{ndb}x{dim} {metric}", cap=0.001)
         assert torch.equal(i, i1), tag
         assert float((d - d1).abs().max()) <= BAR[metric], (tag, float((d - d1).abs().max()))
 
@@ -195,7 +142,7 @@ def test_every_slice_width_gives_the_lists_of_one_slice(cols, dim, metric):
     assert (cols // 4 + 511) // 512 in range(nj // 2 + 1, nj + 1) and (min(cols, 32768) // 8 + 511) // 512 in range(nu // 2 + 1, nu + 1)
     _CASE.clear()
     qu, db = _graded(nq, ndb, dim, 1000 + cols // 4096 + (0 if metric == "ip" else 50))
-    s = _exact64(qu, db, metric)
+    s = R.exact_scores64(qu, db, metric, block=512)
     s_index = _as_flat_index_scores_them(qu, db, s, metric)[1]
     print(f"smallest gap among the best {k + 1}: {_no_near_ties(s, k, metric):.2e}, as the index scores them {_no_near_ties(s_index, k, metric):.2e}")
     with ops.options(topk_rescore_cols=cols, **SCREEN):
@@ -206,8 +153,8 @@ def test_every_slice_width_gives_the_lists_of_one_slice(cols, dim, metric):
         whole = _three_searches(qu, db, k, metric)
     for (tag, (d, i)), (_, (d1, i1)) in zip(sliced, whole):
         ref = s if tag == "one-shot" else s_index
-        assert _check(d, i, ref, k, metric, f"{tag}, slices of {cols}, {nq}x{ndb}x{dim} {metric}") == 0
-        assert _check(d1, i1, ref, k, metric, f"{tag}, one slice, {nq}x{ndb}x{dim} {metric}") == 0
+        assert R.check_lists(d, i, ref, k, metric, f"{tag}, slices of {cols}, {nq}x{ndb}x{dim} {metric}", cap=0.001) == 0
+        assert R.check_lists(d1, i1, ref, k, metric, f"{tag}, one slice, {nq}x{ndb}x{dim} {metric}", cap=0.001) == 0
         assert torch.equal(i, i1), tag
         assert float((d - d1).abs().max()) <= BAR[metric], (tag, float((d - d1).abs().max()))
 
@@ -226,17 +173,17 @@ def test_wide_rows_screened_give_the_exact_lists(nq, ndb, dim, k, metric):
     from anyloc_amd import ops
     qu, db, s = _case(nq, ndb, dim, metric)
     with ops.options(**SCREEN):
-        (d, i), prof = _profiled(lambda: ops.topk(qu, db, k, metric, normalize_db=True))
+        (d, i), prof = R.profiled(lambda: ops.topk(qu, db, k, metric, normalize_db=True))
         assert _screened(prof), sorted(prof)
         d_again, i_again = ops.topk(qu, db, k, metric, normalize_db=True)
         assert torch.equal(d, d_again) and torch.equal(i, i_again)
         d_b, i_b = ops.topk(qu, db, k, metric, normalize_db=True, index_base=5000)
         assert torch.equal(torch.where(i_b >= 0, i_b - 5000, i_b), i) and torch.equal(d_b, d)
     with ops.options(topk_screen=0, topk_h3=1):
-        (d0, i0), prof0 = _profiled(lambda: ops.topk(qu, db, k, metric, normalize_db=True))
+        (d0, i0), prof0 = R.profiled(lambda: ops.topk(qu, db, k, metric, normalize_db=True))
     assert "topk_scores_gemm" in prof0 and "topk_screen_gemm" not in prof0, sorted(prof0)
-    n = _check(d, i, s, k, metric, f"screened {nq}x{ndb}x{dim} {metric}")
-    n0 = _check(d0, i0, s, k, metric, f"unscreened {nq}x{ndb}x{dim} {metric}")
+    n = R.check_lists(d, i, s, k, metric, f"screened {nq}x{ndb}x{dim} {metric}", cap=0.001)
+    n0 = R.check_lists(d0, i0, s, k, metric, f"unscreened {nq}x{ndb}x{dim} {metric}", cap=0.001)
     assert float((d - d0).abs().max()) <= BAR[metric]
     assert int((i != i0).sum()) <= n + n0                  # a differing pair differs from the float64 list on one side at least
 
@@ -251,13 +198,13 @@ def test_wide_rows_screened_on_an_index_without_its_rows():
     with ops.options(**SCREEN):
         bare = retrieval.FlatIndex(db, "cosine", True, keep_fp32=False, rescore="planes")
         assert bare.db is None
-        (d, i), prof = _profiled(lambda: bare.search(qu, k))
+        (d, i), prof = R.profiled(lambda: bare.search(qu, k))
         assert _screened(prof, "topk_screen_rescore_planes"), sorted(prof)
         d_again, i_again = bare.search(qu, k)
         assert torch.equal(d, d_again) and torch.equal(i, i_again)
         d1, i1 = ops.topk(q, db, k, "ip", normalize_db=True)
-    n = _check(d, i, s, k, "ip", "rows free, 131 072 columns")
-    n1 = _check(d1, i1, s, k, "ip", "one-shot, 131 072 columns")
+    n = R.check_lists(d, i, s, k, "ip", "rows free, 131 072 columns", cap=0.001)
+    n1 = R.check_lists(d1, i1, s, k, "ip", "one-shot, 131 072 columns", cap=0.001)
     assert float((d - d1).abs().max()) <= BAR["ip"] and int((i != i1).sum()) <= n + n1
 
 
@@ -272,9 +219,9 @@ def test_wide_rows_without_the_wait():
     qu[7] = 0.0
     with ops.options(**SCREEN):
         d, i = ops.topk(qu, db, k, "ip", normalize_db=True, no_wait=True)
-        (d_w, i_w), prof = _profiled(lambda: ops.topk(qu, db, k, "ip", normalize_db=True))
+        (d_w, i_w), prof = R.profiled(lambda: ops.topk(qu, db, k, "ip", normalize_db=True))
         assert "topk_screen_gemm" in prof and "topk_scores_gemm" in prof, sorted(prof)     # the waiting call falls back for everyone
-        (d_c, i_c), prof_c = _profiled(lambda: ops.topk(clean, db, k, "ip", normalize_db=True))
+        (d_c, i_c), prof_c = R.profiled(lambda: ops.topk(clean, db, k, "ip", normalize_db=True))
         assert _screened(prof_c), sorted(prof_c)
     with ops.options(topk_screen=0, topk_h3=1):
         d0, i0 = ops.topk(qu, db, k, "ip", normalize_db=True)
@@ -285,7 +232,7 @@ def test_wide_rows_without_the_wait():
     assert torch.equal(d[keep], d_c[keep]) and torch.equal(i[keep], i_c[keep])
     s_z = s.clone()
     s_z[7] = 0.0
-    _check(d, i, s_z, k, "ip", "no wait, one zero query")
+    R.check_lists(d, i, s_z, k, "ip", "no wait, one zero query", cap=0.001)
 
 
 def test_narrow_rows_under_default_options_are_unchanged():
@@ -297,13 +244,13 @@ def test_narrow_rows_under_default_options_are_unchanged():
         assert ops.get_option("topk_rescore_cols") == 4096
     assert ops.get_option("topk_rescore_cols") == 0
     qu, db, s = _case(nq, ndb, dim, "ip")
-    (d, i), prof = _profiled(lambda: ops.topk(qu, db, k, "ip", normalize_db=True))
+    (d, i), prof = R.profiled(lambda: ops.topk(qu, db, k, "ip", normalize_db=True))
     assert _screened(prof), sorted(prof)
     d_again, i_again = ops.topk(qu, db, k, "ip", normalize_db=True)
     assert torch.equal(d, d_again) and torch.equal(i, i_again)
     with ops.options(topk_screen=0):
         d0, i0 = ops.topk(qu, db, k, "ip", normalize_db=True)
-    n = _check(d, i, s, k, "ip", "narrow rows, defaults")
-    n0 = _check(d0, i0, s, k, "ip", "narrow rows, unscreened")
+    n = R.check_lists(d, i, s, k, "ip", "narrow rows, defaults", cap=0.001)
+    n0 = R.check_lists(d0, i0, s, k, "ip", "narrow rows, unscreened", cap=0.001)
     assert float((d - d0).abs().max()) <= BAR["ip"] and int((i != i0).sum()) <= n + n0
     _CASE.clear()

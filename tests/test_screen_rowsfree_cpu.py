@@ -15,6 +15,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import split_fp16_study as sh  # noqa: E402
+from _retrieval_refs import planted_rows  # noqa: E402
 
 ERR_ARG, ERR_WORKSPACE = -1, -2
 
@@ -88,18 +89,6 @@ def test_python_surface():
     assert list(inspect.signature(ops.topk_index_build_range).parameters) == ["index", "rows", "row0", "ndb"]
 
 
-def _data(nq, ndb, dim, seed):
-    """tests/test_gpu_screen.py::_data on the host generator."""
-    g = torch.Generator().manual_seed(seed)
-    db = torch.randn(ndb, dim, generator=g) * (0.3 + 2.0 * torch.rand(ndb, 1, generator=g))
-    qu = torch.nn.functional.normalize(torch.randn(nq, dim, generator=g))
-    for j in range(6):
-        rows = torch.randint(0, ndb, (nq,), generator=g)
-        noise = torch.nn.functional.normalize(torch.randn(nq, dim, generator=g))
-        db[rows] = (qu + (0.02 + 0.0004 * j) * noise) * (0.5 + j)
-    return qu, db
-
-
 @pytest.mark.parametrize("nq,ndb,dim", [(64, 4000, 4096), (16, 600, 49152), (64, 4000, 512)])
 def test_scores_over_the_rows_the_planes_hold(nq, ndb, dim):
     """(hi + lo) 2^-e: every element within 2^-23 of its row's maximum.  The row is scaled so that its maximum lies in
@@ -107,7 +96,7 @@ def test_scores_over_the_rows_the_planes_hold(nq, ndb, dim):
     most half an ulp of a number below 8, 2^-9 (8 itself is exact) -- against a maximum of at least 2^14.  The normalised
     float64 score of a unit query then moves by < 1e-7 (measured 3.5e-9 / 9.6e-10 / 9.7e-9 at these widths): thirty times under
     the 3e-6 bar of the retrieval tests."""
-    qu, db = _data(nq, ndb, dim, nq + ndb + dim)
+    qu, db = planted_rows(nq, ndb, dim, nq + ndb + dim, device="cpu")
     h, l, scale = sh.split_h2(db)
     amax = db.abs().amax(dim=1, keepdim=True).double()
     held = (h.double() + l.double()) / scale.double()
