@@ -627,6 +627,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_h3_kernel(const unsigned
       const int64_t gk = g_first + t;
       const unsigned char* Ks = ah_smem + stage * KS * AH_STAGE;
       const unsigned char* Vs = Ks + 8192;
+      const bool edge = gk == g_first || gk == g_last;      // wave-uniform: only the image's first / last key group
       float fk, fv;
       if (ng <= 64) {                   // wave-uniform lane index: v_readlane, no memory access in the loop
         fk = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, fk_lane), t));
@@ -654,6 +655,33 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_h3_kernel(const unsigned
           sacc[qg] = ANYLOC_MFMA_F16(kf[0], qf[qg][0][s], sacc[qg]);
         }
       }
+      if (edge) {
+        // The masked keys of a boundary group are ANOTHER image's rows.  Their P is 0 below, but 0 x NaN is NaN: their V values
+        // are cleared in the staged tile, so that a NaN or an infinity in one image never reaches its batch neighbour's output.
+        // Done here -- behind the score MFMAs, whose latency covers the LDS round trip, and before the V fragments are live -- by
+        // every wave that reads the tile, ahead of its own fragment reads (LDS serves a wave in order).  Lane = row d of
+        // V^T; its 16-byte chunk (hh, s2) holds the keys (j & 3) + 8 (2 s2 + (j >> 2)) + 4 hh, j = 0 .. 7 (qkv_planes_kernel).
+        // (key wave kw reads tile kw of the step: the same offset as in k_lane / v_lane).  The stage was published by the
+        // __syncthreads that ended the previous tile (or the prologue's), the DMA issued above fills the OTHER stage, and the
+        // read-modify-write races only with the same AND by the workgroup's other query waves: idempotent, same bytes.
+        asm volatile("" ::: "memory");
+        const unsigned off = (unsigned)(-(int)(r0 - gk * 32)), len = (unsigned)(r1 - r0);   // key ko is this image's: ko + off < len
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          attn_u32x4 keep;
+#pragma unroll
+          for (int w = 0; w < 4; ++w) {
+            const unsigned ko = (unsigned)(((2 * w) & 3) + 8 * (2 * (c & 1) + (w >> 1)) + 4 * (c >> 1));
+            keep[w] = (ko + off < len ? 0x0000ffffu : 0u) | (ko + 1 + off < len ? 0xffff0000u : 0u);
+          }
+#pragma unroll
+          for (int pl = 0; pl < 2; ++pl) {
+            attn_u32x4* vp = reinterpret_cast<attn_u32x4*>(const_cast<unsigned char*>(Vs) + kw * AH_STAGE + pl * 4096 + lane * 64 + ((c ^ ((lane >> 2) & 3)) << 4));
+            *vp = *vp & keep;
+          }
+        }
+        asm volatile("" ::: "memory");
+      }
       // V^T fragments: lane (d = db*32 + ql, half h2), k-step s2: the 8 keys register r = 8 s2 + j of the score block holds
       attn_u32x4 vf[2][2][2];
 #pragma unroll
@@ -664,7 +692,6 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_h3_kernel(const unsigned
           for (int s2 = 0; s2 < 2; ++s2)                    // d = 32 db + ql: (d >> 2) & 3 does not depend on db
             vf[pl][db][s2] = *reinterpret_cast<const attn_u32x4*>(Vs + pl * 4096 + db * 2048 + v_lane[s2]);
         }
-      const bool edge = gk == g_first || gk == g_last;      // wave-uniform: only the image's first / last key group
       // O is kept in units of the current V tile's scale: moving to a tile with another scale is a power-of-two factor
       const float vratio = (KS == 1 ? t == 0 : first) ? 1.0f : fv_run * ah_pow2_recip(fv);
       fv_run = fv;
@@ -806,9 +833,11 @@ __global__ __launch_bounds__(256) void qkv_planes_kernel(const float* __restrict
   float v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) v[j] = row < rows ? qkv[row * 3 * (int64_t)D + (int64_t)part * D + h * 64 + c8 + j] : 0.f;
+  // the tile's scale comes from its FINITE values: a tile at an image boundary holds rows of two images, and the NaN (fmaxf
+  // drops it) or the infinity of one image must not move the scale of the other image's rows (2^-100 would flush them to zero)
   float amax = 0.f;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
+  for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]) < INFINITY ? fabsf(v[j]) : 0.f);
   amax = wave_max(amax);
   if (lane == 0) red[wave] = amax;
   __syncthreads();

@@ -179,6 +179,9 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// torch's clamp_min (F.normalize's denominator, max(||x||, eps)): a NaN norm stays NaN, so a row that holds a NaN comes out
+// all NaN, as the reference's does.  fmaxf(NaN, eps) is eps: the row's other elements would come out finite, x / eps.
+__device__ __forceinline__ float clamp_min_nan(float v, float lo) { return v < lo ? lo : v; }
 
 // A GATED launch (topk.hip, ANYLOC_TOPK_NO_WAIT): the host enqueues it without knowing whether it is needed; a device word written
 // by an earlier kernel of the stream decides.  Asked at kernel entry, before any barrier or LDS use; the answer is the same for

@@ -104,9 +104,16 @@ __global__ __launch_bounds__(256) void row_amax_sq_kernel(const float* __restric
   __syncthreads();
   if (threadIdx.x == 0) {
     float iv;
-    h2_row_scale(fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3])), iv);
+    const float m = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
+    h2_row_scale(m, iv);
+    float sq = (red_s[0] + red_s[1]) + (red_s[2] + red_s[3]);
+    // A row that holds an infinity has no two-term image: its residual plane would hold inf - inf.  Its 2^-e and its sum of
+    // squares become NaN, so every score of the row is NaN on every kernel that reads the image (leading plane alone or both),
+    // and the row stays out of the screened search's largest-norm bound (scores_screen.hip, ss_max).  A NaN element needs
+    // nothing: fmaxf drops it from m, it stays NaN in the planes and makes the sum NaN by itself.
+    if (!(m < INFINITY)) iv = sq = __uint_as_float(0x7fc00000u);
     inv[blockIdx.x] = iv;
-    if (ss) ss[blockIdx.x] = (red_s[0] + red_s[1]) + (red_s[2] + red_s[3]);
+    if (ss) ss[blockIdx.x] = sq;
   }
 }
 

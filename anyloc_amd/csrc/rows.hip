@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* x, int64_
       const f32x4 v = reinterpret_cast<const f32x4*>(xr)[i];
       ss += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
     }
-    const float nrm = fmaxf(sqrtf(block_sum(ss, red)), eps);
+    const float nrm = clamp_min_nan(sqrtf(block_sum(ss, red)), eps);
     for (int64_t i = threadIdx.x; i < n4; i += 256) {
       f32x4 v = reinterpret_cast<const f32x4*>(xr)[i];
       v[0] /= nrm; v[1] /= nrm; v[2] /= nrm; v[3] /= nrm;
@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* x, int64_
     }
   } else {
     for (int64_t i = threadIdx.x; i < dim; i += 256) ss += xr[i] * xr[i];
-    const float nrm = fmaxf(sqrtf(block_sum(ss, red)), eps);
+    const float nrm = clamp_min_nan(sqrtf(block_sum(ss, red)), eps);
     for (int64_t i = threadIdx.x; i < dim; i += 256) orow[i] = xr[i] / nrm;
   }
 }
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void facet_rows_kernel(const float* __restrict
       const f32x4 v = s[i];
       ss += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
     }
-    nrm = fmaxf(sqrtf(block_sum(ss, red)), eps);
+    nrm = clamp_min_nan(sqrtf(block_sum(ss, red)), eps);
   }
   for (int i = threadIdx.x; i < n4; i += 256) {
     f32x4 v = s[i];
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256) void facet_rows_ragged_kernel(const float* __r
       const f32x4 v = s[k];
       ss += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
     }
-    nrm = fmaxf(sqrtf(block_sum(ss, red)), eps);
+    nrm = clamp_min_nan(sqrtf(block_sum(ss, red)), eps);
   }
   for (int k = threadIdx.x; k < n4; k += 256) {
     f32x4 v = s[k];

@@ -561,6 +561,9 @@ __global__ void rho_from_resid_kernel(const float* __restrict__ resid_sq, const 
   if (rho_max && (threadIdx.x & 63) == 0) atomicMax(rho_max, __float_as_uint(m));
 }
 
+// (fmaxf drops a NaN: the raw sums of squares go through here too (ss_max), and a row that holds a NaN or an infinity arrives
+// with a NaN sum -- row_amax_sq_kernel, gemm_h3.hip -- so one such row does not make dmax, and with it every query's margin,
+// non-finite.  A finite row whose sum of squares overflows still arrives as +inf: every column a candidate, the call falls back.)
 __global__ void rho_max_kernel(const float* __restrict__ rho, int64_t n, unsigned* __restrict__ rho_max) {
   float m = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = fmaxf(m, rho[i]);

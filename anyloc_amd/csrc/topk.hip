@@ -224,7 +224,7 @@ __global__ void dbnorm_kernel(const float* __restrict__ ss, int64_t n, float* __
                               const int* __restrict__ gate) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n || gate_closed(gate)) return;
-  const float d = fmaxf(sqrtf(ss[i]), 1e-12f);
+  const float d = clamp_min_nan(sqrtf(ss[i]), 1e-12f);
   dnorm[i] = d;
   dn[i] = (ss[i] / d) / d;
 }

@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void assign_kernel(const float* __restrict__ s
     if (bi == 0x7fffffff) bi = 0;      // a row of NaN scores: no comparison ever succeeds
     lab32[tok] = bi;
     if (lab64) lab64[tok] = bi;
-    if (nrm) nrm[tok] = norm_descs ? fmaxf(sqrtf(rowsq[tok]), 1e-12f) : 1.0f;
+    if (nrm) nrm[tok] = norm_descs ? clamp_min_nan(sqrtf(rowsq[tok]), 1e-12f) : 1.0f;
   }
 }
 
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(1024) void vlad_finalize_kernel(float* __restrict__
       for (int i = lane; i < D; i += 64) { const float t = p[(int64_t)k * D + i]; ss += t * t; }
       ss = wave_sum(ss);
     }
-    if (lane == 0) knorm[k] = intra ? fmaxf(sqrtf(ss), 1e-12f) : 1.0f;
+    if (lane == 0) knorm[k] = intra ? clamp_min_nan(sqrtf(ss), 1e-12f) : 1.0f;
   }
   __syncthreads();
   const int total = K * D;
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(1024) void vlad_finalize_kernel(float* __restrict__
   float tot = 0.f;
 #pragma unroll
   for (int w = 0; w < 16; ++w) tot += red[w];
-  const float gn = fmaxf(sqrtf(tot), 1e-12f);
+  const float gn = clamp_min_nan(sqrtf(tot), 1e-12f);
   for (int i = threadIdx.x; i < total; i += 1024) p[i] = (p[i] / knorm[i / D]) / gn;
 }
 
@@ -272,17 +272,17 @@ __global__ __launch_bounds__(256) void soft_weights_kernel(float* __restrict__ s
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   float* s = scores + i * kpad;
-  const float xn = fmaxf(sqrtf(rowsq[i]), 1e-8f);
+  const float xn = clamp_min_nan(sqrtf(rowsq[i]), 1e-8f);
   float m = -INFINITY;
   for (int k = 0; k < K; ++k) {
-    const float cs = temp * (s[k] / (xn * fmaxf(sqrtf(csq[k]), 1e-8f)));
+    const float cs = temp * (s[k] / (xn * clamp_min_nan(sqrtf(csq[k]), 1e-8f)));
     s[k] = cs;
     m = fmaxf(m, cs);
   }
   float z = 0.f;
   for (int k = 0; k < K; ++k) { const float e = expf(s[k] - m); s[k] = e; z += e; }
   for (int k = 0; k < K; ++k) s[k] /= z;
-  nrm[i] = norm_descs ? fmaxf(sqrtf(rowsq[i]), 1e-12f) : 1.0f;
+  nrm[i] = norm_descs ? clamp_min_nan(sqrtf(rowsq[i]), 1e-12f) : 1.0f;
 }
 
 // scores[n,k] = x_n . c_k (raw centres) and rowsq[n] = ||x_n||^2 for the soft-max: one block per token, wave w takes the
@@ -368,7 +368,7 @@ __global__ __launch_bounds__(256) void residuals_kernel(const float* __restrict_
   if (norm_descs) {
     float ss = 0.f;
     for (int i = threadIdx.x; i < D; i += 256) ss += r[i] * r[i];
-    den = fmaxf(sqrtf(block_sum256(ss, red)), 1e-12f);
+    den = clamp_min_nan(sqrtf(block_sum256(ss, red)), 1e-12f);
   }
   float* o = out + n * (int64_t)K * D;
   const int d4 = D >> 2;
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(256) void assigned_prep_kernel(const float* __restr
     const float* r = x + t * D;
     float ss = 0.f;
     for (int i = threadIdx.x; i < D; i += 256) ss += r[i] * r[i];
-    den = fmaxf(sqrtf(block_sum256(ss, red)), 1e-12f);
+    den = clamp_min_nan(sqrtf(block_sum256(ss, red)), 1e-12f);
   }
   if (threadIdx.x == 0) {
     nrm[t] = den;

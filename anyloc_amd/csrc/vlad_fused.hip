@@ -213,7 +213,7 @@ __global__ __launch_bounds__(NTH) void vlad_fused_kernel(FusedArgs a) {
         float q = 0.f;
 #pragma unroll
         for (int w2 = 0; w2 < SW; ++w2) q += rsqp[w2 * TT + row];
-        nrm[row] = a.norm_descs ? fmaxf(sqrtf(q), 1e-12f) : 1.0f;
+        nrm[row] = a.norm_descs ? clamp_min_nan(sqrtf(q), 1e-12f) : 1.0f;
       }
       s += my_bias;
       float best = (k < a.K) ? s : -INFINITY;
@@ -328,7 +328,7 @@ __global__ __launch_bounds__(NTH) void vlad_fused_kernel(FusedArgs a) {
   for (int m = 0; m < NV; ++m) ss += acc[m][0] * acc[m][0] + acc[m][1] * acc[m][1] + acc[m][2] * acc[m][2] + acc[m][3] * acc[m][3];
   ss = half_wave_sum(ss);
   if (a.intra) {
-    const float kn = fmaxf(sqrtf(ss), 1e-12f);
+    const float kn = clamp_min_nan(sqrtf(ss), 1e-12f);
     ss = 0.f;
 #pragma unroll
     for (int m = 0; m < NV; ++m) {
@@ -342,7 +342,7 @@ __global__ __launch_bounds__(NTH) void vlad_fused_kernel(FusedArgs a) {
   float tot = 0.f;
 #pragma unroll
   for (int k = 0; k < 32; ++k) tot += red[k];
-  const float gn = fmaxf(sqrtf(tot), 1e-12f);
+  const float gn = clamp_min_nan(sqrtf(tot), 1e-12f);
   if (k_live) {
     float* o = a.out + (unit * a.K + ok_) * (int64_t)D + 4 * oj;
 #pragma unroll
@@ -753,7 +753,7 @@ __global__ __launch_bounds__(64 * SW) void fused3_kernel(FusedArgs a) {
         amb[row] = close ? mask : 0u;
         lab[row] = live ? bi : -1;
         // (the INVERSE: one IEEE division per row here instead of one per row and LANE in the gather -- the same value)
-        if (!KMEANS) nrm[row] = a.norm_descs ? 1.0f / fmaxf(xn, 1e-12f) : 1.0f;
+        if (!KMEANS) nrm[row] = a.norm_descs ? 1.0f / clamp_min_nan(xn, 1e-12f) : 1.0f;
         if (live && !close && a.lab64) a.lab64[n0 + (int64_t)t * TT + row] = bi;
       }
     }
@@ -1064,7 +1064,7 @@ __global__ __launch_bounds__(64 * SW) void fused3_kernel(FusedArgs a) {
         float tot = 0.f;
 #pragma unroll
         for (int w2 = 0; w2 < SW; ++w2) tot += red[w2 * 32 + k];
-        const float kn = fmaxf(sqrtf(tot), 1e-12f);
+        const float kn = clamp_min_nan(sqrtf(tot), 1e-12f);
         float v[CW];
         acc_get(k, v);
 #pragma unroll
@@ -1087,7 +1087,7 @@ __global__ __launch_bounds__(64 * SW) void fused3_kernel(FusedArgs a) {
     float tot = 0.f;
 #pragma unroll
     for (int w2 = 0; w2 < SW; ++w2) tot += red[w2];
-    const float gn = fmaxf(sqrtf(tot), 1e-12f);
+    const float gn = clamp_min_nan(sqrtf(tot), 1e-12f);
     const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(a.out + unit * kd), 0, (int)(kd * 4), 0x00020000);
 #pragma unroll 1
     for (int k = 0; k < Kc; ++k) {

@@ -66,6 +66,32 @@
  *     tests/test_addressing_limits_cpu.py calls every one from its far side, tests/test_gpu_addressing.py runs the near side
  *     and the entry points at 4 - 8 GiB.  Row counts of the row-wise calls (l2norm, layernorm, the splitters, VLAD and k-means
  *     tokens, top-k queries) are below 2^31.
+ *   - Non-finite values.  No entry point rejects a NaN or an infinity; what it does with one is this (audit with file:line per
+ *     operand: profiles/nonfinite_audit.md; tests/test_gpu_nonfinite.py and tests/test_gpu_scaling.py hold the ops to it):
+ *       1. Containment.  A non-finite value spoils only the outputs that mathematically depend on it; every other output has
+ *          the bits it has when the offending unit holds ordinary finite values.  The unit is a row of A (the GEMMs, the
+ *          splitters, layernorm, l2norm_rows, rope_rows), an image (attention, VLAD, pooling, the ViT forward), a query
+ *          (top-k), a row to be labelled (k-means, VLAD assignment); a non-finite weight row n or bias element n of a GEMM
+ *          spoils output column n.  Two shared scales are part of the design and bound this: anyloc_attention_h3 and the h3
+ *          forward scale q, k and v per (head, 32-row group), and a group at an image boundary holds rows of two images -- the
+ *          scale is taken from the group's FINITE values (anyloc_attention_h3's own quantiser) or from its non-NaN values
+ *          (the QKV epilogue of the forward, which a LayerNorm'd row reaches as NaN, never as an infinity), and the V values
+ *          of another image's keys are cleared before they meet this image's zero probabilities.
+ *       2. Propagation.  In the spoiled outputs NaN stands where the float64 evaluation of the same formula has NaN (a norm
+ *          clamp max(||x||, eps) keeps a NaN norm, as torch.clamp does: the normalised row is all NaN).  The two split
+ *          arithmetics are part of "the same formula": the residual plane of an infinity is inf - inf, so on the split-bf16
+ *          and two-term fp16 kernels (anyloc_split_x3 / _h2 and everything that reads their images, the x6 and h3 attention,
+ *          every top-k path but the fp32 score GEMM, a prepared index) an infinite element counts as a NaN element.
+ *       3. Selections never pick a NaN.  +-inf compare as numbers; a NaN score never beats a non-NaN one -- torch.max and
+ *          torch.sort rank NaN FIRST, this library ranks it last, on purpose.  A row whose scores are all NaN gets label 0.
+ *          A database row whose score is NaN is never listed; neither is one whose score is -inf.  A list with fewer than k
+ *          listable rows ends in padding, index -1 with distance -inf (inner product) or +inf (L2) -- on every top-k path,
+ *          screened or not, so a NaN query's list is all padding.  Every label lies in [0, K), every index in
+ *          [index_base, index_base + ndb) or is -1.
+ *       4. Powers of two are exact.  Scaling an input unit by 2^s scales its outputs by the same power, or leaves them
+ *          (the normalising ops), bit for bit, as long as nothing overflows or becomes subnormal.  Exceptions, each with
+ *          an eps or an approximate reciprocal in its formula, are listed in the audit.
+ *     Not covered: fp32 overflow of finite inputs (|x| beyond ~2^60) and the flushing of subnormals.
  *   - return value: 0 on success, a negative anyloc_status otherwise;
  *     anyloc_last_error() returns a thread-local description of the last
  *     failure.  No C++ exception crosses the ABI.
