@@ -55,6 +55,19 @@
  *     *_workspace_bytes() functions answer hold for any such pointer.
  *     tests/test_gpu_guard_bands.py holds every entry point to this between guard
  *     bands, at exactly the documented sizes.
+ *     A call initialises every word of the workspace it depends on.  The workspace may
+ *     hold anything at entry -- another call's leftovers, another shape's or another
+ *     route's, garbage -- and no result depends on it, bit for bit: the arrival tickets,
+ *     row maxima, candidate counts, overflow flags and running maxima a kernel expects
+ *     to find initialised are cleared or stored by THIS call, over the extent THIS
+ *     call's shape and route give them (profiles/workspace_state_audit.md lists each
+ *     word with the line that initialises it; the paths that audit lists as not
+ *     reproducible run to run keep their own, weaker promise -- none today).  The same
+ *     holds for a ViT handle between two forwards (the telemetry target, the
+ *     exact-quantiser switches and the registers are read, never left changed, by a
+ *     forward) and for the options after anyloc_reset_options.
+ *     tests/test_gpu_history.py holds every entry point to this: behind fill patterns,
+ *     behind other ops, behind the same op at another shape or route.
  *     anyloc_gemm_nt reads the rows of one tile through 2 GiB of 32-bit buffer addressing: (min(tile rows, rows) - 1) * ld * 4
  *     + K * 4 < 2^31 for A (tiles of 64, 128 or 256 rows: anyloc_gemm_plan_describe) and for W (tiles of 32, 64 or 128 columns);
  *     a wider row stride is ANYLOC_ERR_INVALID_ARG.
